@@ -3,6 +3,8 @@
 2 ch 44.1 kHz -> 48 kHz (BASELINE.json configs[1]), inputs resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W]            headline (FIR, weak scaling)
+  python bench.py --full                                         ... with everything it is read against (below)
+  python bench.py --dump-outputs DIR                             ... and the last timed step's outputs as DIR/*.npy
   python bench.py --config c4 [--gpus N]                         BASELINE config 4 (strong scaling)
   python bench.py --path fft                                     ResamplerFft line alone
 
@@ -17,9 +19,12 @@ batch of them (weak scaling: every rank owns `--streams` streams; no data-path c
 `python -m torch.distributed.run` (RANK / WORLD_SIZE in the environment) the process is one rank.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, timed with HIP events on the
-launch stream inside the library (rsmp_fir_set_profiling); `cpu_baseline` is the oracle's AVX+FMA
-restatement of the reference path on the host cores; `secondary` (N = 1 only) carries the FFT
-path, the exact-f32 and vector FIR kernels, the cold-plan / distinct-state FIR step and config 4.
+launch stream inside the library (rsmp_fir_set_profiling).  A plain run does only what that line needs:
+set-up, spin-up and warmup, the K timed steps, the outputs (--dump-outputs) and the line.  --full adds
+what takes runs of its own: `cpu_baseline`, the oracle's AVX+FMA restatement of the reference path on
+the host cores; `secondary` (N = 1 only), the FFT path, the exact-f32 and vector FIR kernels, the
+cold-plan / distinct-state FIR step and configs 4 and 5; the device-copy ceiling beside `roofline`
+and the host cost of a step on an idle GPU.
 """
 from __future__ import annotations
 
@@ -662,9 +667,10 @@ def bench_fft(ctx: Ctx, args, steps: int, warmup: int, with_cpu: bool):
                      "kernel_ms_max": round(float(np.max(k)), 4), "kernel_launches_timed": len(k),
                      "algorithmic_bytes": int(alg_bytes)},
     }
-    copy_gbs = device_copy_gbs(ctx, alg_bytes / 2)
-    line["roofline"]["device_copy"] = round(copy_gbs, 1)
-    line["roofline"]["frac_of_device_copy"] = round(achieved / copy_gbs, 4)
+    if args.full:
+        copy_gbs = device_copy_gbs(ctx, alg_bytes / 2)
+        line["roofline"]["device_copy"] = round(copy_gbs, 1)
+        line["roofline"]["frac_of_device_copy"] = round(achieved / copy_gbs, 4)
     if with_cpu:
         line["cpu_baseline"] = cpu_baseline_fft(min(args.cpu_seconds, 6.0), min(args.cpu_all_cores_seconds, 4.0))
     return line
@@ -807,10 +813,12 @@ def bench_fir(ctx: Ctx, args):
               "periodic": ra.FirKernel.Periodic, "periodic-vector": ra.FirKernel.PeriodicVector,
               "periodic-f32": ra.FirKernel.PeriodicF32}[args.kernel]
     handles, batch = make_fir_batch(ctx, ra, S, N, args.chunk, kernel)
+    last = [None]                         # the counts of the latest step (--dump-outputs)
 
     def step():
         batch.reset()                     # a fresh stream per step (a new file)
-        return batch.resample_bulk_device(args.chunk, ctx.stream)
+        last[0] = batch.resample_bulk_device(args.chunk, ctx.stream)
+        return last[0]
 
     t_plan0 = time.perf_counter()
     consumed, produced = step()          # first step also builds the plan / class table
@@ -827,21 +835,24 @@ def bench_fir(ctx: Ctx, args):
     dt, host_dt = timed(ctx, step, args.steps, 1 if args.warmup > 0 else 0)
     k_ms, k_launches = handles[0].mean_kernel_ms()
     handles[0].set_profiling(False)
-    # what a step costs the host when it does not wait for the GPU (in the timed loop the enqueue runs at
-    # most a launch or two ahead, so `host_enqueue_ms_per_step` there is mostly back-pressure)
-    host_idle = 0.0
-    for _ in range(10):
-        ctx.torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        host_idle += time.perf_counter() - t1
-    ctx.torch.cuda.synchronize()
-
+    if args.dump_outputs and ctx.rank == 0:
+        dump_fir_outputs(ctx, args.dump_outputs, batch._keep[1], *last[0])
     values_in_per_step = S * CHANNELS * N            # per rank
     values_out_per_step = int(produced.sum())
     alg_bytes = 4.0 * (values_in_per_step + values_out_per_step) + 4.0 * 1024 * 128
     achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-    copy_gbs = device_copy_gbs(ctx, alg_bytes / 2)
+    host_idle = copy_gbs = None
+    if args.full:
+        # what a step costs the host when it does not wait for the GPU (in the timed loop the enqueue runs at
+        # most a launch or two ahead, so `host_enqueue_ms_per_step` there is mostly back-pressure)
+        host_idle = 0.0
+        for _ in range(10):
+            ctx.torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            host_idle += time.perf_counter() - t1
+        ctx.torch.cuda.synchronize()
+        copy_gbs = device_copy_gbs(ctx, alg_bytes / 2)
     variant = handles[0].kernel_variant()
     line = {
         "metric": "Msamples/s (in) 44.1k->48k FIR 128-tap",
@@ -867,7 +878,6 @@ def bench_fir(ctx: Ctx, args):
             "plan_cold_ms": round(plan_cold_ms, 2),
             "spinup_s": args.spinup_seconds,
             "host_enqueue_ms_per_step": round(host_dt / args.steps * 1e3, 4),
-            "host_cost_ms_per_step_gpu_idle": round(host_idle / 10 * 1e3, 4),
             "feed": "resident per GPU (no data-path collective)",
         },
         "roofline": {
@@ -881,15 +891,37 @@ def bench_fir(ctx: Ctx, args):
             "kernel_ms": round(k_ms, 4),
             "kernel_launches_timed": int(k_launches),
             "algorithmic_bytes": int(alg_bytes),
-            # a plain device copy of the same volume on this GPU (read + written GB/s) and the kernel against it
-            "device_copy": round(copy_gbs, 1),
-            "frac_of_device_copy": round(achieved / copy_gbs, 4) if copy_gbs else None,
             # useful f32 FMAs (128 taps per output value), T/s
             "fma_per_s": round(values_out_per_step * 128 / (k_ms * 1e-3) / 1e12, 2),
         },
     }
+    if args.full:
+        line["config"]["host_cost_ms_per_step_gpu_idle"] = round(host_idle / 10 * 1e3, 4)
+        # a plain device copy of the same volume on this GPU (read + written GB/s) and the kernel against it
+        line["roofline"]["device_copy"] = round(copy_gbs, 1)
+        line["roofline"]["frac_of_device_copy"] = round(achieved / copy_gbs, 4) if copy_gbs else None
     del batch, handles
     return line
+
+
+def dump_fir_outputs(ctx: Ctx, out_dir: str, d_outs, consumed, produced) -> None:
+    """--dump-outputs: what a caller of the headline launch receives from its last timed step, as float32 / float64 .npy
+    files (about 26 MB at the default size; output values 48 MiB at most): the per-stream counts, stream 0's output in full
+    (its first 8 Mi values at most) and the same fixed, seeded sample of positions from every stream's output."""
+    torch = ctx.torch
+    os.makedirs(out_dir, exist_ok=True)
+    consumed, produced = np.array(consumed, np.float64), np.array(produced, np.float64)
+    np.save(os.path.join(out_dir, "consumed.npy"), consumed)
+    np.save(os.path.join(out_dir, "produced.npy"), produced)
+    n0 = min(int(produced[0]), 8 << 20)
+    np.save(os.path.join(out_dir, "output_stream0.npy"), d_outs[0][:n0].cpu().numpy())
+    n_min = int(produced.min())
+    k = min(n_min, 1 << 16, max(1, (16 << 20) // (4 * len(d_outs))))
+    idx = np.sort(np.random.default_rng(1234).choice(n_min, size=k, replace=False))
+    d_idx = torch.from_numpy(idx).to(ctx.dev)
+    sample = torch.stack([d[:n_min].index_select(0, d_idx) for d in d_outs]) if k else torch.zeros(len(d_outs), 0)
+    np.save(os.path.join(out_dir, "output_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "output_sample.npy"), sample.cpu().numpy())
 
 
 def secondary_lines(ctx: Ctx, args):
@@ -1165,12 +1197,21 @@ def main() -> int:
     ap.add_argument("--spinup-seconds", type=float, default=1.0,
                     help="untimed steps run before the --warmup steps until this much time has passed: "
                          "the clock governor needs ~50 ms of load to leave its idle state (0 = off)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the line is read against, in runs of their own: CPU baselines, secondary "
+                         "figures (FFT, other kernels, channel counts, configs 4 and 5), the device-copy ceiling")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary figures")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="headline path: write the last timed step's counts and outputs (a fixed sample) as DIR/*.npy")
     ap.add_argument("--kernel", choices=["auto", "generic", "periodic", "periodic-vector", "periodic-f32"], default="auto")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.path != "fir" or args.config != "c2"):
+        ap.error("--dump-outputs writes the headline path's outputs (not --path fft / --config c4 / c5)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args)       # nothing below has run: this process never touches the GPU
 
@@ -1182,14 +1223,14 @@ def main() -> int:
 
     ctx = Ctx(args)
     if args.path == "fft":
-        line = bench_fft(ctx, args, args.steps, args.warmup, with_cpu=(not args.no_cpu and ctx.world == 1))
+        line = bench_fft(ctx, args, args.steps, args.warmup, with_cpu=(args.full and not args.no_cpu and ctx.world == 1))
     elif args.config == "c4":
         line = bench_c4(ctx, args, args.steps, args.warmup)
     elif args.config == "c5":
         line = bench_c5(ctx, args, args.steps, args.warmup)
     else:
         line = bench_fir(ctx, args)
-        if ctx.world == 1 and ctx.rank == 0:
+        if args.full and ctx.world == 1 and ctx.rank == 0:
             if not args.no_cpu:
                 line["cpu_baseline"] = cpu_baseline_fir(args.frames, args.cpu_seconds, args.cpu_all_cores_seconds)
             if not args.no_secondary:

@@ -9,7 +9,7 @@ OUT="$R/gpurun_out/$TAG"
 SUM="$OUT/summary"
 mkdir -p "$SUM"
 cd /tmp && export TMPDIR=/tmp
-python3 "$R/bench.py" --path fft --steps 20 --warmup 3 > "$SUM/bench_fft.json" 2> "$OUT/bench_fft.err"
+python3 "$R/bench.py" --path fft --full --steps 20 --warmup 3 > "$SUM/bench_fft.json" 2> "$OUT/bench_fft.err"
 python3 "$R/tools/fft_channels_bench.py" > "$SUM/fft_channels_bench.txt" 2> "$OUT/fft_channels_bench.err"
 python3 "$R/tools/fft_pairs_bench.py" --all > "$SUM/fft_pairs_bench.txt" 2> "$OUT/fft_pairs_bench.err"
 timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_fft" -- python3 "$R/bench.py" --path fft --steps 20 --warmup 3 --no-cpu \

@@ -2,7 +2,7 @@
 # tools/profile_round.sh <tag> -- collects the rocprofv3 evidence kept under profiles/<tag>/ (run on the GPU
 # box through gpurun; raw output goes to gpurun_out/<tag>/, the summaries to gpurun_out/<tag>/summary/, which
 # is what gets copied to profiles/<tag>/):
-#   1. bench.py as the driver runs it (headline line incl. cpu_baseline and `secondary`)     -> bench_n1.json
+#   1. bench.py --full (headline line incl. cpu_baseline and `secondary`)                    -> bench_n1.json
 #      bench.py --path fft / --config c4 / --config c5                                        -> bench_fft.json, bench_c4.json, bench_c5.json
 #      per-call latency of config 5, other channel counts, all 90 FFT rate pairs              -> bench_c5_calls.json, channels_bench.txt, fft_channels_bench.txt, fft_pairs_bench.txt
 #      config 4's run: timelines (tools/kt_timeline.py), phase clocks, 16 steps per launch        -> c4_run_timeline_*.txt, wphase_c4_run_*.txt, bench_c4_k16.json
@@ -18,8 +18,8 @@ SUM="$OUT/summary"
 mkdir -p "$SUM"
 cd /tmp && export TMPDIR=/tmp
 
-python3 "$R/bench.py" --steps 20 --warmup 3 > "$SUM/bench_n1.json" 2> "$OUT/bench_n1.err"
-python3 "$R/bench.py" --path fft --steps 20 --warmup 3 > "$SUM/bench_fft.json" 2> "$OUT/bench_fft.err"
+python3 "$R/bench.py" --full --steps 20 --warmup 3 > "$SUM/bench_n1.json" 2> "$OUT/bench_n1.err"
+python3 "$R/bench.py" --path fft --full --steps 20 --warmup 3 > "$SUM/bench_fft.json" 2> "$OUT/bench_fft.err"
 python3 "$R/bench.py" --config c4 --steps 16384 --warmup 512 > "$SUM/bench_c4.json" 2> "$OUT/bench_c4.err"
 python3 "$R/bench.py" --config c4 --c4-k 1 --steps 256 --warmup 16 > "$SUM/bench_c4_k1.json" 2> "$OUT/bench_c4_k1.err"
 python3 "$R/bench.py" --config c4 --c4-k 16 --steps 2048 --warmup 256 > "$SUM/bench_c4_k16.json" 2> "$OUT/bench_c4_k16.err"
