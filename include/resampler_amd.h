@@ -15,6 +15,20 @@
  * are exact and available immediately (they come from the host-side mirror of the reference
  * state machine, not from the GPU).
  *
+ * What a caller may do with its streams (tests/test_stream_order_gpu.py):
+ *  - every device entry point: a call is ordered behind everything enqueued on `stream` before it, and work enqueued there
+ *    after it sees its results -- however busy the stream is;
+ *  - every entry point: change streams from one call of a handle / batch to the next (the library orders the calls of one
+ *    handle across the change), and pass RSMP_STREAM_LEGACY;
+ *  - every entry point: destroy a stream once the caller has synchronized it (a FIR handle's calls -- rsmp_fir_resample_device,
+ *    _resample_bulk_device, rsmp_fir_seek, batch launches planned on the host -- and the FFT entry points order a change of
+ *    streams through an event of the handle's last launch, never through the old stream; a lock-step batch synchronizes
+ *    its last stream when the stream changes, and forgets the caller's streams in rsmp_fir_lockstep_sync, which the caller
+ *    calls before destroying the stream a step or run was enqueued on; rsmp_fir_batch_resample_bulk_device(_ex) through the
+ *    device planner returns when the launch is through);
+ *  - FFT entry points only: destroy a stream right after the call, without synchronizing it (hipStreamDestroy lets the
+ *    enqueued work finish).
+ *
  * There is no CPU fallback: every compute entry point fails with RSMP_ERR_NO_DEVICE when no HIP
  * device is present.  The rsmp_*_plan_* / rsmp_design_* entry points are host-only (filter
  * design, FFT planning, and the (consumed, produced) state machine) and work without a GPU.
@@ -248,8 +262,9 @@ int rsmp_fir_lockstep_table_rebinds(const rsmp_fir_lockstep* ls, size_t* rebinds
  * [3] looks at the drifts that found a class past its tolerance with its next tables still on their way (the old ones
  * serve until the next look; a replacement is prepared by a worker thread, never inside a launch call), [4] times a
  * launch call WAITED for that worker (a class three tolerances past its tables: never observed), [5] probes of which
- * plan stream runs beside a caller's stream, [6] 1 if the last run's stream has a plan stream, [7] drift classes. */
-#define RSMP_LS_STAT_COUNT 8
+ * plan stream runs beside a caller's stream, [6] 1 if the last run's stream has a plan stream, [7] drift classes, [8] runs
+ * taken over whose states were committed on the plan stream (batches under 256 streams, no new buffers or tables in between). */
+#define RSMP_LS_STAT_COUNT 9
 int rsmp_fir_lockstep_stats(const rsmp_fir_lockstep* ls, uint64_t* out, size_t n);
 /* How closely the class tables follow the streams' drift: a class gets new tables when its drift is more than
  * `tolerance_frames` (default 1.2e-7: at worst 2e-7 of a full-scale sample, a fifth of the 1e-6 bound; 2e-8 .. 1e-6) from

@@ -613,7 +613,7 @@ class FirLockstep:
         return v.value
 
     STAT_NAMES = ("table_rebinds", "plan_ahead_hits", "plan_ahead_misses", "late_table_polls", "table_waits",
-                  "plan_stream_probes", "has_plan_stream", "drift_classes")
+                  "plan_stream_probes", "has_plan_stream", "drift_classes", "commits_on_plan_stream")
 
     def stats(self) -> dict:
         """Diagnostic counters of the batch (rsmp_fir_lockstep_stats)."""

@@ -437,6 +437,24 @@ PlanPool& plan_pool() {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The event `leader` records behind what it enqueues (the launch it leads, a seek's copy).
+int launch_event(rsmp_fir* leader) {
+    if (!leader->launch_ev) {
+        auto ev = std::make_shared<FirLaunchEvent>();
+        RSMP_HIP_CHECK(hipEventCreateWithFlags(&ev->ev, hipEventDisableTiming));
+        leader->launch_ev = std::move(ev);
+    }
+    return RSMP_OK;
+}
+
+// ... recorded behind everything `leader` has just enqueued on `stream` (`attached`: the last launch completes it already).
+int record_launch(rsmp_fir* leader, hipStream_t stream, bool attached = false) {
+    if (int rc = launch_event(leader)) return rc;
+    if (!attached) RSMP_HIP_CHECK(rsmp::event_record(leader->launch_ev->ev, stream));
+    if (leader->last_launch != leader->launch_ev) leader->last_launch = leader->launch_ev;
+    return RSMP_OK;
+}
+
 // Assembles and enqueues the launches for a set of planned jobs on one device / stream.
 // `leader` owns the launch workspace.
 // pcm_bits != 0: every job's d_in is a WAV file's PCM of that width, read in place (FirStreamDesc::in_bits): two-channel
@@ -449,9 +467,14 @@ int launch_jobs(rsmp_fir* leader, std::vector<Job>& jobs, hipStream_t stream, ui
     const size_t n = jobs.size();
     // Launches that touch a handle (its buffered frames, its plan slots, the leader's item queue) are
     // ordered: the ABI lets every call name a stream, so a handle that was last used on another stream
-    // waits for that stream first (rare; a caller that keeps one stream per handle never blocks here).
+    // makes this stream wait for the event of its last launch (rare; a caller that keeps one stream per
+    // handle never waits here).  An event, not the previous stream: the caller may have destroyed that one.
+    const FirLaunchEvent* waited = nullptr;
     auto order_after = [&](rsmp_fir* h) -> int {
-        if (h->last_stream_valid && h->last_stream != stream) RSMP_HIP_CHECK(hipStreamSynchronize(h->last_stream));
+        if (h->last_stream_valid && h->last_stream != stream && h->last_launch && h->last_launch.get() != waited) {
+            RSMP_HIP_CHECK(rsmp::stream_wait_event(stream, h->last_launch->ev));
+            waited = h->last_launch.get();
+        }
         h->last_stream = stream;
         h->last_stream_valid = true;
         return RSMP_OK;
@@ -753,31 +776,44 @@ int launch_jobs(rsmp_fir* leader, std::vector<Job>& jobs, hipStream_t stream, ui
         }
     }
     if (no_repair) repairs.clear();
+    // The handle's launch event (a later call on another stream waits for it) is completed by the LAST of the launches below
+    // itself -- hipExtLaunchKernel's stop event: an event record of its own between two launches of 64 streams cost their
+    // step 2-4 % --; where there is no such launch, or the stream is the legacy handle (which an event must not carry,
+    // common.h), it is recorded behind them.
+    if (int rc = launch_event(leader)) return rc;
+    const bool wrap_last = n > n_generic && max_wraps > 0 && tail_fused;
+    const bool repair_last = tail_fused && !wrap_last;
+    hipEvent_t done = stream != reinterpret_cast<hipStream_t>(RSMP_STREAM_LEGACY) ? leader->launch_ev->ev : nullptr;
+    bool done_attached = false;
     if (repairs.size() > 1) {
         std::vector<rsmp::RepairJob> rj;
         for (const Repair& rp : repairs) rj.push_back(rsmp::RepairJob{d_descs + rp.first, rp.count, rp.nf});
-        RSMP_HIP_CHECK(rsmp::launch_fir_repair_multi(rj.data(), rj.size(), stream));
+        RSMP_HIP_CHECK(rsmp::launch_fir_repair_multi(rj.data(), rj.size(), stream, nullptr, 0, 0, repair_last ? done : nullptr,
+                                                     &done_attached));
     } else {
         for (const Repair& rp : repairs)
-            RSMP_HIP_CHECK(rsmp::launch_fir_repair(d_descs + rp.first, rp.count, rp.nf, stream));
+            RSMP_HIP_CHECK(rsmp::launch_fir_repair(d_descs + rp.first, rp.count, rp.nf, stream, repair_last ? done : nullptr,
+                                                   &done_attached));
     }
     if (n > n_generic && max_wraps > 0)
         RSMP_HIP_CHECK(rsmp::launch_fir_wrap_fixup(d_descs + n_generic,
                                                    static_cast<uint32_t>(n - n_generic), max_wraps,
-                                                   stream));
+                                                   stream, wrap_last ? done : nullptr, &done_attached));
     if (!tail_fused)
         RSMP_HIP_CHECK(rsmp::launch_fir_tail_copy(d_descs, static_cast<uint32_t>(n), max_tail_values,
-                                                  stream));
+                                                  stream, done, &done_attached));
     if (direct) {   // the slot may be rewritten once these kernels have read it
         RSMP_HIP_CHECK(rsmp::event_record(leader->plan_copied[slot], stream));
         leader->plan_pending[slot] = true;
         leader->plan_image[slot].clear();
     }
+    if (int rc = record_launch(leader, stream, done_attached)) return rc;
     // Commit: the mirrors advance, the hist buffers swap.
     for (Job& j : jobs) {
         j.r->last_periodic = j.plan->periodic;
         j.r->mirror = j.plan->planned;
         j.r->cur ^= 1;
+        if (j.r->last_launch != leader->launch_ev) j.r->last_launch = leader->launch_ev;   // (no reference count traffic per launch)
     }
     return RSMP_OK;
 }
@@ -910,7 +946,8 @@ extern "C" int rsmp_fir_seek(rsmp_fir* r, const rsmp_fir_plan* p, const float* h
                           need, history_len);
     DeviceGuard guard(r->device);
     hipStream_t stream = stream_v ? static_cast<hipStream_t>(stream_v) : r->stream;
-    if (r->last_stream_valid && r->last_stream != stream) RSMP_HIP_CHECK(hipStreamSynchronize(r->last_stream));
+    if (r->last_stream_valid && r->last_stream != stream && r->last_launch)   // (as launch_jobs: the event, not the old stream)
+        RSMP_HIP_CHECK(rsmp::stream_wait_event(stream, r->last_launch->ev));
     r->last_stream = stream;
     r->last_stream_valid = true;
     if (need) {
@@ -918,6 +955,7 @@ extern "C" int rsmp_fir_seek(rsmp_fir* r, const rsmp_fir_plan* p, const float* h
                                       history_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
         if (!history_on_device) RSMP_HIP_CHECK(hipStreamSynchronize(stream));   // the caller's buffer is free on return
     }
+    if (int rc = record_launch(r, stream)) return rc;
     r->mirror.set_state(s);
     return RSMP_OK;
 }

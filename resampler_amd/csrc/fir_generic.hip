@@ -245,10 +245,17 @@ __global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMu
 
 }  // namespace
 
-hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream) {
+hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
+                             hipEvent_t done, bool* done_attached) {
     if (n_streams == 0 || !nf.words || nf.chunks == 0) return hipSuccess;
     const uint32_t total = n_streams * nf.chunks;
-    hipLaunchKernelGGL(fir_repair_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf);
+    if (done && done_attached) {
+        hipExtLaunchKernelGGL(fir_repair_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, nullptr, done, 0,
+                              d_descs, n_streams, nf);
+        *done_attached = true;
+    } else {
+        hipLaunchKernelGGL(fir_repair_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf);
+    }
     return hipGetLastError();
 }
 
@@ -299,12 +306,17 @@ hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, 
 }
 
 hipError_t launch_fir_tail_copy(const FirStreamDesc* d_descs, uint32_t n_streams,
-                                uint32_t max_tail_values, hipStream_t stream) {
+                                uint32_t max_tail_values, hipStream_t stream, hipEvent_t done, bool* done_attached) {
     if (n_streams == 0 || max_tail_values == 0) return hipSuccess;
     uint32_t blocks = (max_tail_values + kBlock - 1) / kBlock;
     if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(fir_tail_copy_kernel, dim3(blocks, n_streams), dim3(kBlock), 0, stream,
-                       d_descs);
+    if (done && done_attached) {
+        hipExtLaunchKernelGGL(fir_tail_copy_kernel, dim3(blocks, n_streams), dim3(kBlock), 0, stream, nullptr, done, 0, d_descs);
+        *done_attached = true;
+    } else {
+        hipLaunchKernelGGL(fir_tail_copy_kernel, dim3(blocks, n_streams), dim3(kBlock), 0, stream,
+                           d_descs);
+    }
     return hipGetLastError();
 }
 

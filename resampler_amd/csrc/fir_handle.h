@@ -11,6 +11,13 @@
 #include "fir_periodic.h"
 #include "fir_plan.h"
 
+// An event recorded behind a launch on its stream, shared by the handles of a batch launch (the leader re-records its own
+// for every launch it leads: each handle's launches are ordered, so the later recording completes after the earlier one).
+struct FirLaunchEvent {
+    hipEvent_t ev = nullptr;
+    ~FirLaunchEvent() { if (ev) (void)hipEventDestroy(ev); }
+};
+
 struct rsmp_fir {
     int device = 0;
     size_t channels = 0;
@@ -43,8 +50,10 @@ struct rsmp_fir {
     unsigned long long* d_work_counter = nullptr;   // periodic kernel's item queue (leader only), zero between launches
     rsmp::DeviceBuffer d_nf;                        // non-finite marks of the periodic launches (leader only)
     uint32_t nf_tag = 0;
-    hipStream_t last_stream = nullptr;              // the stream of the handle's most recent launch
-    bool last_stream_valid = false;
+    hipStream_t last_stream = nullptr;              // the stream of the handle's most recent launch (compared, never used:
+    bool last_stream_valid = false;                 // the caller may have destroyed it by the next call)
+    // ... and the event behind that launch: a call on another stream waits for it there (fft_api.cpp does the same)
+    std::shared_ptr<FirLaunchEvent> last_launch, launch_ev;   // (launch_ev: the one this handle records when it leads a launch)
     // optional timing of the main convolution launch(es) (rsmp_fir_set_profiling)
     bool profiling = false;
     // ring of event pairs: launches made while profiling is on are timed without any host sync

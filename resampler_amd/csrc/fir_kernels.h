@@ -79,7 +79,10 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
 constexpr uint32_t kFirBulkMinOut = 8192;   // launches whose longest generic stream produces fewer frames keep fir_generic_kernel
 // Re-evaluates, in the reference's two-row form, the output chunks a periodic launch marked as non-finite
 // (fir_nonfinite.h); exits at once when the launch marked nothing.
-hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream);
+// (done / done_attached, here and in launch_fir_tail_copy: as in launch_fir_repair_multi below -- the launch completes `done`
+// itself; *done_attached stays false when there was nothing to launch)
+hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
+                             hipEvent_t done = nullptr, bool* done_attached = nullptr);
 // The same for up to eight groups of streams (each with its own marks) in one launch.
 struct RepairJob {
     const FirStreamDesc* d_descs;
@@ -95,6 +98,6 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
                                    uint32_t n_tail = 0, uint32_t max_tail_values = 0, hipEvent_t done = nullptr, bool* done_attached = nullptr);
 // Copies the still-buffered tail of [hist|in] into hist_next; grid = (blocks, streams).
 hipError_t launch_fir_tail_copy(const FirStreamDesc* d_descs, uint32_t n_streams,
-                                uint32_t max_tail_values, hipStream_t stream);
+                                uint32_t max_tail_values, hipStream_t stream, hipEvent_t done = nullptr, bool* done_attached = nullptr);
 
 }  // namespace rsmp

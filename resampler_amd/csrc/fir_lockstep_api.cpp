@@ -623,7 +623,7 @@ extern "C" rsmp_fir_lockstep* rsmp_fir_lockstep_new(rsmp_fir* const* rs, size_t 
     // every stream's earlier launches (which wrote its buffered frames) must be complete
     for (size_t i = 0; i < n; ++i) {
         (void)hipStreamSynchronize(rs[i]->stream);
-        if (rs[i]->last_stream_valid) (void)hipStreamSynchronize(rs[i]->last_stream);
+        if (rs[i]->last_launch) (void)hipEventSynchronize(rs[i]->last_launch->ev);   // (not the stream: it may be gone)
     }
     if (hipMemcpy(ls->d_groups.get(), ls->groups.data(), ls->groups.size() * sizeof(LockstepGroup),
                   hipMemcpyHostToDevice) != hipSuccess ||
@@ -844,11 +844,63 @@ extern "C" int rsmp_fir_lockstep_status(rsmp_fir_lockstep* ls, uint32_t* status)
     return RSMP_OK;
 }
 
+// The answer of the plan-stream probe in flight (pick_plan_stream), once the device has given it: kept for the caller's stream
+// it was made for.
+static void take_probe_answer(rsmp_fir_lockstep* ls) {
+    if (!ls->probe_owner) return;
+    if (hipEventQuery(ls->probe_ev) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    rsmp_fir_lockstep::PlanPick& pp = ls->plan_pick[ls->probe_owner];
+    pp.probing = false;
+    if (*ls->h_probe.as<volatile uint32_t>() == 1u) {
+        pp.pick = pp.cand;
+        pp.decided = true;
+    } else if (++pp.tries >= 4) {
+        pp.pick = -1;
+        pp.decided = true;
+    } else {
+        pp.cand ^= 1;
+    }
+    static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
+    if (verbose && pp.decided)
+        fprintf(stderr, "[rsmp] lock-step run: plan stream candidate %d runs beside stream %p (%d probes)\n", pp.pick,
+                static_cast<void*>(ls->probe_owner), pp.tries + 1);
+    ls->probe_owner = nullptr;
+}
+
+// Everything the batch enqueued on a caller's stream is complete (that stream has just been synchronized; a change of streams
+// synchronized the one before): the batch keeps no handle of the caller's streams beyond this point, so the caller may destroy
+// them (a stream per launch: the routed bulk entry syncs through here before it returns).  The slots' computations are
+// through, a run planned ahead is waited for through its event, and a stream seen again is only compared, never used.  A probe
+// in flight on the caller's stream is through as well: it is forgotten (that stream is probed again if it comes back), so the
+// next stream's probe is not held up by a stream that may no longer exist.
+static void forget_caller_streams(rsmp_fir_lockstep* ls) {
+    ls->last_stream = nullptr;
+    if (ls->probe_owner) {
+        take_probe_answer(ls);
+        if (ls->probe_owner) {   // (no answer although its stream is through: that stream is probed again if it comes back)
+            auto it = ls->plan_pick.find(ls->probe_owner);
+            if (it != ls->plan_pick.end()) it->second.probing = false;
+            ls->probe_owner = nullptr;
+        }
+    }
+    for (auto& sl : ls->slot)
+        if (sl.compute_stream != ls->own_stream) {
+            sl.used = false;
+            sl.compute_stream = nullptr;
+        }
+    ls->ahead_waited = false;
+    ls->ahead_waited_on = nullptr;
+}
+
 extern "C" int rsmp_fir_lockstep_sync(rsmp_fir_lockstep* ls) {
     if (!ls) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_sync: null batch");
     DeviceGuard guard(ls->device);
     const size_t n = ls->rs.size();
     if (ls->last_stream) RSMP_HIP_CHECK(hipStreamSynchronize(ls->last_stream));
+    forget_caller_streams(ls);
     ls->h_states.resize(n);
     RSMP_HIP_CHECK(hipMemcpy(ls->h_states.data(), ls->d_states.get(), n * sizeof(FirMirrorState),
                              hipMemcpyDeviceToHost));
@@ -994,29 +1046,14 @@ namespace {
 // stream itself.  (A stream of higher priority has a queue of its own for certain -- and starves the short kernels between
 // the bulk launches: a run of 16 calls took 2.7x as long.)
 int pick_plan_stream(rsmp_fir_lockstep* ls, hipStream_t s) {
+    // (a caller with a stream per launch would grow the map by one entry per launch: its answers are dropped beyond 64
+    // streams -- except the one whose probe is in flight -- and such a stream is probed again)
+    if (ls->plan_pick.size() >= 64 && ls->plan_pick.find(s) == ls->plan_pick.end())
+        for (auto it = ls->plan_pick.begin(); it != ls->plan_pick.end();)
+            it = it->first == ls->probe_owner ? std::next(it) : ls->plan_pick.erase(it);
     rsmp_fir_lockstep::PlanPick& pp = ls->plan_pick[s];
-    static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
     if (!pp.decided) {
-        if (pp.probing && ls->probe_owner == s) {
-            if (hipEventQuery(ls->probe_ev) == hipSuccess) {
-                pp.probing = false;
-                ls->probe_owner = nullptr;
-                if (*ls->h_probe.as<volatile uint32_t>() == 1u) {
-                    pp.pick = pp.cand;
-                    pp.decided = true;
-                } else if (++pp.tries >= 4) {
-                    pp.pick = -1;
-                    pp.decided = true;
-                } else {
-                    pp.cand ^= 1;
-                }
-                if (verbose && pp.decided)
-                    fprintf(stderr, "[rsmp] lock-step run: plan stream candidate %d runs beside stream %p (%d probes)\n", pp.pick,
-                            static_cast<void*>(s), pp.tries + 1);
-            } else {
-                (void)hipGetLastError();
-            }
-        }
+        if (pp.probing && ls->probe_owner == s) take_probe_answer(ls);
         if (!pp.decided && !pp.probing && ls->probe_owner == nullptr) {
             const uint32_t token = ++ls->probe_token ? ls->probe_token : ++ls->probe_token;
             *ls->h_probe.as<volatile uint32_t>() = 0u;
@@ -1273,6 +1310,7 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
         ls->ahead_inflight = false;
         plan_taken_over = true;
         ++ls->stat_ahead_hits;
+        const bool rebased = ls->rebased;
         if (ls->rebased) {   // (planned when the batch was bound to other buffers: the two pointers of every descriptor again)
             RSMP_HIP_CHECK(rsmp::launch_fir_lockstep_rebase(ls->slot[sl].descs.as<rsmp::FirStreamDesc>(), ls->d_streams.as<LockstepStream>(),
                                                             ls->d_run_rs.as<rsmp::LsRunStream>(), key.in_offset, static_cast<uint32_t>(n), s));
@@ -1289,10 +1327,14 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
         // run -- plan stream -> caller's stream (commit) -> plan stream (the next plan): two event hand-overs of ~12 us in a
         // 185 us period (profiles/r06/c4_run_timeline_128_ahead1.txt).  So the commit goes to the PLAN stream, right behind
         // the plan it commits, the next plan right behind it, and the caller's stream waits for the commit -- unless this
-        // call put something on the caller's stream that the next plan must see (new class tables: rare).
+        // call put something on the caller's stream that the next plan must see (new class tables: rare), or unless the buffers
+        // changed under this run (rsmp_fir_lockstep_rebind_buffers: the new stream table and the zeroed append positions are
+        // still queued on the caller's stream -- behind whatever the caller enqueued there before -- and a commit on the plan
+        // stream could land in front of the zeroing, which would then wipe the positions after this run, while the next plan
+        // read the old buffers' pointers).
         static const bool commit_knob = [] { const char* e = rsmp::knob("RSMP_LS_COMMIT_ON_PLAN"); return !e || atoi(e) != 0; }();
         static const bool commit_any_n = [] { const char* e = rsmp::knob("RSMP_LS_COMMIT_ON_PLAN"); return e && atoi(e) == 2; }();
-        commit_on_q = commit_knob && (n < 256 || commit_any_n) && ls->ahead_q != nullptr && ls->stat_table_ops == table_ops0;
+        commit_on_q = commit_knob && (n < 256 || commit_any_n) && ls->ahead_q != nullptr && ls->stat_table_ops == table_ops0 && !rebased;
         hipStream_t cs = commit_on_q ? ls->ahead_q : s;
         if (commit_on_q && ls->drift_inflight)   // (a reading of the states on the caller's stream: in front of what changes them)
             RSMP_HIP_CHECK(rsmp::stream_wait_event(cs, ls->drift_ev));
@@ -1550,7 +1592,8 @@ extern "C" int rsmp_fir_lockstep_run_slow_calls(rsmp_fir_lockstep* ls, size_t* s
 extern "C" int rsmp_fir_lockstep_stats(const rsmp_fir_lockstep* ls, uint64_t* out, size_t n) {
     if (!ls || !out) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_stats: null argument");
     const uint64_t v[RSMP_LS_STAT_COUNT] = {ls->table_rebinds, ls->stat_ahead_hits, ls->stat_ahead_misses, ls->stat_late_polls,
-                                            ls->stat_table_waits, ls->stat_probes, ls->plan_stream ? 1u : 0u, ls->classes.size()};
+                                            ls->stat_table_waits, ls->stat_probes, ls->plan_stream ? 1u : 0u, ls->classes.size(),
+                                            ls->stat_commits_on_plan_stream};
     for (size_t i = 0; i < n && i < RSMP_LS_STAT_COUNT; ++i) out[i] = v[i];
     return RSMP_OK;
 }

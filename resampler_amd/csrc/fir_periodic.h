@@ -141,8 +141,9 @@ hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
                                bool fuse_tail = false, uint64_t items_key = 0, uint32_t pcm_bits = 0);
 // Recomputes the outputs listed in each stream's `wraps` with row 1023 / previous frame
 // (only for geometries without inline wraps).
+// (done / done_attached: as in launch_fir_repair_multi, fir_kernels.h)
 hipError_t launch_fir_wrap_fixup(const FirStreamDesc* d_descs, uint32_t n_streams,
-                                 uint32_t max_wraps, hipStream_t stream);
+                                 uint32_t max_wraps, hipStream_t stream, hipEvent_t done = nullptr, bool* done_attached = nullptr);
 // Number of period blocks (grid.x) a stream's launch needs.
 uint32_t periodic_blocks(const PeriodicGeometry& geo, uint64_t abs_out, uint32_t n_out);
 

@@ -19,6 +19,8 @@
 // (<= a few hundred KB) stays in L2 / scalar cache.
 #include "fir_periodic.h"
 
+#include <hip/hip_ext.h>
+
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -2268,10 +2270,16 @@ static const char* trace_env = rsmp::knob("RSMP_FIR_TRACE");
 }
 
 hipError_t launch_fir_wrap_fixup(const FirStreamDesc* d_descs, uint32_t n_streams,
-                                 uint32_t max_wraps, hipStream_t stream) {
+                                 uint32_t max_wraps, hipStream_t stream, hipEvent_t done, bool* done_attached) {
     if (n_streams == 0 || max_wraps == 0) return hipSuccess;
-    hipLaunchKernelGGL(fir_wrap_fixup_kernel, dim3((max_wraps + 31) / 32, n_streams), dim3(256), 0,
-                       stream, d_descs);
+    if (done && done_attached) {
+        hipExtLaunchKernelGGL(fir_wrap_fixup_kernel, dim3((max_wraps + 31) / 32, n_streams), dim3(256), 0, stream, nullptr, done, 0,
+                              d_descs);
+        *done_attached = true;
+    } else {
+        hipLaunchKernelGGL(fir_wrap_fixup_kernel, dim3((max_wraps + 31) / 32, n_streams), dim3(256), 0,
+                           stream, d_descs);
+    }
     return hipGetLastError();
 }
 
