@@ -129,8 +129,8 @@ int rsmp_fir_last_kernel_ms(rsmp_fir* r, float* ms);
  * happens between those launches, so this is the kernel's duration inside a timed region. */
 int rsmp_fir_mean_kernel_ms(rsmp_fir* r, float* ms, size_t* launches);
 /* Which kernel the handle's last launch used (diagnostic, for benchmark reports): 0 generic
- * (any ratio), 1 periodic vector kernel, 2 periodic vector kernel with double-buffered
- * workgroups, 3 periodic exact-f32 matrix-core kernel, 4 periodic split matrix-core kernel with
+ * (any ratio), 1 periodic vector kernel, 2 no longer returned (it was the periodic vector kernel with
+ * double-buffered workgroups), 3 periodic exact-f32 matrix-core kernel, 4 periodic split matrix-core kernel with
  * three bf16 planes per operand (RSMP_FIR_SPLIT_PLANES=3), 5 periodic split matrix-core kernel with
  * two fp16 planes per operand (the default for rate pairs it has a geometry for); negative: invalid
  * handle. */

@@ -384,7 +384,7 @@ class ResamplerFir:
         return ms.value, n.value
 
     def kernel_variant(self) -> int:
-        """0 generic, 1 periodic vector, 2 periodic vector (double-buffered), 3 periodic f32 matrix-core,
+        """0 generic, 1 periodic vector, (2 is no longer returned), 3 periodic f32 matrix-core,
         4 periodic split matrix-core with three bf16 planes, 5 with two fp16 planes (default)."""
         return int(lib().rsmp_fir_kernel_variant(self._h))
 

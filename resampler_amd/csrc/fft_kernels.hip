@@ -780,8 +780,7 @@ hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, 
         return run;
     };
     size_t lds = fft_ola_lds_bytes(plan, max_channels);
-    constexpr int big_knob = 160 * 1024;
-    if (lds > static_cast<size_t>(big_knob)) {   // the two-buffer kernels do not fit: one buffer, in place, a workgroup per channel
+    if (lds > 160 * 1024) {   // the two-buffer kernels do not fit: one buffer, in place, a workgroup per channel
         const size_t big = fft_big_lds_bytes(plan);
         if (big > 160 * 1024) return hipErrorInvalidValue;
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fft_ola_big_kernel),
@@ -792,14 +791,12 @@ hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, 
                            stream, plan, d_descs, run);
         return hipGetLastError();
     }
-    bool all_stereo = max_channels == 2 && min_channels == 2;
+    const bool stereo = max_channels == 2 && min_channels == 2;
     static const bool generic_only = rsmp::knob("RSMP_FFT_GENERIC") != nullptr;   // A/B: skip the specialised builds
     const bool rc_full = plan.n_rc_f == plan.fft_in / 2 - 1 && plan.n_rc_i == plan.fft_out / 2 - 1;
     typedef void (*Kernel)(FftPlanDev, const FftStreamDesc*, uint32_t);
     Kernel fn = fft_ola_kernel<kFftThreads, false>;
     uint32_t threads = kFftThreads, grid_z = 1;
-    constexpr bool no_stereo = false;
-    const bool stereo = all_stereo && !no_stereo;
     if (!generic_only && rc_full && Plan1176::matches(plan.fft_in, plan.n_stages_f, plan.radix_f) &&
         Plan1280::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
         fn = stereo ? fft_ola_kernel_ct2<Plan1176, Plan1280> : fft_ola_kernel_ct<Plan1176, Plan1280>;
@@ -807,24 +804,21 @@ hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, 
              Plan1176::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
         fn = stereo ? fft_ola_kernel_ct2<Plan1280, Plan1176> : fft_ola_kernel_ct<Plan1280, Plan1176>;
     else {
-        all_stereo = false;
         // the generic pipeline: for blocks up to 512 frames (both sides) a one-wave workgroup per channel (see the
         // kernel; 96 -> 48 kHz 1.56 -> 1.18 ms, 192 -> 48 kHz 1.48 -> 0.76 ms per 64 x 2^20 frames); above that the
         // four-wave workgroups keep more waves on a CU for the same LDS and win (tools/fft_pairs_bench.py)
-        constexpr int wave_knob = -1;
         const size_t lds_wave = 2 * static_cast<size_t>(plan.lds_complex) * sizeof(float2) + static_cast<size_t>(plan.fft_out) * sizeof(float);
-        const bool per_channel = wave_knob >= 0 ? wave_knob != 0 : plan.lds_complex <= 513;
-        constexpr int threads_knob = 0;
+        const bool per_channel = plan.lds_complex <= 513;
         if (per_channel && lds_wave <= 160 * 1024) {
             fn = fft_ola_kernel<64, true>;
             threads = 64;
             grid_z = max_channels;
             lds = lds_wave;
-        } else if (threads_knob ? threads_knob == 1024 : lds > 80 * 1024) {
+        } else if (lds > 80 * 1024) {
             // the long plans: one workgroup per CU is all the LDS holds, so it is 16 waves wide, not 4
             fn = fft_ola_kernel<1024, false>;
             threads = 1024;
-        } else if (threads_knob ? threads_knob == 512 : lds > 160 * 1024 / 3) {
+        } else if (lds > 160 * 1024 / 3) {
             fn = fft_ola_kernel<512, false>;   // two workgroups per CU
             threads = 512;
         }

@@ -681,7 +681,6 @@ struct WaveChoice {
     size_t lds = 0;          // bytes of a workgroup
     uint32_t waves = 0;      // waves per workgroup
     uint32_t resident = 0;   // waves a CU holds at once
-    int occ = 0;
 };
 
 // The instantiation for (FWD, INV) if the plan is that pair.  Waves per CU, by what the CU's LDS holds (one copy
@@ -691,7 +690,7 @@ struct WaveChoice {
 // sample addressing; it spilled 290 bytes per lane under the 168 cap and ran 25-30 % slower,
 // tools/fft_channels_bench.py) and runs 2 x 4.  Plans too long for that run one workgroup of up to 8 waves.
 template <class FWD, class INV>
-bool wave_choice(const FftPlanDev& plan, uint32_t channels, int occ_env, WaveChoice* out) {
+bool wave_choice(const FftPlanDev& plan, uint32_t channels, WaveChoice* out) {
     if (!FWD::matches(plan.fft_in, plan.n_stages_f, plan.radix_f) || !INV::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
         return false;
     constexpr size_t tables = static_cast<size_t>(FWD::kTw + INV::kTw + FWD::kRc + INV::kRc + (FWD::N < INV::N ? FWD::N + 1 : INV::N));   // (+ the filter bins in use)
@@ -704,40 +703,31 @@ bool wave_choice(const FftPlanDev& plan, uint32_t channels, int occ_env, WaveCho
     // (fewer than two waves per CU -- the longest plans in the exact build, whose twiddle rows are whole -- belong to
     // the workgroup kernels)
     if constexpr (!fit4 && wide < 2) {
-        (void)channels; (void)occ_env; (void)out;
+        (void)channels; (void)out;
         return false;
     } else {
     static const bool no_c2 = rsmp::knob("RSMP_FFT_WAVE_NOC2") != nullptr;   // A/B: the any-channel-count build for two channels
     // (an even number of channels: channel pairs on the two-channel build)
     const bool paired = channels % 2 == 0 && !no_c2;
     // (the pairs build addresses its frames at a run-time stride: under the 168-register cap of twelve waves per CU it
-    // spills 25 registers and runs 13 % slower than 2 x 4 waves with all of them -- 8 channels 0.84 against 0.73 ms)
-    int occ = paired ? (fit12 && channels == 2 ? 3 : fit4 ? 2 : 1) : (fit4 ? 2 : 1);
-    if (paired && ((occ_env == 3 && fit12) || (occ_env == 2 && fit4))) occ = occ_env;
-    out->occ = occ;
-    out->fn = nullptr;
-    if (paired && channels == 2) {
-        if constexpr (fit12) if (occ == 3) out->fn = fft_ola_wave_kernel<FWD, INV, 1, 3>;
-        if constexpr (fit4) if (occ == 2) out->fn = fft_ola_wave_kernel<FWD, INV, 1, 2>;
-        if constexpr (!fit4) if (occ == 1) out->fn = fft_ola_wave_kernel<FWD, INV, 1, 1>;
-    } else if (paired) {
-        if constexpr (fit12) if (occ == 3) out->fn = fft_ola_wave_kernel<FWD, INV, 2, 3>;
-        if constexpr (fit4) if (occ == 2) out->fn = fft_ola_wave_kernel<FWD, INV, 2, 2>;
-        if constexpr (!fit4) if (occ == 1) out->fn = fft_ola_wave_kernel<FWD, INV, 2, 1>;
-    } else {
-        if constexpr (fit4) out->fn = fft_ola_wave_kernel<FWD, INV, 0, 2>;
-        else out->fn = fft_ola_wave_kernel<FWD, INV, 0, 1>;
-    }
+    // spills 25 registers and runs 13 % slower than 2 x 4 waves with all of them -- 8 channels 0.84 against 0.73 ms:
+    // only the two-channel build runs twelve waves, occupancy 3; the others 2 x 4 waves (2) or one workgroup (1))
+    constexpr int occ_any = fit4 ? 2 : 1, occ_c2 = fit12 ? 3 : occ_any;
+    const bool c2 = paired && channels == 2;
+    const int occ = c2 ? occ_c2 : occ_any;
+    if (c2) out->fn = fft_ola_wave_kernel<FWD, INV, 1, occ_c2>;
+    else if (paired) out->fn = fft_ola_wave_kernel<FWD, INV, 2, occ_any>;
+    else out->fn = fft_ola_wave_kernel<FWD, INV, 0, occ_any>;
     static const uint32_t wide_knob = [] { const char* e = rsmp::knob("RSMP_FFT_WAVE_WIDE"); return e ? static_cast<uint32_t>(atoi(e)) : 0u; }();
     out->waves = occ == 3 ? 12u : occ == 2 ? 4u : (wide_knob >= 1 && wide_knob <= wide ? wide_knob : wide);
     out->resident = occ == 2 ? 8u : out->waves;
     out->lds = (tables + out->waves * buf + kFlags) * sizeof(cf);
-    return out->fn != nullptr;
+    return true;
     }
 }
 template <class FWD, class... INVS>
-bool wave_choices(const FftPlanDev& plan, uint32_t channels, int occ_env, WaveChoice* out) {
-    return (wave_choice<FWD, INVS>(plan, channels, occ_env, out) || ...);
+bool wave_choices(const FftPlanDev& plan, uint32_t channels, WaveChoice* out) {
+    return (wave_choice<FWD, INVS>(plan, channels, out) || ...);
 }
 
 }  // namespace
@@ -760,24 +750,23 @@ hipError_t launch_fft_ola_wave(const FftPlanDev& plan, const FftStreamDesc* d_de
     if (plan.n_rc_f != plan.fft_in / 2 - 1 || plan.n_rc_i != plan.fft_out / 2 - 1) return hipErrorNotSupported;
     if (plan.new_length != (plan.fft_in < plan.fft_out ? plan.fft_in + 1 : plan.fft_out)) return hipErrorNotSupported;
     const uint32_t C = max_channels;
-    constexpr int occ_env = 0;
     WaveChoice wc;
-    const bool found = wave_choices<W1176, W1280>(plan, C, occ_env, &wc) || wave_choices<W1280, W1176>(plan, C, occ_env, &wc)
+    const bool found = wave_choices<W1176, W1280>(plan, C, &wc) || wave_choices<W1280, W1176>(plan, C, &wc)
 #if RSMP_EXP != 0   // (timing experiments instantiate the 44.1 <-> 48 kHz pair alone: 25 s instead of 160 s per build)
                        ;
 #else
                        ||
-                       wave_choices<W512, W64, W128, W256, W768, W1024, W1536, W2048, W3072, W4096>(plan, C, occ_env, &wc) ||
-                       wave_choices<W768, W64, W128, W256, W512>(plan, C, occ_env, &wc) ||
-                       wave_choices<W1536, W64, W128>(plan, C, occ_env, &wc) ||
-                       wave_choices<W588, W1280, W2560>(plan, C, occ_env, &wc) || wave_choices<W882, W640, W1280>(plan, C, occ_env, &wc) ||
-                       wave_choices<W1764, W640, W1280>(plan, C, occ_env, &wc) || wave_choices<W2352, W1280, W2560>(plan, C, occ_env, &wc) ||
-                       wave_choice<W1176, W2560>(plan, C, occ_env, &wc) || wave_choice<W1280, W2352>(plan, C, occ_env, &wc) ||
-                       wave_choices<W2560, W2352, W1176, W588>(plan, C, occ_env, &wc) || wave_choices<W640, W882, W1764, W3528>(plan, C, occ_env, &wc) || wave_choices<W3528, W640, W1280>(plan, C, occ_env, &wc) ||
-                       wave_choices<W1280, W588, W882, W1764, W3528, W4704>(plan, C, occ_env, &wc) ||
-                       wave_choices<W4704, W1280, W2560>(plan, C, occ_env, &wc) || wave_choices<W5120, W1176, W2352>(plan, C, occ_env, &wc) ||
-                       wave_choice<W2560, W4704>(plan, C, occ_env, &wc) || wave_choice<W1176, W5120>(plan, C, occ_env, &wc) ||
-                       wave_choice<W2352, W5120>(plan, C, occ_env, &wc) || wave_choice<W588, W5120>(plan, C, occ_env, &wc);
+                       wave_choices<W512, W64, W128, W256, W768, W1024, W1536, W2048, W3072, W4096>(plan, C, &wc) ||
+                       wave_choices<W768, W64, W128, W256, W512>(plan, C, &wc) ||
+                       wave_choices<W1536, W64, W128>(plan, C, &wc) ||
+                       wave_choices<W588, W1280, W2560>(plan, C, &wc) || wave_choices<W882, W640, W1280>(plan, C, &wc) ||
+                       wave_choices<W1764, W640, W1280>(plan, C, &wc) || wave_choices<W2352, W1280, W2560>(plan, C, &wc) ||
+                       wave_choice<W1176, W2560>(plan, C, &wc) || wave_choice<W1280, W2352>(plan, C, &wc) ||
+                       wave_choices<W2560, W2352, W1176, W588>(plan, C, &wc) || wave_choices<W640, W882, W1764, W3528>(plan, C, &wc) || wave_choices<W3528, W640, W1280>(plan, C, &wc) ||
+                       wave_choices<W1280, W588, W882, W1764, W3528, W4704>(plan, C, &wc) ||
+                       wave_choices<W4704, W1280, W2560>(plan, C, &wc) || wave_choices<W5120, W1176, W2352>(plan, C, &wc) ||
+                       wave_choice<W2560, W4704>(plan, C, &wc) || wave_choice<W1176, W5120>(plan, C, &wc) ||
+                       wave_choice<W2352, W5120>(plan, C, &wc) || wave_choice<W588, W5120>(plan, C, &wc);
 #endif
     if (!found) return hipErrorNotSupported;
     const uint32_t kWavesPerGroup = wc.waves;

@@ -46,8 +46,8 @@ struct PeriodicGeometry {
     uint32_t pw = 0;             // periods per workgroup (<= 64 / lp)
     uint32_t row_stride = 0;     // LDS dwords between period rows (odd frame count: conflict-free)
     uint32_t waves = 0;          // waves per workgroup
-    uint32_t producers = 0;      // > 0: double-buffered kernel, this many waves only stage
-    uint32_t images = 0;         // double-buffered kernels: LDS images in the ring (2 or 4)
+    uint32_t producers = 0;      // > 0 (matrix-core kernels only): double-buffered kernel, this many waves only stage
+    uint32_t images = 0;         // double-buffered kernels: LDS images in the ring (split kernel: 2 or 3; else 2)
     uint32_t mfma = 0;           // > 0: matrix-core kernel (16-class tiles); period groups of 16 per work unit;
                                  // 3: split kernel (fir_split.hip)
     uint32_t planes = 0;         // split kernel: 16-bit planes per f32 operand (3: bf16, exact; 2: fp16)

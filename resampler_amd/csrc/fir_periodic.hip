@@ -1,15 +1,13 @@
 // fir_periodic.hip -- throughput FIR kernels for rational rate pairs on gfx950 (see fir_periodic.h
 // for the idea; DESIGN.md section 4.1 for the measurements).  They replace the same reference code
 // as fir_generic.hip (src/resampler_fir.rs:542-590 + src/fir/avx.rs:5-61) for launches long enough
-// to work in whole periods.  Three kernels share the staging, geometry and class-table code:
+// to work in whole periods.  Two kernels share the staging, geometry and class-table code:
 //
-//   fir_periodic_db_kernel<.., MF != 0>   matrix-core consumers (default for 2 channels): one
-//       workgroup per CU owning two (or four) LDS images; producer waves stage with LDS-DMA,
+//   fir_periodic_db_kernel                matrix-core consumers (default for 2 channels): one
+//       workgroup per CU owning two LDS images; producer waves stage with LDS-DMA,
 //       consumer waves run v_mfma_f32_16x16x4_f32 streams over 16-class tiles (exact f32), the
 //       coefficient tile in registers, samples from LDS, stores without any transpose; the wrap
 //       variant is computed by a producer from the staged image;
-//   fir_periodic_db_kernel<.., 0>         the same producer / consumer skeleton around the vector
-//       tile code (RSMP_FIR_PRODUCERS=n; measured slower than the next one);
 //   fir_periodic_kernel                   vector kernel, two workgroups per CU alternating between
 //       staging and computing: lane = period, the 8 coefficients of a tap wave-uniform through the
 //       scalar cache into the SGPR operand of v_pk_fma_f32, 4x4 DPP transposes before the stores,
@@ -1127,7 +1125,8 @@ __device__ __forceinline__ void mfma_store_pending(const GeoArgs& geo, MfmaPendi
     pend.valid = false;
 }
 
-// Register-resident, software-pipelined variant for windows of 12 * NB3 steps (<= 192 taps).
+// Register-resident, software-pipelined variant for windows of 12 * NB3 steps (NB3 = 1..3: <= 144 taps;
+// with a 192-tap tile in registers the build spilled).
 //  * The whole coefficient tile of a unit (3 * NB3 dwordx4 per lane) sits in registers.  As soon as
 //    a block has been used, its register is refilled with the same block of the NEXT unit's tile --
 //    requested a full unit time (2-5 us) before its first use.  The vector memory pipe is shared
@@ -1151,6 +1150,7 @@ __device__ __forceinline__ void mfma_unit_run(const GeoArgs& geo, const ItemCtx&
                                               v2f (&x)[kRing][G], MfmaTileRegs<NB3>& regs,
                                               MfmaPending<G>& pend, uint32_t unit_next, bool has_next,
                                               WaveTrace& wt) {
+    static_assert(NB3 >= 1 && NB3 <= 3, "windows of 48, 96 or 144 taps");
     constexpr uint32_t kBlocks = 3 * NB3, kSteps = 4 * kBlocks;
     typedef const v4f __attribute__((address_space(1)))* gptr_v4f;
     const uint32_t jump = geo.row_stride - geo.a * 2;  // dwords skipped between two period rows
@@ -1230,13 +1230,16 @@ __device__ __forceinline__ void mfma_unit_run(const GeoArgs& geo, const ItemCtx&
 }
 
 // ---- double-buffered kernel ------------------------------------------------------------------------
-// One 16-wave workgroup per CU owning two LDS images.  The first `producers` waves only stage:
+// One 12-wave workgroup per CU owning two LDS images.  The first `producers` waves only stage:
 // wait until every consumer has left an image, claim the next work item, DMA it in, publish it.
-// The other waves only compute: class tiles of the published image are claimed one at a time, and
-// a wave that finds none left moves straight on to the other image -- no workgroup barrier anywhere,
-// so staging, the uneven progress of the waves (the SIMD arbiter favours the oldest) and the tile
-// count not dividing the wave count cost nothing as long as an image is staged (~4-7 us) faster
-// than its tiles are consumed (~14 us).
+// The other waves only compute: matrix-core work units of the published image are claimed one at a
+// time, and a wave that finds none left moves straight on to the other image -- no workgroup barrier
+// anywhere, so staging, the uneven progress of the waves (the SIMD arbiter favours the oldest) and the
+// unit count not dividing the wave count cost nothing as long as an image is staged (~4-7 us) faster
+// than its units are consumed (~14 us).
+// MF = period groups per unit (bits 0-3) | RSMP_FIR_MFMA_DBG << 4 | NB3 << 6 | FLAT << 9; NB3 = 0: the
+// coefficients go through a ring (process_unit_mfma), else the tile of 48 * NB3 taps sits in registers
+// (mfma_consumer_stream).  CG, C2 and NT are those of fir_periodic_kernel; only <2, true, 8> is built.
 //
 // LDS control words (u32): [0..1] tile_counter per image, [2..3] consumers that have left the
 // image (cumulative over its uses), [4..5] sequence number + 1 of the item the image holds,
@@ -1382,8 +1385,9 @@ __device__ __forceinline__ void mfma_consumer_stream(const GeoArgs& geo, float* 
 }
 
 template <int CG, bool C2, int NT, int MF, bool DIAG>
-__global__ __launch_bounds__(MF ? 768 : 1024) void fir_periodic_db_kernel(const FirStreamDesc* __restrict__ descs,
-                                                               GeoArgs geo_arg) {
+__global__ __launch_bounds__(768) void fir_periodic_db_kernel(const FirStreamDesc* __restrict__ descs,
+                                                              GeoArgs geo_arg) {
+    static_assert((MF & 15) != 0, "matrix-core consumers only");
     GeoArgs geo = geo_arg;
     if constexpr (!DIAG) {
         geo.debug = 0;
@@ -1413,7 +1417,7 @@ __global__ __launch_bounds__(MF ? 768 : 1024) void fir_periodic_db_kernel(const 
         // is waited for between producers except the turn to claim (claims stay in sequence order
         // so that the first failed claim is also the last item).  Otherwise the producers stage
         // every image together.
-        const bool own_image = producers == geo.images && MF != 0;
+        const bool own_image = producers == geo.images;
         uint32_t* claim_turn = ctrl + 28;
         for (uint32_t s = own_image ? wave : 0;; s += own_image ? geo.images : 1) {
             const uint32_t b = s & imask;
@@ -1489,74 +1493,72 @@ __global__ __launch_bounds__(MF ? 768 : 1024) void fir_periodic_db_kernel(const 
             }
             if (own_image || n + 1 == producers * ((s >> ishift) + 1)) {   // the last one to arrive publishes the image
                 lds_store_release(ready + b, s + 1);
-                if constexpr (MF != 0) {
-                    // ... and then computes the wrap variant of the item's wrap classes from the staged
-                    // image (row 1023 on the window one frame earlier, resampler_fir.rs:544, :562-565):
-                    // lane = period, 2 channels.  It is 0.5 % of the item's arithmetic; the consumers
-                    // only pick the result up in their store path.
-                    if (geo.inline_wraps && item != kNoItem) {
-                        float* wv = lds + kDbCtrlWords + geo.images * image_len + b * mfma_wrap_words(geo.pw);
-                        const uint32_t wstride = mfma_wrap_words(geo.pw) / kMfmaWrapMax;   // floats per wrap class
-                        const_f32_ptr wrow = (const_f32_ptr)(d.coeffs) + static_cast<size_t>(1023) * d.taps;
-                        gconst_u32_ptr wrap_bits = (gconst_u32_ptr)d.wrap_bits;
-                        const uint32_t num = geo.a / geo.r, jump = geo.row_stride - 2 * geo.a;
-                        const uint32_t p = lane < geo.pw ? lane : 0;
-                        const float* row = rows + p * geo.row_stride;
-                        for (uint32_t i = 0; i < geo.r && i < kMfmaWrapMax && !(geo.debug & 1024); ++i) {
-                            const int32_t ws = static_cast<int32_t>(i * num) - 1;   // first frame of the window
-                            v2f acc = v2f{0.f, 0.f};
-                            uint32_t m = 0;
-                            if (ws < 0) {   // i == 0: the first tap falls on the frame in front of the period
-                                const v2f xv = *reinterpret_cast<const v2f*>(xprev + p * 2);
-                                const float w = wrow[0];
-                                acc.x = w * xv.x;
-                                acc.y = w * xv.y;
-                                m = 1;
-                            }
-                            // the remaining taps are consecutive frames: up to the end of the period row,
-                            // then on in the next row
-                            const uint32_t f0 = static_cast<uint32_t>(ws + static_cast<int32_t>(m));
-                            const uint32_t in_row = f0 < geo.a ? (geo.a - f0 < d.taps - m ? geo.a - f0 : d.taps - m) : 0;
-                            const float* px = row + 2 * f0;
-                            const_f32_ptr pw_ = wrow + m;
-                            auto run = [&](uint32_t count) {
-                                uint32_t q = 0;
-                                for (; q + 8 <= count; q += 8) {
-                                    v2f xv[8];
-#pragma unroll
-                                    for (int e = 0; e < 8; ++e) xv[e] = *reinterpret_cast<const v2f*>(px + 2 * (q + e));
-#pragma unroll
-                                    for (int e = 0; e < 8; ++e) {
-                                        const float w = pw_[q + e];
-                                        acc.x = fmaf(w, xv[e].x, acc.x);
-                                        acc.y = fmaf(w, xv[e].y, acc.y);
-                                    }
-                                }
-                                for (; q < count; ++q) {
-                                    const v2f x1 = *reinterpret_cast<const v2f*>(px + 2 * q);
-                                    const float w = pw_[q];
-                                    acc.x = fmaf(w, x1.x, acc.x);
-                                    acc.y = fmaf(w, x1.y, acc.y);
-                                }
-                                px += 2 * count;
-                                pw_ += count;
-                            };
-                            run(in_row);
-                            px += jump;
-                            run(d.taps - m - in_row);
-                            const int32_t nw = ig.n_block0 + static_cast<int32_t>(p * geo.b + i * geo.den);
-                            uint32_t take = 0;
-                            if (lane < geo.pw && nw >= 0 && nw < static_cast<int32_t>(d.n_out)) {
-                                const uint32_t K = static_cast<uint32_t>(ig.k_block0 + static_cast<int32_t>(p * geo.r + i));
-                                take = (wrap_bits[K >> 5] >> (K & 31)) & 1u;
-                            }
-                            if (lane * 4 < wstride)
-                                *reinterpret_cast<v4f*>(wv + i * wstride + lane * 4) =
-                                    v4f{acc.x, acc.y, __uint_as_float(take), 0.f};
+                // ... and then computes the wrap variant of the item's wrap classes from the staged
+                // image (row 1023 on the window one frame earlier, resampler_fir.rs:544, :562-565):
+                // lane = period, 2 channels.  It is 0.5 % of the item's arithmetic; the consumers
+                // only pick the result up in their store path.
+                if (geo.inline_wraps && item != kNoItem) {
+                    float* wv = lds + kDbCtrlWords + geo.images * image_len + b * mfma_wrap_words(geo.pw);
+                    const uint32_t wstride = mfma_wrap_words(geo.pw) / kMfmaWrapMax;   // floats per wrap class
+                    const_f32_ptr wrow = (const_f32_ptr)(d.coeffs) + static_cast<size_t>(1023) * d.taps;
+                    gconst_u32_ptr wrap_bits = (gconst_u32_ptr)d.wrap_bits;
+                    const uint32_t num = geo.a / geo.r, jump = geo.row_stride - 2 * geo.a;
+                    const uint32_t p = lane < geo.pw ? lane : 0;
+                    const float* row = rows + p * geo.row_stride;
+                    for (uint32_t i = 0; i < geo.r && i < kMfmaWrapMax && !(geo.debug & 1024); ++i) {
+                        const int32_t ws = static_cast<int32_t>(i * num) - 1;   // first frame of the window
+                        v2f acc = v2f{0.f, 0.f};
+                        uint32_t m = 0;
+                        if (ws < 0) {   // i == 0: the first tap falls on the frame in front of the period
+                            const v2f xv = *reinterpret_cast<const v2f*>(xprev + p * 2);
+                            const float w = wrow[0];
+                            acc.x = w * xv.x;
+                            acc.y = w * xv.y;
+                            m = 1;
                         }
-                        __builtin_amdgcn_s_waitcnt(0);
-                        lds_store_release(wflag + b, s + 1);
+                        // the remaining taps are consecutive frames: up to the end of the period row,
+                        // then on in the next row
+                        const uint32_t f0 = static_cast<uint32_t>(ws + static_cast<int32_t>(m));
+                        const uint32_t in_row = f0 < geo.a ? (geo.a - f0 < d.taps - m ? geo.a - f0 : d.taps - m) : 0;
+                        const float* px = row + 2 * f0;
+                        const_f32_ptr pw_ = wrow + m;
+                        auto run = [&](uint32_t count) {
+                            uint32_t q = 0;
+                            for (; q + 8 <= count; q += 8) {
+                                v2f xv[8];
+#pragma unroll
+                                for (int e = 0; e < 8; ++e) xv[e] = *reinterpret_cast<const v2f*>(px + 2 * (q + e));
+#pragma unroll
+                                for (int e = 0; e < 8; ++e) {
+                                    const float w = pw_[q + e];
+                                    acc.x = fmaf(w, xv[e].x, acc.x);
+                                    acc.y = fmaf(w, xv[e].y, acc.y);
+                                }
+                            }
+                            for (; q < count; ++q) {
+                                const v2f x1 = *reinterpret_cast<const v2f*>(px + 2 * q);
+                                const float w = pw_[q];
+                                acc.x = fmaf(w, x1.x, acc.x);
+                                acc.y = fmaf(w, x1.y, acc.y);
+                            }
+                            px += 2 * count;
+                            pw_ += count;
+                        };
+                        run(in_row);
+                        px += jump;
+                        run(d.taps - m - in_row);
+                        const int32_t nw = ig.n_block0 + static_cast<int32_t>(p * geo.b + i * geo.den);
+                        uint32_t take = 0;
+                        if (lane < geo.pw && nw >= 0 && nw < static_cast<int32_t>(d.n_out)) {
+                            const uint32_t K = static_cast<uint32_t>(ig.k_block0 + static_cast<int32_t>(p * geo.r + i));
+                            take = (wrap_bits[K >> 5] >> (K & 31)) & 1u;
+                        }
+                        if (lane * 4 < wstride)
+                            *reinterpret_cast<v4f*>(wv + i * wstride + lane * 4) =
+                                v4f{acc.x, acc.y, __uint_as_float(take), 0.f};
                     }
+                    __builtin_amdgcn_s_waitcnt(0);
+                    lds_store_release(wflag + b, s + 1);
                 }
             }
             if (item == kNoItem) break;
@@ -1565,52 +1567,26 @@ __global__ __launch_bounds__(MF ? 768 : 1024) void fir_periodic_db_kernel(const 
     }
 
     // ---- consumer --------------------------------------------------------------------------------
-    if constexpr (MF != 0 && ((MF >> 6) & 7) != 0) {
-        mfma_consumer_stream<(MF & 15), ((MF >> 9) & 1) != 0, ((MF >> 6) & 7)>(geo, lds, image_len, lane, wt);
-        return;
-    }
-    for (uint32_t s = 0;; ++s) {
-        const uint32_t b = s & imask;
-        const float* xprev = lds + kDbCtrlWords + b * image_len;
-        const float* rows = xprev + geo.xprev_len;
-        wt.event(1);
-        while (lds_load_acquire(ready + b) != s + 1) __builtin_amdgcn_s_sleep(2);
-        wt.event(2);
-        const uint32_t item = __builtin_amdgcn_readfirstlane(item_id[b]);
-        if (item == kNoItem) break;
-        const uint32_t stream_idx = item / geo.blocks_per_stream;
-        const FirStreamDesc d = load_uniform(descs + stream_idx);
-        const ItemGeom ig = item_geom(geo, d, item - stream_idx * geo.blocks_per_stream);
-        const ItemCtx cx = item_ctx<CG, C2>(geo, d, ig, rows, xprev, lane, stream_idx);
-        if constexpr (MF == 0) {
-            uint32_t t_claim = 0;
-            if (lane == 0) t_claim = atomicAdd(tile_counter + b, 1u);
-            uint32_t t = __builtin_amdgcn_readfirstlane(t_claim);
-            TileMeta tm_cur = load_uniform(cx.metas + (t < geo.n_tiles ? t : 0));
-            while (t < geo.n_tiles) {
-                wt.event(6);
-                // The image is free again only when its last tile is done, and the SIMD arbiter
-                // serves the oldest wave first: a young wave that picks up one of the last tiles
-                // would hold the image for several tile times while everyone else has moved on.
-                // Late tiles therefore run at raised priority (the later, the higher); the next
-                // image's first tiles yield.
-                const uint32_t from_end = geo.n_tiles - 1 - t;
-                if (from_end < 3) __builtin_amdgcn_s_setprio(3);
-                else if (from_end < 6) __builtin_amdgcn_s_setprio(2);
-                else if (from_end < 9) __builtin_amdgcn_s_setprio(1);
-                else __builtin_amdgcn_s_setprio(0);
-                if (lane == 0) t_claim = atomicAdd(tile_counter + b, 1u);   // next tile, consumed below
-                process_tile<CG, C2, NT>(geo, cx, t, tm_cur);
-                wt.event(7);
-                t = __builtin_amdgcn_readfirstlane(t_claim);
-                tm_cur = load_uniform(cx.metas + (t < geo.n_tiles ? t : 0));
-            }
-            __builtin_amdgcn_s_setprio(0);
-        } else {
-            // Matrix-core units.  Two claims are kept in flight: the unit after the current one must
-            // be known when the current one starts (its coefficients and addressing are requested
-            // then), and the claim's LDS round trip should never be waited for.
-            constexpr int G = MF & 15, DBG = (MF >> 4) & 3, NB3 = (MF >> 6) & 7;
+    constexpr int G = MF & 15, DBG = (MF >> 4) & 3, NB3 = (MF >> 6) & 7;
+    if constexpr (NB3 != 0) {
+        mfma_consumer_stream<G, ((MF >> 9) & 1) != 0, NB3>(geo, lds, image_len, lane, wt);
+    } else {
+        for (uint32_t s = 0;; ++s) {
+            const uint32_t b = s & imask;
+            const float* xprev = lds + kDbCtrlWords + b * image_len;
+            const float* rows = xprev + geo.xprev_len;
+            wt.event(1);
+            while (lds_load_acquire(ready + b) != s + 1) __builtin_amdgcn_s_sleep(2);
+            wt.event(2);
+            const uint32_t item = __builtin_amdgcn_readfirstlane(item_id[b]);
+            if (item == kNoItem) break;
+            const uint32_t stream_idx = item / geo.blocks_per_stream;
+            const FirStreamDesc d = load_uniform(descs + stream_idx);
+            const ItemGeom ig = item_geom(geo, d, item - stream_idx * geo.blocks_per_stream);
+            const ItemCtx cx = item_ctx<CG, C2>(geo, d, ig, rows, xprev, lane, stream_idx);
+            // Two claims are kept in flight: the unit after the current one must be known when the
+            // current one starts (its coefficients and addressing are requested then), and the claim's
+            // LDS round trip should never be waited for.
             uint32_t c1 = 0, c2 = 0;
             if (lane == 0) {
                 c1 = atomicAdd(tile_counter + b, 1u);
@@ -1618,34 +1594,35 @@ __global__ __launch_bounds__(MF ? 768 : 1024) void fir_periodic_db_kernel(const 
             }
             uint32_t t = __builtin_amdgcn_readfirstlane(c1);
             uint32_t t_next = __builtin_amdgcn_readfirstlane(c2);
-            // Late units of an image outrank the rest (see the vector consumer above).
+            // The image is free again only when its last unit is done, and the SIMD arbiter serves the
+            // oldest wave first: a young wave that picks up one of the last units would hold the image
+            // for several unit times while everyone else has moved on.  Late units therefore outrank
+            // the rest.
             auto set_priority = [&](uint32_t unit) {
                 if (geo.n_tiles - 1 - unit < 4) __builtin_amdgcn_s_setprio(2);
                 else __builtin_amdgcn_s_setprio(0);
             };
-            if constexpr (NB3 == 0) {
-                // first frame of a tile's window: floor(16 T a / b), < 2^16 * 2^12 (32-bit math)
-                auto base_of = [&](uint32_t unit) { return ((unit >> geo.unit_shift) * kMfmaClassTile * geo.a) / geo.b; };
-                const bool flat = geo.row_stride == 2 * geo.a;
-                MfmaPipe pipe;
-                pipe.primed = false;
-                while (t < geo.n_tiles) {
-                    wt.event(6);
-                    set_priority(t);
-                    if (lane == 0) c2 = atomicAdd(tile_counter + b, 1u);   // the unit after the next
-                    const bool more = t_next < geo.n_tiles;
-                    const uint32_t ob = base_of(t);
-                    if (flat) process_unit_mfma<G, true, DBG>(geo, cx, rows, t, ob, pipe, t_next, more, wt);
-                    else process_unit_mfma<G, false, DBG>(geo, cx, rows, t, ob, pipe, t_next, more, wt);
-                    wt.event(7);
-                    t = t_next;
-                    t_next = __builtin_amdgcn_readfirstlane(c2);
-                }
+            // first frame of a tile's window: floor(16 T a / b), < 2^16 * 2^12 (32-bit math)
+            auto base_of = [&](uint32_t unit) { return ((unit >> geo.unit_shift) * kMfmaClassTile * geo.a) / geo.b; };
+            const bool flat = geo.row_stride == 2 * geo.a;
+            MfmaPipe pipe;
+            pipe.primed = false;
+            while (t < geo.n_tiles) {
+                wt.event(6);
+                set_priority(t);
+                if (lane == 0) c2 = atomicAdd(tile_counter + b, 1u);   // the unit after the next
+                const bool more = t_next < geo.n_tiles;
+                const uint32_t ob = base_of(t);
+                if (flat) process_unit_mfma<G, true, DBG>(geo, cx, rows, t, ob, pipe, t_next, more, wt);
+                else process_unit_mfma<G, false, DBG>(geo, cx, rows, t, ob, pipe, t_next, more, wt);
+                wt.event(7);
+                t = t_next;
+                t_next = __builtin_amdgcn_readfirstlane(c2);
             }
             __builtin_amdgcn_s_setprio(0);
+            // this wave's reads of image b have all returned (their values were consumed above)
+            if (lane == 0) __hip_atomic_fetch_add(left + b, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        // this wave's reads of image b have all returned (their values were consumed above)
-        if (lane == 0) __hip_atomic_fetch_add(left + b, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
 
@@ -1800,15 +1777,10 @@ PeriodicGeometry geometry_for(uint64_t num, uint64_t den, uint32_t taps, uint32_
     // most); matrix-core path den >= 16 and at most kMfmaWrapMax wrap classes per super period
     // (only the register-resident variant picks the results up: windows <= 144 taps, 1-2 groups/unit)
     static const bool ring_forced = rsmp::knob("RSMP_FIR_MFMA_RING") != nullptr;
-    constexpr bool nowrap = false;
-    // (144 taps at most: with a 192-tap tile in registers the register-resident build spills)
-    const bool mfma_regs = want_mfma && knob_mfma <= 2 && g.row_len <= 144 && !ring_forced && !nowrap;
+    // (144 taps at most: with a 192-tap tile in registers the register-resident build spilled)
+    const bool mfma_regs = want_mfma && knob_mfma <= 2 && g.row_len <= 144 && !ring_forced;
     g.inline_wraps = want_mfma ? (mfma_regs && den >= kMfmaClassTile && r <= kMfmaWrapMax) : den >= kClassTile;
 
-    // RSMP_FIR_PRODUCERS = n: n producer waves; for the vector kernels it also selects the
-    // double-buffered workgroup (measured slower than two single-image workgroups per CU: 12
-    // consumer waves cannot hide the scalar-cache latency that 24 can)
-    constexpr int knob_db = -1;
     bool two_per_cu = false;   // set by fit(): the single-image vector kernel with two workgroups per CU
     auto fit = [&](uint32_t cg) -> bool {
         two_per_cu = false;
@@ -1828,55 +1800,33 @@ PeriodicGeometry geometry_for(uint64_t num, uint64_t den, uint32_t taps, uint32_
         g.cg = cg;
         g.lp = lp;
         g.row_stride = stride;
-        // Fast path: two images in one workgroup (fir_periodic_db_kernel), if that keeps >= 75 % of
-        // the lanes busy.
-        // Fast path: several images in one workgroup (fir_periodic_db_kernel).  Per image: + 96 floats of
-        // read-ahead padding; matrix-core path: + the wrap results.  RSMP_FIR_IMAGES=4 selects a ring of
-        // four 32-period images, one per producer, instead of two 64-period ones (producers up to three
-        // items ahead; measured equal: the doubled per-item work eats what the extra slack gains).
-        constexpr int knob_images = 0;
-        auto db_fit = [&](uint32_t images, uint32_t pw_cap, uint32_t& pw_out, uint32_t& bytes_out) -> bool {
-            if (pw_cap > pw_max) pw_cap = pw_max;
-            for (uint32_t pw = pw_cap; pw * 4 >= pw_cap * 3 && pw > 0; --pw) {
-                const uint32_t bytes = (kDbCtrlWords + images * db_image_len(xprev_len_of(pw, channels), pw, stride) +
-                                        (want_mfma ? images * mfma_wrap_words(pw) : 0)) * 4;
-                if (bytes <= kLdsMax) {
-                    pw_out = pw;
-                    bytes_out = bytes;
-                    return true;
-                }
-            }
-            return false;
-        };
-        uint32_t pw = 0, bytes = 0;
-        bool have_db = false;
-        if (want_mfma && knob_mfma == 2 && knob_images == 4 && pw_max == 64 && db_fit(4, 32, pw, bytes) && pw == 32) {
-            g.images = 4;
-            have_db = true;
-        } else if ((knob_db > 0 || want_mfma) && db_fit(2, 64, pw, bytes)) {
+        if (want_mfma) {
+            // Two images in one workgroup (fir_periodic_db_kernel), if that keeps >= 75 % of the lanes
+            // busy; else periodic_geometry() retries with the vector kernels.  Per image: + 96 floats of
+            // read-ahead padding + the wrap results.  (A ring of four 32-period images, one per producer,
+            // measured equal: the doubled per-item work ate what the extra slack gained.  The same
+            // workgroup around the vector tile code measured slower than two single-image workgroups
+            // per CU: 12 consumer waves cannot hide the scalar-cache latency that 24 can.)
+            auto db_bytes = [&](uint32_t pw) -> uint32_t {
+                return (kDbCtrlWords + 2 * (db_image_len(xprev_len_of(pw, channels), pw, stride) + mfma_wrap_words(pw))) * 4;
+            };
+            uint32_t pw = pw_max;
+            while (pw * 4 >= pw_max * 3 && db_bytes(pw) > kLdsMax) --pw;
+            if (pw * 4 < pw_max * 3) return false;
             g.images = 2;
-            have_db = true;
-        }
-        if (have_db) {
             g.pw = pw;
-            g.producers = knob_db > 0 && knob_db < 8 ? static_cast<uint32_t>(knob_db) : 4u;
-            g.lds_bytes = bytes;
-            if (want_mfma) {
-                // two consumer waves per SIMD keep the matrix pipe busy; more only add arbitration
-                constexpr int knob_consumers = 8;
-                g.mfma = static_cast<uint32_t>(knob_mfma);
-                // a work unit spans knob_mfma groups of 16 periods
-                const uint32_t groups = (pw + 15) / 16;
-                g.n_units = g.n_tiles * ((groups + g.mfma - 1) / g.mfma);
-                g.waves = g.producers + static_cast<uint32_t>(knob_consumers);
-                if (g.waves > 12) g.waves = 12;   // __launch_bounds__(768) of the matrix-core kernels
-            } else {
-                g.waves = 16;
-            }
+            g.producers = 4;
+            g.lds_bytes = db_bytes(pw);
+            g.mfma = static_cast<uint32_t>(knob_mfma);
+            // a work unit spans knob_mfma groups of 16 periods
+            const uint32_t groups = (pw + 15) / 16;
+            g.n_units = g.n_tiles * ((groups + g.mfma - 1) / g.mfma);
+            // 4 producers + 8 consumers: two consumer waves per SIMD keep the matrix pipe busy, more only
+            // add arbitration (and 12 waves are the __launch_bounds__(768) of the kernel)
+            g.waves = 12;
             return true;
         }
-        if (want_mfma) return false;   // periodic_geometry() retries with the vector kernels
-        pw = rows_in(kLdsTwoPerCu);
+        uint32_t pw = rows_in(kLdsTwoPerCu);
         two_per_cu = pw * 4 >= pw_max * 3;
         if (!two_per_cu) pw = rows_in(kLdsMax);  // < 75% of the lanes: use the whole LDS
         if (pw > pw_max) pw = pw_max;
@@ -1896,17 +1846,14 @@ PeriodicGeometry geometry_for(uint64_t num, uint64_t den, uint32_t taps, uint32_
         // and only one single-image workgroup fits a CU -- staging and arithmetic then take turns.  One channel per
         // lane halves the periods per image: where that is what lets two workgroups share a CU it is faster
         // (8 channels 96 -> 44.1 kHz: 0.73 -> 0.62 ms per 20 M frames).
-        constexpr int knob_cg = 0;
-        bool ok = false;
-        if (knob_cg != 1) ok = fit(2);
-        if (knob_cg != 2 && (!ok || !two_per_cu)) {
+        const bool ok2 = fit(2);
+        if (!ok2 || !two_per_cu) {
             const PeriodicGeometry g2 = g;
-            const bool ok2 = ok;
-            if (fit(1) && (two_per_cu || !ok2)) ok = true;
-            else if (ok2) { g = g2; ok = true; }
-            else ok = false;
+            if (!(fit(1) && (two_per_cu || !ok2))) {
+                if (!ok2) return g;
+                g = g2;
+            }
         }
-        if (!ok) return g;
     }
     g.ok = true;
     return g;
@@ -2149,10 +2096,10 @@ hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
     const uint32_t slots = cus * (geo.lds_bytes > kLdsTwoPerCu ? 1u : 2u);   // workgroups that fit
     const dim3 grid(args.total_items < slots ? args.total_items : slots);
     args.work_counter = d_work_counter;
-    // every claiming wave makes exactly one failing claim: one per workgroup, or one per producer when
-    // each producer owns an image
-    const bool own_image = geo.mfma && geo.producers == geo.images;
-    args.n_claimers = grid.x * (own_image ? geo.images : 1u);
+    // every claiming wave makes exactly one failing claim: one wave per workgroup claims (the kernel's
+    // mode in which every producer owns an image and claims for itself needs producers == images, and
+    // geometry_for() gives 4 producers for 2 images)
+    args.n_claimers = grid.x;
     static const char* trace_path = rsmp::knob("RSMP_FIR_TRACE");
     static unsigned long long* d_trace = nullptr;
     const size_t trace_words = 6ull * grid.x;
@@ -2174,44 +2121,40 @@ hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
     // Dynamic LDS above 64 KiB must be opted into, once per kernel and device.
     static std::mutex mu;
     static std::map<std::pair<int, int>, bool> granted;
-    // variants: 0 = two channels, one lane per period; 1 = CG 2, any even channel count; 2 = CG 1;
-    // +3 for the double-buffered kernel; 6 / 7 = matrix-core consumers (2 / 4 period groups per unit).
-    // (4-tap chunks with 16-wave workgroups at 8 waves per SIMD measured 13 % slower than 8-tap
-    // chunks: the 64-VGPR cap spills.)
+    // Slots of the kernel table below.  0..2 = vector kernel: two channels with one lane per period / CG 2,
+    // any even channel count / CG 1.  (4-tap chunks with 16-wave workgroups at 8 waves per SIMD measured
+    // 13 % slower than 8-tap chunks: the 64-VGPR cap spills.)  Matrix-core consumers: 3 / 4 = coefficient
+    // ring (any window length), 2 / 4 period groups per unit; 5..7 = ring timing experiments
+    // (RSMP_FIR_MFMA_DBG 1..3); 8..13 = coefficient tile in registers, 2 groups per unit, windows of
+    // 48 / 96 / 144 taps, padded (8..10) or back-to-back (11..13) rows; 14..19 = the same with 1 group.
     static const int mfma_dbg = [] {   // RSMP_FIR_MFMA_DBG: 1 hot coefficient line, 2 no LDS reads, 3 both
         const char* e = rsmp::knob("RSMP_FIR_MFMA_DBG");
         const int v = e ? atoi(e) : 0;
         return v >= 0 && v <= 3 ? v : 0;
     }();
     static const bool mfma_ring = rsmp::knob("RSMP_FIR_MFMA_RING") != nullptr;   // force the ring variant
-    // matrix-core variants: 6 / 7 = coefficient ring (any window length), 2 / 4 period groups per
-    // unit; 8..10 = ring timing experiments; 11..18 = coefficient tile in registers, windows of
-    // 48 / 96 / 144 / 192 taps (2 groups per unit), padded (11..14) or back-to-back (15..18) rows
-    const uint32_t nb3 = geo.row_len % 48 == 0 && geo.row_len <= 144 ? geo.row_len / 48 : 0;
+    const uint32_t nb3 = geo.row_len % 48 == 0 && geo.row_len <= 144 ? geo.row_len / 48 : 0;   // 0..3
     const bool flat_rows = geo.row_stride == 2 * geo.a;
     int variant;
-    if (!geo.mfma) variant = (geo.cg == 2 ? (geo.lp == 1 ? 0 : 1) : 2) + (geo.producers ? 3 : 0);
-    else if (geo.mfma == 4) variant = 7;
+    if (!geo.mfma) variant = geo.cg == 2 ? (geo.lp == 1 ? 0 : 1) : 2;
+    else if (geo.mfma == 4) variant = 4;
     else if (geo.mfma == 1 && (!nb3 || mfma_ring)) return hipErrorInvalidValue;   // G = 1 exists only register-resident
-    else if (mfma_dbg) variant = 7 + mfma_dbg;
-    else if (nb3 && !mfma_ring && geo.mfma == 1) variant = 18 + static_cast<int>(nb3) + (flat_rows ? 4 : 0);
-    else if (nb3 && !mfma_ring) variant = 10 + static_cast<int>(nb3) + (flat_rows ? 4 : 0);
-    else variant = 6;
-static const char* trace_env = rsmp::knob("RSMP_FIR_TRACE");
+    else if (mfma_dbg) variant = 4 + mfma_dbg;
+    else if (nb3 && !mfma_ring) variant = (geo.mfma == 1 ? 13 : 7) + static_cast<int>(nb3) + (flat_rows ? 3 : 0);
+    else variant = 3;
+    static const char* trace_env = rsmp::knob("RSMP_FIR_TRACE");
     static const char* wtrace_env = rsmp::knob("RSMP_FIR_WTRACE");
     const bool diag = args.debug != 0 || trace_env != nullptr || wtrace_env != nullptr;
 #define RSMP_SK(cg, c2, D) reinterpret_cast<const void*>(fir_periodic_kernel<cg, c2, 8, D>)
 #define RSMP_DB(cg, c2, mf, D) reinterpret_cast<const void*>(fir_periodic_db_kernel<cg, c2, 8, mf, D>)
 #define RSMP_MF(nb3v, flatv, D) RSMP_DB(2, true, 2 + 64 * (nb3v) + 512 * (flatv), D)
 #define RSMP_MF1(nb3v, flatv, D) RSMP_DB(2, true, 1 + 64 * (nb3v) + 512 * (flatv), D)
-#define RSMP_FNS(D)                                                                                          \
-    {RSMP_SK(2, true, D), RSMP_SK(2, false, D), RSMP_SK(1, false, D), RSMP_DB(2, true, 0, D), RSMP_DB(2, false, 0, D), \
-     RSMP_DB(1, false, 0, D), RSMP_DB(2, true, 2, D), RSMP_DB(2, true, 4, D), RSMP_DB(2, true, 2 + 16, D),            \
-     RSMP_DB(2, true, 2 + 32, D), RSMP_DB(2, true, 2 + 48, D), RSMP_MF(1, 0, D), RSMP_MF(2, 0, D), RSMP_MF(3, 0, D), \
-     RSMP_MF(4, 0, D), RSMP_MF(1, 1, D), RSMP_MF(2, 1, D), RSMP_MF(3, 1, D), RSMP_MF(4, 1, D), RSMP_MF1(1, 0, D),    \
-     RSMP_MF1(2, 0, D), RSMP_MF1(3, 0, D), RSMP_MF1(4, 0, D), RSMP_MF1(1, 1, D), RSMP_MF1(2, 1, D),                  \
-     RSMP_MF1(3, 1, D), RSMP_MF1(4, 1, D)}
-    static const void* const fns_all[2][27] = {RSMP_FNS(false), RSMP_FNS(true)};
+#define RSMP_FNS(D)                                                                                                  \
+    {RSMP_SK(2, true, D), RSMP_SK(2, false, D), RSMP_SK(1, false, D), RSMP_DB(2, true, 2, D), RSMP_DB(2, true, 4, D),  \
+     RSMP_DB(2, true, 2 + 16, D), RSMP_DB(2, true, 2 + 32, D), RSMP_DB(2, true, 2 + 48, D), RSMP_MF(1, 0, D),          \
+     RSMP_MF(2, 0, D), RSMP_MF(3, 0, D), RSMP_MF(1, 1, D), RSMP_MF(2, 1, D), RSMP_MF(3, 1, D), RSMP_MF1(1, 0, D),      \
+     RSMP_MF1(2, 0, D), RSMP_MF1(3, 0, D), RSMP_MF1(1, 1, D), RSMP_MF1(2, 1, D), RSMP_MF1(3, 1, D)}
+    static const void* const fns_all[2][20] = {RSMP_FNS(false), RSMP_FNS(true)};
     const void* const* fns = fns_all[diag ? 1 : 0];
 #undef RSMP_FNS
 #undef RSMP_SK

@@ -66,9 +66,6 @@ __host__ __device__ constexpr uint32_t row_bytes(int planes) { return planes == 
 // 2^-14); samples of magnitude >= 16 overflow to infinity there -- the launch's non-finite check then has
 // the item recomputed in the reference's f32 form.
 constexpr float kXScale = 4096.0f;        // 2^12 (the sample scale of an item without samples; see `peak`)
-#ifndef RSMP_EXP
-#define RSMP_EXP 0   // A/B builds (make exp): timing experiments, never shipped
-#endif
 constexpr uint32_t kPeakHeadroom = 4;     // a predicted scale leaves 2^4 above the pair's latest peak
 constexpr uint32_t kPeakQuiet = 10;       // an item whose peak lies more than 2^-10 below what its scale allows (2^-6 below the prediction) is redone
 constexpr uint32_t kPeakMax = 138;        // no scale is derived from a peak of 2^11 and above (samples of 2^13 and above overflow the planes: redone)
