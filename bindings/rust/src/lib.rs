@@ -119,6 +119,8 @@ extern "C" {
     fn rsmp_fir_lockstep_table_rebinds(ls: *const rsmp_fir_lockstep, rebinds: *mut usize) -> c_int;
     fn rsmp_fir_lockstep_run_bulk(ls: *mut rsmp_fir_lockstep, total_frames: usize, chunk_frames: usize, in_offset_frames: usize,
                                   append: c_int, stream: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_fir_lockstep_run_bulk_v(ls: *mut rsmp_fir_lockstep, total_frames: *const usize, chunk_frames: usize, in_offset_frames: usize,
+                                    append: c_int, stream: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_fir_lockstep_stats(ls: *const rsmp_fir_lockstep, out: *mut u64, n: usize) -> c_int;
     fn rsmp_fir_lockstep_set_drift_policy(ls: *mut rsmp_fir_lockstep, tolerance_frames: f64, check_frames: usize) -> c_int;
 }

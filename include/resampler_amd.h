@@ -171,8 +171,14 @@ int rsmp_fir_batch_resample_bulk_device(rsmp_fir* const* rs, size_t n, const flo
  * handles, which the library keeps from launch to launch for as long as the handles are touched through nothing else; the states are
  * written back into the handles before the call returns, so the call returns when the launch is THROUGH, not when it is enqueued);
  * planner = 0 never; planner = -1 -- what rsmp_fir_batch_resample_bulk_device does -- where the batch has at least 16 different
- * states.  The device planner takes batches of one channel count and one buffer length, calls of at most 2048 frames, at least eight
- * of them, and output buffers of rsmp_fir_bulk_output_bound; anything else is planned on the host whatever `planner` says.
+ * states.  The device planner takes batches of one channel count, whole calls (in_lens[i] a multiple of chunk_len) of at most 2048
+ * frames, at least eight of them, and output buffers with room for the outputs the launch makes in exact arithmetic + 2 frames
+ * (rsmp_fir_bulk_output_bound's value is always enough for a stream's first launch; it grows with the frames a stream has
+ * buffered, so it is no test); anything else is planned on the host whatever `planner` says.  Buffer lengths: planner = -1 takes
+ * batches of ONE buffer length only; planner = 1 also takes batches whose in_lens differ (zero among them: such a stream makes no
+ * call; the eight calls are then asked of the longest stream) through rsmp_fir_lockstep_run_bulk_v -- unless a stream has so many
+ * frames buffered that a call could accept less than it is offered (buffered + chunk frames > 4096), which goes to the host
+ * planner before anything is launched.
  * *planned_on_device (may be null): which it was.  Same (consumed, produced), samples and end states either way. */
 int rsmp_fir_batch_resample_bulk_device_ex(rsmp_fir* const* rs, size_t n, const float* const* d_in,
                                            const size_t* in_lens, size_t chunk_len,
@@ -249,6 +255,26 @@ int rsmp_fir_lockstep_run_counts(rsmp_fir_lockstep* ls, size_t* consumed, size_t
  * remainder again, a run's calls read at fixed offsets) -- RSMP_ERR_INVALID_INPUT_BUFFER_SIZE otherwise. */
 int rsmp_fir_lockstep_run_bulk(rsmp_fir_lockstep* ls, size_t total_frames, size_t chunk_frames, size_t in_offset_frames,
                                int append, void* stream);
+/* rsmp_fir_lockstep_run_bulk with a buffer length per stream: total_frames[i] frames (HOST array, the order of `rs`,
+ * read before the call returns) from d_in[i] + in_offset_frames, in calls of chunk_frames frames, the stream's last call
+ * shorter where total_frames[i] is no multiple -- per stream exactly the calls resample/src/main.rs:226-254 makes, no
+ * others: a stream with total_frames[i] == 0 makes no call and keeps its state, counts and append position.
+ * Asynchronous on `stream` and ordered like every other device entry; ALL of a stream's calls, the short one included, are
+ * planned on the device in one run and computed by one launch per kernel build.  Limits as for rsmp_fir_lockstep_run_bulk:
+ * chunk_frames <= max_step_frames and chunk_frames + taps + 8 <= 4096 (RSMP_ERR_INVALID_INPUT_BUFFER_SIZE otherwise), at most
+ * 2^27 frames / 2^31 outputs / 2^20 calls per stream and run; the caller sizes d_out[i] for the stream's whole run, out_caps[i]
+ * stays the room of ONE call.  NULL ls / total_frames or chunk_frames == 0: RSMP_ERR_INVALID_ARGUMENT (checked before anything
+ * touches the device); all lengths zero: RSMP_OK, nothing enqueued.
+ * Counts: with calls_i = ceil(total_frames[i] / chunk_frames), rsmp_fir_lockstep_run_counts returns max_i calls_i rows; row s
+ * of stream i is its call s -- the short last call included, as row calls_i - 1 -- and (0, 0) for s >= calls_i.
+ * rsmp_fir_lockstep_counts returns every stream's OWN last call (a stream without a call keeps what it had).
+ * rsmp_fir_lockstep_sync_totals, _status, _run_slow_calls and _sync work as after any run.  An array of equal lengths gives
+ * what rsmp_fir_lockstep_run_bulk gives: the same counts, the same end states bit for bit.
+ * A ragged run is neither planned ahead nor does it keep a run that was planned ahead: the launch plans on `stream` itself, and
+ * the next rsmp_fir_lockstep_run after it plans there too.  Batches with a rate pair no bulk kernel serves run as a loop of steps
+ * in which a stream that is through takes empty calls (state-neutral; they appear in no count). */
+int rsmp_fir_lockstep_run_bulk_v(rsmp_fir_lockstep* ls, const size_t* total_frames, size_t chunk_frames,
+                                 size_t in_offset_frames, int append, void* stream);
 /* Diagnostic: calls of the last run (all streams) that the device planner's fast path declined and the plain state
  * machine did (fir_mirror_fast.h); 0 for a run executed as a loop of steps. */
 int rsmp_fir_lockstep_run_slow_calls(rsmp_fir_lockstep* ls, size_t* slow_calls);

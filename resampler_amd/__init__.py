@@ -142,6 +142,7 @@ _SIGNATURES = [
     ("rsmp_fir_lockstep_run", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
     ("rsmp_fir_lockstep_run_counts", C.c_int, [C.c_void_p, _szp, _szp, C.c_size_t]),
     ("rsmp_fir_lockstep_run_bulk", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
+    ("rsmp_fir_lockstep_run_bulk_v", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
     ("rsmp_fir_lockstep_run_slow_calls", C.c_int, [C.c_void_p, _szp]),
     ("rsmp_fir_lockstep_table_rebinds", C.c_int, [C.c_void_p, _szp]),
     ("rsmp_fir_lockstep_status", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
@@ -453,14 +454,22 @@ class FirBatch:
         self._consumed = (C.c_size_t * n)()
         self._produced = (C.c_size_t * n)()
 
-    def bind(self, d_ins, d_outs) -> None:
-        """Binds one input and one output tensor per stream (kept until the next bind)."""
+    def bind(self, d_ins, d_outs, in_lens: Optional[Sequence[int]] = None) -> None:
+        """Binds one input and one output tensor per stream (kept until the next bind).  in_lens: f32 values of every input to
+        feed, at most the tensor's (default: all of it; 0: nothing for this stream in this launch)."""
         self._keep = (list(d_ins), list(d_outs))
         for i, (a, b) in enumerate(zip(d_ins, d_outs)):
             self._in[i] = _dev_ptr(a)
             self._out[i] = _dev_ptr(b)
             self._in_lens[i] = a.numel()
             self._out_caps[i] = b.numel()
+        if in_lens is not None:
+            if len(in_lens) != len(self.resamplers):
+                raise ValueError(f"bind: {len(in_lens)} lengths for {len(self.resamplers)} streams")
+            for i, v in enumerate(in_lens):
+                if not 0 <= int(v) <= self._in_lens[i]:
+                    raise ValueError(f"bind: in_lens[{i}] = {v}, the tensor has {self._in_lens[i]} values")
+                self._in_lens[i] = int(v)
 
     def reset(self) -> None:
         lib().rsmp_fir_batch_reset(self._handles, len(self.resamplers))
@@ -595,6 +604,22 @@ class FirLockstep:
         _check(lib().rsmp_fir_lockstep_run_bulk(self._h, total_frames, chunk_frames, in_offset_frames, 1 if append else 0,
                                                 C.c_void_p(stream or 0)))
         self._last_run = total_frames // chunk_frames
+
+    def run_bulk_v(self, total_frames: Sequence[int], chunk_frames: int, in_offset_frames: int = 0, append: bool = False,
+                   stream: Optional[int] = None) -> None:
+        """run_bulk with a buffer length per stream (rsmp_fir_lockstep_run_bulk_v): stream i makes the driver loop's calls
+        for total_frames[i] frames, the short last one included, all planned on the device in one run; a stream with 0
+        frames makes no call.  run_counts() has max_i ceil(total_frames[i] / chunk_frames) rows: a stream's calls, then
+        (0, 0); counts() every stream's own last call."""
+        n = len(self.resamplers)
+        if len(total_frames) != n:
+            raise ValueError(f"run_bulk_v: {len(total_frames)} lengths for {n} streams")
+        totals = (C.c_size_t * n)(*[int(t) for t in total_frames])
+        _check(lib().rsmp_fir_lockstep_run_bulk_v(self._h, totals, chunk_frames, in_offset_frames, 1 if append else 0,
+                                                  C.c_void_p(stream or 0)))
+        longest = max(totals) if n else 0
+        if longest:   # (all lengths zero: nothing was enqueued, the previous run's counts stay readable)
+            self._last_run = -(-longest // chunk_frames)
 
     def run_counts(self):
         """(consumed, produced) of every call of the last run: two int64 arrays [k_steps][streams], in f32 values."""

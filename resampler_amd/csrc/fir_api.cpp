@@ -1147,20 +1147,41 @@ static int batch_bulk_routed(rsmp_fir* const* rs, size_t n, const float* const* 
                              int* took) {
     *took = 0;
     if (planner == 0 || n < 2) return RSMP_OK;
-    const size_t ch = rs[0]->channels, length = in_lens[0];
+    // A batch whose buffer lengths differ goes through rsmp_fir_lockstep_run_bulk_v -- where the caller asked for the device planner
+    // (planner = 1); the default (planner = -1) keeps its conditions: one buffer length.  `length`: the longest stream's.
+    bool ragged = false;
+    size_t longest = in_lens[0];
+    for (size_t i = 1; i < n; ++i) {
+        ragged = ragged || in_lens[i] != in_lens[0];
+        longest = std::max(longest, in_lens[i]);
+    }
+    if (ragged && planner != 1) return RSMP_OK;
+    const size_t ch = rs[0]->channels, length = ragged ? longest : in_lens[0];
     if (ch == 0 || chunk_len % ch != 0 || length % ch != 0) return RSMP_OK;
     const size_t frames = chunk_len / ch;
     // calls every stream accepts whole (rsmp_fir_lockstep_run_bulk), at least a handful of them, the same buffer length for all
+    // (ragged: at least a handful for the longest stream, whole calls only for every stream)
     if (frames > kRoutedMaxCallFrames || length / ch < kRoutedMinCalls * frames) return RSMP_OK;
     for (size_t i = 0; i < n; ++i) {
-        if (!rs[i] || rs[i]->channels != ch || rs[i]->device != rs[0]->device || in_lens[i] != length) return RSMP_OK;
+        if (!rs[i] || rs[i]->channels != ch || rs[i]->device != rs[0]->device || (!ragged && in_lens[i] != length)) return RSMP_OK;
+        if (ragged) {
+            if (in_lens[i] % chunk_len != 0) return RSMP_OK;
+            // a stream with so many frames buffered that a call could accept less than it is offered (resampler_fir.rs:524-528): the
+            // device planner would flag the run afterwards (kLsStatusPartialAccept) -- the host planner's, before anything is launched
+            if (in_lens[i] != 0 && rs[i]->mirror.state().available + frames > rsmp::kMirrorInputCapacity) return RSMP_OK;
+            if (in_lens[i] == 0) {   // (makes no call: needs no room)
+                for (size_t k = 0; k < i; ++k)
+                    if (rs[k] == rs[i]) return RSMP_OK;
+                continue;
+            }
+        }
         // room for what the launch will produce: the outputs below the limit once `length` more values are accepted, in exact arithmetic
         // (fir_mirror_fast.h: mirror_predict's m1), + 2 for an output that f64 puts a hair below it.  (rsmp_fir_bulk_output_bound is
         // no test here: it grows with the frames a stream has buffered, and a buffer sized by it before the stream's first launch
         // would fail it ever after.)  Anything else: the host path, which checks the room exactly and says so.
         {
             const rsmp::FirMirrorState st = rs[i]->mirror.state();
-            const uint64_t a_now = st.abs_consumed + st.available + length / ch;
+            const uint64_t a_now = st.abs_consumed + st.available + in_lens[i] / ch;
             if (st.num == 0 || st.den == 0 || st.den >= (1ull << 21) || st.num >= (1ull << 21) || a_now >= (1ull << 40)) return RSMP_OK;
             // ceil(x den / num): the outputs m >= 0 with m num / den < x
             const uint64_t m1 = a_now + 1 > st.taps ? ((a_now + 1 - st.taps) * st.den + st.num - 1) / st.num : 0;
@@ -1244,7 +1265,11 @@ static int batch_bulk_routed(rsmp_fir* const* rs, size_t n, const float* const* 
         }
         rb.bound = bound;
     }
-    if (int rc = rsmp_fir_lockstep_run_bulk(rb.ls, length / ch, frames, 0, 0, stream)) return fail_and_drop(rc);
+    if (ragged) {
+        std::vector<size_t> totals(n);
+        for (size_t i = 0; i < n; ++i) totals[i] = in_lens[i] / ch;
+        if (int rc = rsmp_fir_lockstep_run_bulk_v(rb.ls, totals.data(), frames, 0, 0, stream)) return fail_and_drop(rc);
+    } else if (int rc = rsmp_fir_lockstep_run_bulk(rb.ls, length / ch, frames, 0, 0, stream)) return fail_and_drop(rc);
     uint32_t flags = 0;
     std::vector<size_t> acc(n), made(n);
     if (int rc = rsmp_fir_lockstep_sync_totals(rb.ls, acc.data(), made.data(), &flags)) return fail_and_drop(rc);

@@ -168,6 +168,10 @@ struct LsRunArgs {
     uint64_t in_offset;        // frames added to every stream's `in`
     uint32_t n_streams, k, in_frames, wrap_words, append, hist_parity;
     uint32_t parallel_chain;   // K2: chunks of lean calls by the parallel chain (set by launch_fir_lockstep_plan; RSMP_LS_PCHAIN=0, debug: never)
+    // A RAGGED run (rsmp_fir_lockstep_run_bulk_v): frames per stream, internal order; null: every stream makes k calls of in_frames.
+    // Stream i makes totals[i] / in_frames calls of in_frames frames and, where that leaves a remainder, one more of that many;
+    // k is then the batch's largest number of calls (the short one included) and stays the stride of preds / call_recs / counts.
+    const uint32_t* totals;
 };
 struct LsCommitArgs {
     FirMirrorState* states; const FirMirrorState* sp_states;
@@ -230,5 +234,16 @@ hipError_t launch_fir_lockstep_rebase(FirStreamDesc* descs, const LockstepStream
                                       uint32_t n_streams, hipStream_t stream);
 hipError_t launch_fir_lockstep_gather_counts(const uint64_t* last_counts, const LsRunStream* rs, uint32_t* counts, uint32_t n,
                                              hipStream_t stream);
+// A ragged run as a loop of steps (rate pairs no bulk kernel serves).  In front of step `step`: what every stream is offered,
+// clamp(totals[gs] - step * chunk, 0, chunk) frames, into offer[caller index] (rsmp_fir_lockstep_step's d_in_frames), and the
+// counts of the stream's latest call into `keep`; cursor_to_front (the run's first step, no `append`; else null): the append
+// positions of the streams that make a call go back to 0.  Behind the step: the step's counts into the row of the run's table -- or, for a
+// stream that is through (its call was an empty one, which the driver loop never makes), zeros into the row and `keep` back into
+// last_counts.
+hipError_t launch_fir_lockstep_ragged_offer(const uint32_t* totals, const LsRunStream* rs, uint32_t* offer, const uint64_t* last_counts,
+                                            uint64_t* keep, uint64_t* cursor_to_front, uint32_t step, uint32_t chunk, uint32_t n,
+                                            hipStream_t stream);
+hipError_t launch_fir_lockstep_ragged_gather(const uint32_t* totals, const LsRunStream* rs, uint64_t* last_counts, const uint64_t* keep,
+                                             uint32_t* counts, uint32_t step, uint32_t chunk, uint32_t n, hipStream_t stream);
 
 }  // namespace rsmp

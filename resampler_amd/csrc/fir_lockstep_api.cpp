@@ -89,6 +89,16 @@ struct rsmp_fir_lockstep {
     bool run_planned = false;   // the most recent run went through the device planner
     size_t run_counts_k = 0;    // calls of the most recent run whose counts are in slot[last_slot].counts
     std::vector<uint32_t> h_run_counts;
+    // rsmp_fir_lockstep_run_bulk_v: the streams' frame totals (internal order) on the device, uploaded in stream order from a small
+    // ring of pinned staging buffers (the caller's array is free when the call returns; a launch enqueued behind launches that
+    // have not run yet does not wait for them); a loop of steps also keeps what every stream is offered per step and the counts
+    // of its latest real call
+    static constexpr int kTotalsRing = 4;
+    DeviceBuffer d_totals, d_offer, d_keep;
+    rsmp::PinnedBuffer h_totals[kTotalsRing];
+    hipEvent_t totals_ev[kTotalsRing] = {};
+    bool totals_inflight[kTotalsRing] = {};
+    int totals_next = 0;
     // The class tables follow the streams' f64 drift.  The reference's position (src/resampler_fir.rs:589) moves away from
     // the exact rational one by ~1e-14 of a frame per output for as long as a stream runs (every add rounds on the grid of
     // its binade): 1e-6 of a frame after half an hour of audio -- 2e-6 of a full-scale sample with coefficient rows mixed
@@ -674,6 +684,7 @@ static void lockstep_destroy(rsmp_fir_lockstep* ls, bool write_back) {
         rsmp::split_release_stream(ls->device, ls->own_stream);
         (void)hipStreamDestroy(ls->own_stream);
     }
+    for (hipEvent_t e : ls->totals_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ls->prof_start) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ls->prof_stop) if (e) (void)hipEventDestroy(e);
     ls->refresher.reset();   // (joins its thread, frees the images: every kernel that read them has been waited for above)
@@ -1177,10 +1188,24 @@ int prepare_run(rsmp_fir_lockstep* ls) {
     return RSMP_OK;
 }
 
+// k_steps calls of in_frames frames per stream -- or, d_totals != null (rsmp_fir_lockstep_run_bulk_v), a RAGGED run: d_totals[gs]
+// frames for stream gs (device array, internal order, in place on `stream`) in calls of in_frames frames, the last one shorter;
+// k_steps is then the largest number of calls a stream makes.
+int lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size_t in_frames, size_t in_offset_frames, int append, void* stream,
+                 const uint32_t* d_totals);
+
 }  // namespace
 
 extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size_t in_frames, size_t in_offset_frames,
                                      int append, void* stream) {
+    return lockstep_run(ls, k_steps, in_frames, in_offset_frames, append, stream, nullptr);
+}
+
+namespace {
+
+int lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size_t in_frames, size_t in_offset_frames, int append, void* stream,
+                 const uint32_t* d_totals) {
+    const bool ragged = d_totals != nullptr;
     if (!ls || !ls->bound)
         return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_run: bind buffers first");
     if (k_steps == 0) return RSMP_OK;
@@ -1233,15 +1258,28 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
         if (ls->last_stream && ls->last_stream != s) RSMP_HIP_CHECK(hipStreamSynchronize(ls->last_stream));   // (in front of the memset below)
         if (int rc = drop_plan_ahead(ls, s)) return rc;
         ls->prev.valid = false;
-        if (!append)   // (the device planner starts a run at the front itself: no launch for it)
+        if (!append && !ragged)   // (the device planner starts a run at the front itself: no launch for it; ragged: the first step's offer kernel)
             RSMP_HIP_CHECK(hipMemsetAsync(ls->d_cursor.get(), 0, n * sizeof(uint64_t), s));
         const int sl = ls->next_slot;
         for (uint32_t i = 0; i < k; ++i) {
-            if (int rc = rsmp_fir_lockstep_step(ls, in_frames, in_offset_frames + static_cast<size_t>(i) * in_frames, nullptr, 1, stream))
-                return rc;
-            RSMP_HIP_CHECK(rsmp::launch_fir_lockstep_gather_counts(ls->d_counts.as<uint64_t>(), ls->d_run_rs.as<rsmp::LsRunStream>(),
-                                                                   ls->slot[sl].counts.as<uint32_t>() + 2 * n * static_cast<size_t>(i),
-                                                                   static_cast<uint32_t>(n), s));
+            const size_t offset = in_offset_frames + static_cast<size_t>(i) * in_frames;
+            uint32_t* row = ls->slot[sl].counts.as<uint32_t>() + 2 * n * static_cast<size_t>(i);
+            const rsmp::LsRunStream* rs = ls->d_run_rs.as<rsmp::LsRunStream>();
+            const uint32_t nn = static_cast<uint32_t>(n), chunk = static_cast<uint32_t>(in_frames);
+            if (ragged) {
+                // step i offers every stream what is left of its buffer, at most in_frames frames.  A stream that is through takes an
+                // EMPTY call, which the driver loop never makes: state-neutral behind a call that was not stopped by its output room
+                // (src/resampler_fir.rs:542-602: the loop breaks at once, nothing is retired), and kept out of the stream's counts.
+                RSMP_HIP_CHECK(rsmp::launch_fir_lockstep_ragged_offer(d_totals, rs, ls->d_offer.as<uint32_t>(), ls->d_counts.as<uint64_t>(),
+                                                                      ls->d_keep.as<uint64_t>(),
+                                                                      i == 0 && !append ? ls->d_cursor.as<uint64_t>() : nullptr, i, chunk, nn, s));
+                if (int rc = rsmp_fir_lockstep_step(ls, in_frames, offset, ls->d_offer.as<uint32_t>(), 1, stream)) return rc;
+                RSMP_HIP_CHECK(rsmp::launch_fir_lockstep_ragged_gather(d_totals, rs, ls->d_counts.as<uint64_t>(), ls->d_keep.as<uint64_t>(), row, i,
+                                                                       chunk, nn, s));
+            } else {
+                if (int rc = rsmp_fir_lockstep_step(ls, in_frames, offset, nullptr, 1, stream)) return rc;
+                RSMP_HIP_CHECK(rsmp::launch_fir_lockstep_gather_counts(ls->d_counts.as<uint64_t>(), rs, row, nn, s));
+            }
         }
         ls->last_slot = sl;
         ls->run_counts_k = k;
@@ -1294,6 +1332,7 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
         a.wrap_words = ls->run_wrap_words;
         a.append = kk.append;
         a.hist_parity = kk.parity;
+        a.totals = scratch ? nullptr : d_totals;   // (a ragged run is planned here and now; what is planned ahead is a uniform run)
         return a;
     };
     if (ls->profiling)
@@ -1302,7 +1341,7 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
     bool plan_taken_over = false;
     bool commit_pending = false;   // ... are still to be committed on the caller's stream: by K1 of the next run, or a launch of its own
     rsmp::LsCommitArgs c{};
-    if (same_key(ls->ahead, key)) {
+    if (!ragged && same_key(ls->ahead, key)) {
         // planned while the previous run computed: wait for it (an event, no host block) and take its results over
         // (a big batch's caller stream has waited already, behind the previous run's split launch -- see below)
         if (!(ls->ahead_waited && ls->ahead_waited_on == s)) RSMP_HIP_CHECK(rsmp::stream_wait_event(s, ls->plan_done));
@@ -1372,7 +1411,7 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
     // streams the same -- the stagers of the split kernel and the chain compete for the same issue slots, and each is slowed
     // by what the other takes.  RSMP_LS_AHEAD=0 (debug): every run plans on the caller's stream.
     static const bool ahead_on = [] { const char* e = rsmp::knob("RSMP_LS_AHEAD"); return !e || atoi(e) != 0; }();
-    bool repeat = ahead_on && ls->prev.valid && ls->prev.k == key.k && ls->prev.in_frames == key.in_frames && ls->prev.append == key.append;
+    bool repeat = !ragged && ahead_on && ls->prev.valid && ls->prev.k == key.k && ls->prev.in_frames == key.in_frames && ls->prev.append == key.append;
     if (repeat) {
         if (int rc = pick_plan_stream(ls, s)) return rc;
         repeat = ls->plan_stream != nullptr;
@@ -1551,8 +1590,11 @@ extern "C" int rsmp_fir_lockstep_run(rsmp_fir_lockstep* ls, size_t k_steps, size
     ls->last_slot = sl;
     ls->next_slot = sl ^ 1;
     ls->prev = key;
+    if (ragged) ls->prev.valid = false;   // (nothing is guessed from a ragged run, and nothing planned ahead survives one)
     return request_drift(ls, s, static_cast<uint64_t>(k) * in_frames);
 }
+
+}  // namespace
 
 extern "C" int rsmp_fir_lockstep_run_counts(rsmp_fir_lockstep* ls, size_t* consumed, size_t* produced, size_t max_steps) {
     if (!ls) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_run_counts: null batch");
@@ -1639,4 +1681,53 @@ extern "C" int rsmp_fir_lockstep_run_bulk(rsmp_fir_lockstep* ls, size_t total_fr
         if (k > 0) ls->run_counts_k = run_k;   // (the run's counts stay readable: the last call's are rsmp_fir_lockstep_counts')
     }
     return RSMP_OK;
+}
+
+// rsmp_fir_lockstep_run_bulk with a buffer length per stream: every stream makes the calls the driver loop makes for ITS buffer
+// (resample/src/main.rs:226-254), all of them -- the short last one included -- planned on the device in one run
+// (fir_lockstep_run.hip: the RAGGED instantiations of the planner's kernels), the bulk kernels launched once over descriptors
+// whose lengths differ from stream to stream as they always have.
+extern "C" int rsmp_fir_lockstep_run_bulk_v(rsmp_fir_lockstep* ls, const size_t* total_frames, size_t chunk_frames, size_t in_offset_frames,
+                                            int append, void* stream) {
+    if (!ls || !total_frames || chunk_frames == 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_run_bulk_v: null batch, null lengths or zero chunk");
+    if (chunk_frames > ls->step_frames)
+        return rsmp::fail(RSMP_ERR_INVALID_INPUT_BUFFER_SIZE, "lock-step batch: calls of %zu frames, created for %u per step", chunk_frames,
+                          ls->step_frames);
+    size_t max_taps = 0;   // (calls every stream accepts whole: rsmp_fir_lockstep_run_bulk)
+    for (const rsmp_fir* r : ls->rs) max_taps = std::max<size_t>(max_taps, r->taps);
+    if (chunk_frames + max_taps + 8 > rsmp::kMirrorInputCapacity)
+        return rsmp::fail(RSMP_ERR_INVALID_INPUT_BUFFER_SIZE,
+                          "rsmp_fir_lockstep_run_bulk_v: calls of %zu frames are not accepted whole by a stream of %zu taps (at most %zu)", chunk_frames,
+                          max_taps, static_cast<size_t>(rsmp::kMirrorInputCapacity) - max_taps - 8);
+    if (!ls->bound) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_run_bulk_v: bind buffers first");
+    const size_t n = ls->rs.size();
+    size_t longest = 0;
+    for (size_t i = 0; i < n; ++i) longest = std::max(longest, total_frames[i]);
+    if (longest == 0) return RSMP_OK;
+    if (longest > (1u << 27)) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_lockstep_run_bulk_v: at most 2^27 frames per stream and run");
+    const size_t k = (longest + chunk_frames - 1) / chunk_frames;   // rows of the run's tables: the longest stream's calls
+    DeviceGuard guard(ls->device);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ls->own_stream;
+    if (ls->last_stream && ls->last_stream != s) RSMP_HIP_CHECK(hipStreamSynchronize(ls->last_stream));   // (in front of the upload below)
+    if (int rc = prepare_run(ls)) return rc;
+    if (ls->d_totals.capacity() < n * sizeof(uint32_t) || !ls->totals_ev[rsmp_fir_lockstep::kTotalsRing - 1]) {   // (the batch's first ragged run)
+        if (ls->d_totals.reserve(n * sizeof(uint32_t)) != hipSuccess || ls->d_offer.reserve(n * sizeof(uint32_t)) != hipSuccess ||
+            ls->d_keep.reserve(2 * n * sizeof(uint64_t)) != hipSuccess)
+            return rsmp::fail(RSMP_ERR_HIP, "rsmp_fir_lockstep_run_bulk_v: cannot allocate device state");
+        for (int j = 0; j < rsmp_fir_lockstep::kTotalsRing; ++j)
+            if (ls->h_totals[j].reserve(n * sizeof(uint32_t)) != hipSuccess ||
+                (!ls->totals_ev[j] && hipEventCreateWithFlags(&ls->totals_ev[j], hipEventDisableTiming) != hipSuccess))
+                return rsmp::fail(RSMP_ERR_HIP, "rsmp_fir_lockstep_run_bulk_v: cannot allocate staging memory");
+    }
+    const int j = ls->totals_next;
+    ls->totals_next = (j + 1) % rsmp_fir_lockstep::kTotalsRing;
+    if (ls->totals_inflight[j]) RSMP_HIP_CHECK(hipEventSynchronize(ls->totals_ev[j]));   // (the upload four ragged runs ago)
+    uint32_t* h = ls->h_totals[j].as<uint32_t>();
+    for (size_t gs = 0; gs < n; ++gs) h[gs] = static_cast<uint32_t>(total_frames[ls->order[gs]]);
+    RSMP_HIP_CHECK(hipMemcpyAsync(ls->d_totals.get(), h, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    RSMP_HIP_CHECK(rsmp::event_record(ls->totals_ev[j], s));
+    ls->totals_inflight[j] = true;
+    ls->last_stream = s;
+    return lockstep_run(ls, k, chunk_frames, in_offset_frames, append, stream, ls->d_totals.as<uint32_t>());
 }

@@ -53,6 +53,21 @@ static_assert(sizeof(CallRec) == 24, "CallRec layout");
 // K1 -- the structure of every call of the run, in exact integer arithmetic: one thread per (stream, call), a workgroup
 // per stream and 256 calls; its first threads make the stream's binade-edge constants (MirrorEdges: thirteen divisions,
 // once per workgroup instead of once per call).
+// (RAGGED, here and in K2 / K3: the instantiations of a run with a buffer length per stream, LsRunArgs::totals.  Builds of their own,
+// so that the uniform run's kernels stay the instructions they are: K2 is bound by instruction fetch.  A stream's EQUAL calls are
+// what the closed form is about: run_equal_calls; a short last call is made by the plain state machine behind them, K2.)
+template <bool RAGGED>
+__device__ __forceinline__ uint32_t run_equal_calls(const LsRunArgs& a, uint32_t gs) {
+    if constexpr (RAGGED) return a.totals[gs] / a.in_frames;
+    else return a.k;
+}
+template <bool RAGGED>
+__device__ __forceinline__ uint32_t run_tail_frames(const LsRunArgs& a, uint32_t gs) {
+    if constexpr (RAGGED) return a.totals[gs] % a.in_frames;
+    else return 0u;
+}
+
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void fir_lockstep_predict_kernel(LsRunArgs a, uint32_t blocks_per_stream, LsCommitArgs cm) {
     __shared__ MirrorEdges edges;
     const uint32_t gs = blockIdx.x / blocks_per_stream;
@@ -60,11 +75,14 @@ __global__ __launch_bounds__(256) void fir_lockstep_predict_kernel(LsRunArgs a, 
     // (cm.n_streams != 0: the states before this run are still in the scratch copies of the run planned before it; they are read
     // from there, and the stream's first thread puts them -- and what else that plan left -- in place for the kernels behind)
     const FirMirrorState* const states_now = cm.n_streams ? cm.sp_states : a.states_in;
-    const MirrorRunBase base = mirror_run_base(states_now[gs], a.in_frames, a.k);
+    const uint32_t k_eq = run_equal_calls<RAGGED>(a, gs);
+    const MirrorRunBase base = mirror_run_base(states_now[gs], a.in_frames, k_eq);
     if (base.usable && threadIdx.x <= kPredBinades) mirror_edge(base, threadIdx.x, edges.q[threadIdx.x], edges.r[threadIdx.x]);
     __syncthreads();
     if (c >= a.k) return;
-    if (base.usable) a.preds[static_cast<size_t>(gs) * a.k + c] = mirror_predict_edges(base, edges, c);
+    // (ragged: predictions for the stream's own equal calls only -- but every one of the a.k threads goes on: the stream's first
+    // thread copies the state also of a stream without a call, and the loop below zeroes the bitmap with a stride of a.k)
+    if (base.usable && (!RAGGED || c < k_eq)) a.preds[static_cast<size_t>(gs) * a.k + c] = mirror_predict_edges(base, edges, c);
     if (c == 0) {
         if (cm.n_streams) {
             cm.states[gs] = cm.sp_states[gs];
@@ -262,7 +280,9 @@ __device__ inline uint32_t chain_eval_lane(uint32_t shape, double& pos, uint32_t
 // 128-stream shard take 0.72 or 0.91 us per step, profiles/r06/ab_c4_shard.txt.)
 // (PCHAIN: the build with the parallel chain and without round 5's run of equal-shape calls -- chain_fast_run, twelve instantiations --
 // and the other way round for RSMP_LS_PCHAIN=0: a wave of this kernel is bound by instruction fetch, and neither build needs both)
-template <bool PCHAIN>
+// (RAGGED: the chunk loop walks the stream's own equal calls, `kc` of them -- wave-uniform, in a scalar register --; a short last call
+// follows behind the loop by the plain state machine, and the rows of the run's tables the stream has no call for are zeroed.)
+template <bool PCHAIN, bool RAGGED>
 __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(LsRunArgs a) {
     const uint32_t gs = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (gs >= a.n_streams) return;
@@ -270,7 +290,16 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
     const LsRunStream rs = a.rs[gs];
     FirMirrorState st = a.states_in[gs];
     uint32_t* bits = a.wrap_bits + static_cast<size_t>(gs) * a.wrap_words;
-    const MirrorRunBase base = mirror_run_base(st, a.in_frames, a.k);
+    uint32_t kc_own = 0, tail = 0;   // ragged: the stream's equal calls, the frames of its short last call
+    if constexpr (RAGGED) {
+        kc_own = rfl(run_equal_calls<RAGGED>(a, gs));
+        tail = rfl(run_tail_frames<RAGGED>(a, gs));
+    }
+    auto kc = [&]() -> uint32_t {   // the calls the chunk loop walks
+        if constexpr (RAGGED) return kc_own;
+        else return a.k;
+    };
+    const MirrorRunBase base = mirror_run_base(st, a.in_frames, kc());
     const MirrorBinades bn = mirror_binades(st.ratio, base.e0);
     const bool chain_ready = base.usable && mirror_chain_ready(bn);
 
@@ -297,21 +326,28 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
     const uint32_t out_cap = rfl(static_cast<uint32_t>(ls.out_cap_frames < 0xFFFFFFFFull ? ls.out_cap_frames : 0xFFFFFFFFull));
     uint64_t mine[7], ahead[7], succ[2], succ_ahead[2];
     auto fetch = [&](uint32_t c0, uint64_t (&v)[7], uint64_t (&sv)[2]) {
-        const uint32_t c = c0 + lane < a.k ? c0 + lane : a.k - 1;
-        const uint32_t cn = c + 1 < a.k ? c + 1 : a.k - 1;
+        uint32_t kk;   // (= kc(); read here, not through the lambda: the uniform build keeps its schedule only so -- tools/planner_isa.py checks)
+        if constexpr (RAGGED) kk = kc_own;
+        else kk = a.k;
+        const uint32_t c = c0 + lane < kk ? c0 + lane : kk - 1;
+        const uint32_t cn = c + 1 < kk ? c + 1 : kk - 1;
 #pragma unroll
         for (int i = 0; i < 7; ++i) v[i] = __builtin_nontemporal_load(preds + static_cast<size_t>(c) * 7 + i);
         sv[0] = __builtin_nontemporal_load(preds + static_cast<size_t>(cn) * 7);       // the next call's m0, c0
         sv[1] = __builtin_nontemporal_load(preds + static_cast<size_t>(cn) * 7 + 1);
     };
-    fetch(0, ahead, succ_ahead);
-    for (uint32_t c0 = 0; c0 < a.k; c0 += 64) {
-        const uint32_t nc = a.k - c0 < 64u ? a.k - c0 : 64u;
+    if constexpr (RAGGED) {
+        if (kc() != 0) fetch(0, ahead, succ_ahead);
+    } else {
+        fetch(0, ahead, succ_ahead);
+    }
+    for (uint32_t c0 = 0; c0 < kc(); c0 += 64) {
+        const uint32_t nc = kc() - c0 < 64u ? kc() - c0 : 64u;
 #pragma unroll
         for (int i = 0; i < 7; ++i) mine[i] = ahead[i];
         succ[0] = succ_ahead[0];
         succ[1] = succ_ahead[1];
-        if (c0 + 64 < a.k) fetch(c0 + 64, ahead, succ_ahead);
+        if (c0 + 64 < kc()) fetch(c0 + 64, ahead, succ_ahead);
         // ---- the lanes' part: which of these 64 calls may take the unchecked chain, and which continue their predecessor
         const uint32_t my_call = c0 + lane;
         const uint32_t my_n_total = static_cast<uint32_t>(mine[2]);
@@ -321,7 +357,7 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
         // frames buffered when call j starts, IF the stream is on the prediction's track there: accepted - retired
         const uint64_t my_avail = frames0 + static_cast<uint64_t>(my_call) * a.in_frames - mine[1];
         const bool my_struct_ok = lane < nc && (my_cp.ctl & kChainLean) && my_n_total + 1 < out_cap && my_avail + a.in_frames <= kMirrorInputCapacity;
-        const bool my_last = my_call + 1 >= a.k;
+        const bool my_last = my_call + 1 >= kc();
         const bool my_succ_ok = my_last || succ[0] == mine[0] + my_n_total;
         const uint32_t my_cpred = static_cast<uint32_t>(succ[1] - mine[1]);   // frames the prediction has the call retire
         const uint64_t lean_mask = __ballot(my_struct_ok && chain_ready);
@@ -599,6 +635,34 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
         st.available = sc.available;
         st.next_int = lean_ni_after;
     }
+    bool any_call = true;
+    if constexpr (RAGGED) {
+        const uint32_t calls = kc_own + (tail ? 1u : 0u);   // the stream's calls; its rows of the run's tables are [0, calls)
+        any_call = calls != 0;
+        if (tail) {   // the short last call (resample/src/main.rs:226-254): no "equal call" of the closed form -- the plain state machine
+            const double pos0 = st.position;
+            const uint32_t ni = st.next_int;
+            sink.rel = static_cast<uint32_t>(st.abs_out - k0 * rs.wrap_unit);
+            sink.periodic = wraps_exist && st.periodic_ok != 0;
+            const FirCallCounts c = mirror_call(st, tail, ls.out_cap_frames, sink);
+            if (c.accepted != tail) flags |= kLsStatusPartialAccept;
+            last_c0 = static_cast<uint32_t>(c.accepted) * C;
+            last_c1 = static_cast<uint32_t>(c.produced) * C;
+            last_lean = false;
+            if (lane == 0) {
+                recs[kc_own] = CallRec{pos0, st.drift, kCallSlow | (ni < c.produced ? kCallHasInt : 0u), 0u};
+                uint32_t* counts = a.counts + 2 * (static_cast<size_t>(kc_own) * a.n_streams + rs.caller);
+                counts[0] = last_c0;
+                counts[1] = last_c1;
+            }
+        }
+        for (uint32_t r = calls + lane; r < a.k; r += 64) {   // (nobody else clears these buffers)
+            recs[r] = CallRec{0.0, 0.0, 0u, 0u};
+            uint32_t* counts = a.counts + 2 * (static_cast<size_t>(r) * a.n_streams + rs.caller);
+            counts[0] = 0;
+            counts[1] = 0;
+        }
+    }
     if (lane != 0) return;
     if (sink.overflow) flags |= kLsStatusRunOverflow;
     // the run's totals, from the counters it ends with: outputs, frames retired, frames accepted (= retired + what the
@@ -613,7 +677,12 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
 
     // the calls' outputs follow each other: behind what was appended before, or (no `append`) from the front of `out`
     const uint64_t cursor = a.append ? a.cursor_in[gs] : 0;
-    a.cursor_out[gs] = cursor + static_cast<uint64_t>(n_out) * C;
+    // (ragged: a stream without a call keeps its append position and its last call's counts)
+    if constexpr (RAGGED) {
+        if (any_call) a.cursor_out[gs] = cursor + static_cast<uint64_t>(n_out) * C;
+    } else {
+        a.cursor_out[gs] = cursor + static_cast<uint64_t>(n_out) * C;
+    }
     FirStreamDesc* d = a.descs + gs;
     d->in = ls.in + a.in_offset * C;
     d->hist = a.hist_parity ? ls.hist_alt : ls.hist;
@@ -630,8 +699,15 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
     d->wrap_k0 = k0;
     a.states_out[gs] = st;
     // the last call's counts, where rsmp_fir_lockstep_counts looks for them
-    a.last_counts[2 * gs] = last_c0;
-    a.last_counts[2 * gs + 1] = last_c1;
+    if constexpr (RAGGED) {
+        if (any_call) {
+            a.last_counts[2 * gs] = last_c0;
+            a.last_counts[2 * gs + 1] = last_c1;
+        }
+    } else {
+        a.last_counts[2 * gs] = last_c0;
+        a.last_counts[2 * gs + 1] = last_c1;
+    }
     if (flags) a.status[gs] |= flags;
 }
 
@@ -644,6 +720,7 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
 // settle the stream's drift -- that of the LAST call with an output at an integer position -- through LDS: 32 -> ~10 us
 // per run at 128 streams x 256 calls.)
 constexpr uint32_t kLsWrapWaves = 16;   // (at most: a run of 256 calls has four chunks, a bulk launch of 4096 calls sixty-four)
+template <bool RAGGED>
 __global__ __launch_bounds__(64 * kLsWrapWaves) void fir_lockstep_wraps_kernel(LsRunArgs a) {
     __shared__ double s_drift[kLsWrapWaves];
     __shared__ uint32_t s_chunk[kLsWrapWaves], s_flags[kLsWrapWaves];
@@ -651,7 +728,14 @@ __global__ __launch_bounds__(64 * kLsWrapWaves) void fir_lockstep_wraps_kernel(L
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = blockDim.x >> 6;
     const LsRunStream rs = a.rs[gs];
     const FirMirrorState st0 = a.states_before[gs];   // the state before the run
-    const MirrorRunBase base = mirror_run_base(st0, a.in_frames, a.k);
+    // (ragged: the stream's own calls -- the short last one, a record of the chain's slow path, among them)
+    uint32_t calls_own = 0;
+    if constexpr (RAGGED) calls_own = run_equal_calls<RAGGED>(a, gs) + (run_tail_frames<RAGGED>(a, gs) ? 1u : 0u);
+    auto calls = [&]() -> uint32_t {
+        if constexpr (RAGGED) return calls_own;
+        else return a.k;
+    };
+    const MirrorRunBase base = mirror_run_base(st0, a.in_frames, run_equal_calls<RAGGED>(a, gs));
     const MirrorBinades bn = mirror_binades(st0.ratio, base.e0);
     const bool wraps_exist = rs.wrap_unit == rs.den && st0.periodic_ok != 0;
     uint32_t* bits = a.wrap_bits + static_cast<size_t>(gs) * a.wrap_words;
@@ -661,11 +745,11 @@ __global__ __launch_bounds__(64 * kLsWrapWaves) void fir_lockstep_wraps_kernel(L
     double drift = st0.drift;
     uint32_t have_chunk = 0;   // 1 + the index of this wave's last chunk with an output at an integer position
     bool aperiodic = false, overflow = false, unchecked = false;
-    for (uint32_t c0 = 64u * wave, chunk = wave; c0 < a.k; c0 += 64u * n_waves, chunk += n_waves) {
+    for (uint32_t c0 = 64u * wave, chunk = wave; c0 < calls(); c0 += 64u * n_waves, chunk += n_waves) {
         const uint32_t c = c0 + lane;
         bool has_int = false;
         double my_drift = 0.0;
-        if (c < a.k) {
+        if (c < calls()) {
             const CallRec rec = recs[c];
             if (rec.flags & kCallSlow) {
                 has_int = (rec.flags & kCallHasInt) != 0;
@@ -741,6 +825,34 @@ __global__ __launch_bounds__(256) void fir_lockstep_gather_counts_kernel(const u
     const uint32_t i = rs[gs].caller;
     counts[2 * i] = static_cast<uint32_t>(last_counts[2 * gs]);
     counts[2 * i + 1] = static_cast<uint32_t>(last_counts[2 * gs + 1]);
+}
+
+// (fir_lockstep.h: launch_fir_lockstep_ragged_offer / _gather)
+__global__ __launch_bounds__(256) void fir_lockstep_ragged_offer_kernel(const uint32_t* totals, const LsRunStream* rs, uint32_t* offer,
+                                                                       const uint64_t* last_counts, uint64_t* keep, uint64_t* cursor_to_front,
+                                                                       uint32_t step, uint32_t chunk, uint32_t n) {
+    const uint32_t gs = blockIdx.x * 256u + threadIdx.x;
+    if (gs >= n) return;
+    if (cursor_to_front && totals[gs] != 0) cursor_to_front[gs] = 0;   // (a stream without a call keeps its append position, as in K2)
+    const uint64_t done = static_cast<uint64_t>(step) * chunk;
+    const uint64_t left = totals[gs] > done ? totals[gs] - done : 0;
+    offer[rs[gs].caller] = static_cast<uint32_t>(left < chunk ? left : chunk);
+    keep[2 * gs] = last_counts[2 * gs];
+    keep[2 * gs + 1] = last_counts[2 * gs + 1];
+}
+__global__ __launch_bounds__(256) void fir_lockstep_ragged_gather_kernel(const uint32_t* totals, const LsRunStream* rs, uint64_t* last_counts,
+                                                                        const uint64_t* keep, uint32_t* counts, uint32_t step, uint32_t chunk,
+                                                                        uint32_t n) {
+    const uint32_t gs = blockIdx.x * 256u + threadIdx.x;
+    if (gs >= n) return;
+    const uint32_t i = rs[gs].caller;
+    const bool called = totals[gs] > static_cast<uint64_t>(step) * chunk;
+    if (!called) {   // (an empty call: not one of the stream's)
+        last_counts[2 * gs] = keep[2 * gs];
+        last_counts[2 * gs + 1] = keep[2 * gs + 1];
+    }
+    counts[2 * i] = called ? static_cast<uint32_t>(last_counts[2 * gs]) : 0u;
+    counts[2 * i + 1] = called ? static_cast<uint32_t>(last_counts[2 * gs + 1]) : 0u;
 }
 
 __global__ __launch_bounds__(256) void fir_lockstep_commit_kernel(LsCommitArgs a) {
@@ -846,6 +958,20 @@ hipError_t launch_fir_lockstep_gather_counts(const uint64_t* last_counts, const 
     return hipGetLastError();
 }
 
+hipError_t launch_fir_lockstep_ragged_offer(const uint32_t* totals, const LsRunStream* rs, uint32_t* offer, const uint64_t* last_counts,
+                                            uint64_t* keep, uint64_t* cursor_to_front, uint32_t step, uint32_t chunk, uint32_t n,
+                                            hipStream_t stream) {
+    hipLaunchKernelGGL(fir_lockstep_ragged_offer_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, totals, rs, offer, last_counts, keep,
+                       cursor_to_front, step, chunk, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_fir_lockstep_ragged_gather(const uint32_t* totals, const LsRunStream* rs, uint64_t* last_counts, const uint64_t* keep,
+                                             uint32_t* counts, uint32_t step, uint32_t chunk, uint32_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(fir_lockstep_ragged_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, totals, rs, last_counts, keep, counts, step, chunk, n);
+    return hipGetLastError();
+}
+
 uint32_t lockstep_plan_pack(size_t n_streams) {
     static const uint32_t knob = [] { const char* e = rsmp::knob("RSMP_LS_PACK"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 ? static_cast<uint32_t>(v) : 0u; }();
     if (n_streams >= kLsPlanPackBelow) return 1u;
@@ -863,24 +989,33 @@ hipError_t launch_fir_lockstep_plan(const LsRunArgs& args_in, hipStream_t stream
     static const bool pchain = [] { const char* e = rsmp::knob("RSMP_LS_PCHAIN"); return !e || atoi(e) != 0; }();
     LsRunArgs args = args_in;
     args.parallel_chain = pchain ? 1u : 0u;
+    // (a ragged run is never planned ahead: no commit to fuse, no event for K1 to complete)
+    const bool ragged = args.totals != nullptr;
+    if (ragged && (commit || k1_done || parts != 3)) return hipErrorInvalidValue;
     const uint32_t blocks_per_stream = (args.k + 255) / 256;
     if (parts & 1) {
         LsCommitArgs cm{};
         if (commit) cm = *commit;
         if (k1_done)
-            hipExtLaunchKernelGGL(fir_lockstep_predict_kernel, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, nullptr, k1_done, 0, args,
+            hipExtLaunchKernelGGL(fir_lockstep_predict_kernel<false>, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, nullptr, k1_done, 0, args,
                                   blocks_per_stream, cm);
+        else if (ragged)
+            hipLaunchKernelGGL(fir_lockstep_predict_kernel<true>, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, args, blocks_per_stream, cm);
         else
-            hipLaunchKernelGGL(fir_lockstep_predict_kernel, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, args, blocks_per_stream, cm);
+            hipLaunchKernelGGL(fir_lockstep_predict_kernel<false>, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, args, blocks_per_stream, cm);
     }
     if (parts & 2) {
         const uint32_t pack = lockstep_plan_pack(args.n_streams);
-        if (pchain) hipLaunchKernelGGL(fir_lockstep_chain_kernel<true>, dim3((args.n_streams + pack - 1) / pack), dim3(64 * pack), 0, stream, args);
-        else hipLaunchKernelGGL(fir_lockstep_chain_kernel<false>, dim3((args.n_streams + pack - 1) / pack), dim3(64 * pack), 0, stream, args);
+        const dim3 chain_grid((args.n_streams + pack - 1) / pack), chain_block(64 * pack);
+        if (ragged && pchain) hipLaunchKernelGGL((fir_lockstep_chain_kernel<true, true>), chain_grid, chain_block, 0, stream, args);
+        else if (ragged) hipLaunchKernelGGL((fir_lockstep_chain_kernel<false, true>), chain_grid, chain_block, 0, stream, args);
+        else if (pchain) hipLaunchKernelGGL((fir_lockstep_chain_kernel<true, false>), chain_grid, chain_block, 0, stream, args);
+        else hipLaunchKernelGGL((fir_lockstep_chain_kernel<false, false>), chain_grid, chain_block, 0, stream, args);
         // (the replay: a wave per chunk of 64 calls for small batches, one wave per stream otherwise)
         const uint32_t chunks = (args.k + 63) / 64;
         const uint32_t wwaves = pack > 1 ? std::min<uint32_t>(kLsWrapWaves, chunks) : 1u;
-        hipLaunchKernelGGL(fir_lockstep_wraps_kernel, dim3(args.n_streams), dim3(64 * wwaves), 0, stream, args);
+        if (ragged) hipLaunchKernelGGL(fir_lockstep_wraps_kernel<true>, dim3(args.n_streams), dim3(64 * wwaves), 0, stream, args);
+        else hipLaunchKernelGGL(fir_lockstep_wraps_kernel<false>, dim3(args.n_streams), dim3(64 * wwaves), 0, stream, args);
     }
     return hipGetLastError();
 }
