@@ -74,6 +74,36 @@ private:
     size_t cap_ = 0;
 };
 
+// Owners of one hipEvent_t / hipStream_t: created once (a second create() keeps what is there), destroyed with the holder or
+// by reset().  Neither ever WAITS: whoever must wait for what was recorded or enqueued does so before the holder goes.
+class EventHolder {
+public:
+    EventHolder() = default;
+    EventHolder(const EventHolder&) = delete;
+    EventHolder& operator=(const EventHolder&) = delete;
+    ~EventHolder() { reset(); }
+    hipError_t create(unsigned flags = hipEventDefault) { return ev_ ? hipSuccess : hipEventCreateWithFlags(&ev_, flags); }
+    void reset() { if (ev_) (void)hipEventDestroy(ev_); ev_ = nullptr; }
+    operator hipEvent_t() const { return ev_; }
+
+private:
+    hipEvent_t ev_ = nullptr;
+};
+
+class StreamHolder {
+public:
+    StreamHolder() = default;
+    StreamHolder(const StreamHolder&) = delete;
+    StreamHolder& operator=(const StreamHolder&) = delete;
+    ~StreamHolder() { reset(); }
+    hipError_t create(unsigned flags = hipStreamDefault) { return s_ ? hipSuccess : hipStreamCreateWithFlags(&s_, flags); }
+    void reset() { if (s_) (void)hipStreamDestroy(s_); s_ = nullptr; }
+    operator hipStream_t() const { return s_; }
+
+private:
+    hipStream_t s_ = nullptr;
+};
+
 // Restores the caller's current device on scope exit.
 class DeviceGuard {
 public:

@@ -1,6 +1,6 @@
 // fir_table_refresher.h -- replacement class tables for a lock-step batch, prepared OFF the launch path.
 //
-// The class tables of a lock-step batch follow the streams' f64 drift (fir_lockstep_api.cpp, DriftClass; the
+// The class tables of a lock-step batch follow the streams' f64 drift (fir_lockstep_batch.h, DriftClass; the
 // reference's `position += ratio`, src/resampler_fir.rs:589, leaves the exact rational position by ~1e-14 of a frame
 // per output).  A replacement used to be made inside rsmp_fir_lockstep_run / _step: a process-wide mutex, a host build
 // when the image was not ready, hipMalloc and three synchronous hipMemcpy -- each of which waits for the kernels in

@@ -295,7 +295,7 @@ def test_a_big_batch_runs_in_a_row(own_stream):
     """Config 4's path proper: from 256 streams on, K1 of the next run goes in FRONT of a run's bulk kernels on the caller's
     stream and commits the run planned ahead on its way, the caller's stream waits for the planner behind the split launch,
     the item tables come from the plan stream, and -- on a stream of the caller's own -- the launches complete the events
-    themselves (fir_lockstep_api.cpp, round 6).  264 streams, runs of 8 calls over the same span again and again, a step in
+    themselves (fir_lockstep_runpath.cpp, round 6).  264 streams, runs of 8 calls over the same span again and again, a step in
     between (the plan made ahead is dropped, its commit still due): counts, samples, states."""
     import torch
     dev = torch.device("cuda:0")
