@@ -1,0 +1,243 @@
+"""A plain f64 reference of the two resamplers, in numpy.  TEST INFRASTRUCTURE ONLY, like the rest of oracle/.
+
+The CPU oracle (oracle/*.c) restates the reference in its own f32 arithmetic and so carries the reference's rounding
+error; a kernel held to "1e-6 RMS of the oracle" may be several times farther from the true sum than the reference is.
+This module evaluates the SAME operation -- the reference's f32 operands (coefficient table, samples, `frac`), the
+reference's control flow -- with every sum in f64, and `budget` expresses a distance from it in multiples of the
+reference's own (the scalar spec's) distance.
+
+Written from the algorithm (src/resampler_fir.rs:509-621, src/resampler_fft.rs:385-424): pyoracle supplies only the
+f32 TABLES (make_sincs_for_kaiser, calculate_cutoff_kaiser, fft_plan); no control flow and no sum goes through it.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+PHASES = 1024           # resampler_fir.rs:17
+INPUT_CAPACITY = 4096   # resampler_fir.rs:18
+BUFFER_SIZE = 8192      # resampler_fir.rs:19
+
+
+# ---- FIR: control flow --------------------------------------------------------------------------------------------
+@dataclass
+class FirPositions:
+    """What a sequence of resample() calls evaluates, output frame by output frame."""
+    index: np.ndarray     # int64: absolute input frame of the window's first tap (frames accepted so far count from 0)
+    phase1: np.ndarray    # int64
+    phase2: np.ndarray    # int64
+    frac: np.ndarray      # float32: the reference's `frac`
+    calls: np.ndarray     # int64 [n_calls, 2]: (consumed, produced) of every call, in FRAMES
+    state: Tuple[int, int, float]   # (read_position, available_frames, position) after the last call
+    accepted: int = 0     # frames accepted in total
+
+    def __len__(self) -> int:
+        return int(self.index.size)
+
+
+class FirReplay:
+    """ResamplerFir's state machine without its samples: Python ints and floats (a Python float is an f64, and
+    `position += ratio` is the same IEEE addition the reference makes)."""
+
+    def __init__(self, in_hz: int, out_hz: int, taps: int):
+        self.ratio = float(in_hz) / float(out_hz)
+        self.taps = int(taps)
+        self.read_position = 0
+        self.available_frames = 0
+        self.position = 0.0
+        self.base = 0          # absolute index of the frame at read_position
+        self.accepted = 0
+        self.index: List[int] = []
+        self.phase1: List[int] = []
+        self.frac: List[float] = []
+        self.calls: List[Tuple[int, int]] = []
+
+    def buffer_size_output_frames(self) -> int:
+        """resampler_fir.rs:456-465, per channel."""
+        return int(math.ceil(float(INPUT_CAPACITY - self.taps) / self.ratio)) + 2
+
+    def call(self, input_frames: int, output_capacity_frames: int) -> Tuple[int, int]:
+        write_position = self.read_position + self.available_frames
+        remaining_capacity = max(0, BUFFER_SIZE - write_position)
+        frames_to_copy = min(int(input_frames), remaining_capacity, INPUT_CAPACITY - self.available_frames)
+        self.available_frames += frames_to_copy
+        self.accepted += frames_to_copy
+        produced = 0
+        taps, ratio, position, available = self.taps, self.ratio, self.position, self.available_frames
+        index, phase1, frac = self.index, self.phase1, self.frac
+        while True:
+            input_offset = int(math.floor(position))
+            if input_offset + taps > available or produced >= output_capacity_frames:
+                break
+            phase_f = min((position - math.trunc(position)) * float(PHASES), float(PHASES - 1))
+            p1 = int(phase_f)
+            index.append(self.base + input_offset)
+            phase1.append(p1)
+            frac.append(phase_f - float(p1))     # rounded to f32 by positions()
+            produced += 1
+            position += ratio
+        consumed = min(int(math.floor(position)), available)
+        self.read_position += consumed
+        self.available_frames = available - consumed
+        self.position = position - float(consumed)
+        self.base += consumed
+        if self.read_position > INPUT_CAPACITY:   # compaction
+            self.read_position = 0
+        self.calls.append((frames_to_copy, produced))
+        return frames_to_copy, produced
+
+    def state(self) -> Tuple[int, int, float]:
+        return self.read_position, self.available_frames, self.position
+
+    def positions(self, first_output: int = 0) -> FirPositions:
+        """The outputs from `first_output` on (all calls so far are listed in .calls)."""
+        p1 = np.asarray(self.phase1[first_output:], np.int64)
+        return FirPositions(index=np.asarray(self.index[first_output:], np.int64), phase1=p1,
+                            phase2=np.minimum(p1 + 1, PHASES - 1),
+                            frac=np.asarray(self.frac[first_output:], np.float64).astype(np.float32),
+                            calls=np.asarray(self.calls, np.int64).reshape(-1, 2), state=self.state(),
+                            accepted=self.accepted)
+
+
+def fir_positions(in_hz: int, out_hz: int, taps: int, frames_per_call: Sequence[int],
+                  out_cap_frames: Sequence[int]) -> FirPositions:
+    """Replays resample() over calls that OFFER frames_per_call[i] frames with room for out_cap_frames[i] output
+    frames.  A call may accept fewer frames than offered (calls[:, 0] says how many): the absolute indices count the
+    accepted frames, so a caller that re-offers the rest (as the driver loops do) indexes its own buffer with them."""
+    rp = FirReplay(in_hz, out_hz, taps)
+    for n, cap in zip(frames_per_call, out_cap_frames):
+        rp.call(n, cap)
+    return rp.positions()
+
+
+def drive(rp: FirReplay, total_frames: int, chunk_frames: int) -> None:
+    """The reference's driver loop (resample/src/main.rs:226-254) over a buffer of total_frames frames: calls of
+    chunk_frames frames, the last one shorter, each with room for buffer_size_output(); the next call starts where the
+    last one stopped accepting."""
+    cap = rp.buffer_size_output_frames()
+    off = 0
+    while off < total_frames:
+        consumed, _ = rp.call(min(chunk_frames, total_frames - off), cap)
+        off += consumed
+        if consumed == 0:
+            break
+
+
+def fir_positions_bulk(in_hz: int, out_hz: int, taps: int, total_frames: int, chunk_frames: int) -> FirPositions:
+    rp = FirReplay(in_hz, out_hz, taps)
+    drive(rp, total_frames, chunk_frames)
+    return rp.positions()
+
+
+# ---- FIR: the sum -------------------------------------------------------------------------------------------------
+def fir_f64(x: np.ndarray, channels: int, coeffs: np.ndarray, positions: FirPositions, chunk: int = 4096) -> np.ndarray:
+    """(1 - frac) * sum(c1 * x) + frac * sum(c2 * x) in f64 over the reference's f32 operands: `coeffs` [1024][taps]
+    f32, `x` interleaved f32 (the accepted frames in order), frac f32, 1 - frac rounded to f32 as the reference rounds
+    it.  Returns interleaved f64 [outputs * channels]; `chunk` outputs at a time, so the windows stay a few MB."""
+    assert x.dtype == np.float32 and coeffs.dtype == np.float32 and coeffs.shape[0] == PHASES
+    taps = coeffs.shape[1]
+    frames = x.size // channels
+    xs = x.reshape(frames, channels).astype(np.float64)
+    c64 = coeffs.astype(np.float64)
+    n = len(positions)
+    out = np.empty((n, channels), np.float64)
+    if n:
+        assert int(positions.index.max()) + taps <= frames and int(positions.index.min()) >= 0
+    k = np.arange(taps)
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        win = xs[positions.index[a:b, None] + k[None, :]]            # [m, taps, channels]
+        s1 = np.einsum("mt,mtc->mc", c64[positions.phase1[a:b]], win)
+        s2 = np.einsum("mt,mtc->mc", c64[positions.phase2[a:b]], win)
+        f = positions.frac[a:b]
+        omf = (np.float32(1.0) - f).astype(np.float32).astype(np.float64)
+        out[a:b] = s1 * omf[:, None] + s2 * f.astype(np.float64)[:, None]
+    return out.reshape(-1)
+
+
+def fir_table(in_hz: int, out_hz: int, taps: int, attenuation_db: int = 90) -> np.ndarray:
+    """The reference's coefficient table [1024][taps] f32 (resampler_fir.rs:313-326, 407-416) from the oracle's filter
+    design; the tests assert it equal to OracleFir.coeffs() and to the library's own design."""
+    from oracle import pyoracle as o
+    beta = {60: 7.0, 90: 10.0, 120: 13.0}[attenuation_db]
+    base = o.calculate_cutoff_kaiser(taps, beta)
+    cutoff = base if in_hz <= out_hz else base * (float(out_hz) / float(in_hz))
+    return o.make_sincs_for_kaiser(taps, PHASES, float(np.float32(cutoff)), beta, o.WINDOW_SYMMETRIC)
+
+
+# ---- FFT ----------------------------------------------------------------------------------------------------------
+def fft_filter_f64(fft_in: int, fft_out: int) -> np.ndarray:
+    """rfft (f64) of the reference's f32 filter: sincs / (2 * fft_in) in f32, zero padded to 2 * fft_in
+    (resampler_fft.rs:353-376)."""
+    from oracle import pyoracle as o
+    cutoff = (o.calculate_cutoff_kaiser(fft_out, 10.0) * (float(fft_out) / float(fft_in)) if fft_in > fft_out
+              else o.calculate_cutoff_kaiser(fft_in, 10.0))
+    sincs = o.make_sincs_for_kaiser(fft_in, 1, float(np.float32(cutoff)), 10.0, o.WINDOW_PERIODIC).reshape(-1)
+    time = np.zeros(2 * fft_in, np.float64)
+    time[:fft_in] = (sincs / np.float32(2 * fft_in)).astype(np.float32)
+    return np.fft.rfft(time)
+
+
+def fft_f64(x: np.ndarray, channels: int, in_hz: int, out_hz: int, blocks: int, filter_of=None) -> np.ndarray:
+    """`blocks` chunks of ResamplerFft from a zero overlap: per channel, zero-pad a block to 2 * fft_in, rfft, multiply
+    the first min(fft_in + 1, fft_out) bins by the filter spectrum, zero the others, irfft at 2 * fft_out (unnormalised
+    as the reference's inverse is), add the carried overlap, keep the second half.  Interleaved f64 output.
+    filter_of: a hook for the defect models of tests/test_reference_f64.py (replaces the filter spectrum)."""
+    from oracle import pyoracle as o
+    fft_in, fft_out, _, _ = o.fft_plan(in_hz, out_hz)
+    assert x.dtype == np.float32 and x.size >= blocks * fft_in * channels
+    H = fft_filter_f64(fft_in, fft_out)
+    if filter_of is not None:
+        H = filter_of(H)
+    keep = min(fft_in + 1, fft_out)
+    xs = x[:blocks * fft_in * channels].reshape(blocks, fft_in, channels).astype(np.float64)
+    out = np.empty((blocks, fft_out, channels), np.float64)
+    for c in range(channels):
+        overlap = np.zeros(fft_out, np.float64)
+        for b in range(blocks):
+            buf = np.zeros(2 * fft_in, np.float64)
+            buf[:fft_in] = xs[b, :, c]
+            spec = np.zeros(fft_out + 1, np.complex128)
+            spec[:keep] = np.fft.rfft(buf)[:keep] * H[:keep]
+            y = np.fft.irfft(spec, 2 * fft_out) * float(2 * fft_out)
+            out[b, :, c] = y[:fft_out] + overlap
+            overlap = y[fft_out:]
+    return out.reshape(-1)
+
+
+# ---- the gate -----------------------------------------------------------------------------------------------------
+# Beyond these the gate stops rejecting the modelled defects of tests/test_reference_f64.py: no family's margin may pass them.
+M_RMS_CAP = 3.0
+M_MAX_CAP = 4.0
+# (M_RMS, M_MAX) per kernel family: 1.25 x the worst ratio over the family's cases in tests/test_accuracy_f64_gpu.py on an
+# MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
+MARGINS = {
+    "fir_bulk": (1.5, 1.6),    # worst x1.191 / x1.256: the f32 periodic kernels (pre-mixed rows); the split kernel x0.78 / x0.92
+    "lockstep": (1.0, 1.1),    # worst x0.784 / x0.867
+    "fft": (1.4, 1.4),         # worst x1.068 / x1.115 (per-call, 512-frame blocks)
+}
+
+
+def errors(y: np.ndarray, ref: np.ndarray) -> Tuple[float, float]:
+    """(RMS, max abs) of y - ref in f64."""
+    assert y.size == ref.size
+    if y.size == 0:
+        return 0.0, 0.0
+    d = np.asarray(y, np.float64).reshape(-1) - np.asarray(ref, np.float64).reshape(-1)
+    return float(np.sqrt(np.mean(d * d))), float(np.max(np.abs(d)))
+
+
+def budget(y: np.ndarray, ref: np.ndarray, yard_scalar: np.ndarray) -> Tuple[float, float]:
+    """The distance of y from the f64 reference `ref` in multiples of the yardstick's: (rms(y - ref) / rms(yard - ref),
+    max|y - ref| / max|yard - ref|), all three over the same outputs.  The yardstick is the reference's scalar spec
+    on the same input.  A non-finite y gives (inf, inf)."""
+    assert y.size == ref.size == yard_scalar.size and y.size > 0
+    if not np.all(np.isfinite(y)):
+        return float("inf"), float("inf")
+    e_rms, e_max = errors(y, ref)
+    s_rms, s_max = errors(yard_scalar, ref)
+    assert s_rms > 0.0 and s_max > 0.0, "the yardstick equals the f64 reference: nothing to measure against"
+    return e_rms / s_rms, e_max / s_max
