@@ -1,4 +1,8 @@
-#include "common.h"
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+
+#include "errors.h"
 
 namespace rsmp {
 

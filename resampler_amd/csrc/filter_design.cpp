@@ -8,7 +8,7 @@
 #include <mutex>
 #include <tuple>
 
-#include "common.h"
+#include "errors.h"
 
 #pragma STDC FP_CONTRACT OFF
 

@@ -1,5 +1,5 @@
-// fir_handle.h -- the ResamplerFir handle behind the C ABI (shared by fir_api.cpp and
-// fir_lockstep_api.cpp; not part of the public interface).
+// fir_handle.h -- the ResamplerFir handle behind the C ABI (shared by the files of its front-end,
+// DESIGN.md 4.3b, and fir_lockstep_api.cpp; not part of the public interface).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,7 +34,7 @@ struct rsmp_fir {
     // Launch plans travel through a small ring of pinned buffers so the host can enqueue several
     // launches ahead of the GPU (a slot is reused only after its upload has left host memory).
     static constexpr int kPlanSlots = 4;
-    hipEvent_t plan_copied[kPlanSlots] = {nullptr, nullptr, nullptr, nullptr};
+    rsmp::EventHolder plan_copied[kPlanSlots];
     bool plan_pending[kPlanSlots] = {false, false, false, false};
     int plan_slot = 0;
     // launch workspace (descs + runs + tile index), host-pinned and device
@@ -58,9 +58,25 @@ struct rsmp_fir {
     bool profiling = false;
     // ring of event pairs: launches made while profiling is on are timed without any host sync
     static constexpr int kProfRing = 64;
-    hipEvent_t prof_start[kProfRing] = {}, prof_stop[kProfRing] = {};
+    rsmp::EventHolder prof_start[kProfRing], prof_stop[kProfRing];
     size_t prof_count = 0;
 
     rsmp_fir(uint32_t i, uint32_t o, size_t t) : mirror(i, o, t) {}
 };
+
+namespace rsmp {
+
+// What is wrong with a batch's list of handles: the first fault in list order.  (Says nothing and sets no error: the host path
+// answers each with a message of its own, the routed path falls through to it.)
+enum class BatchFault { None, NullOrOtherDevice, Duplicate };
+inline BatchFault batch_handles_fault(rsmp_fir* const* rs, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        if (!rs[i] || rs[i]->device != rs[0]->device) return BatchFault::NullOrOtherDevice;
+        for (size_t k = 0; k < i; ++k)
+            if (rs[k] == rs[i]) return BatchFault::Duplicate;
+    }
+    return BatchFault::None;
+}
+
+}  // namespace rsmp
 

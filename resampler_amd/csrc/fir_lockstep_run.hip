@@ -8,7 +8,7 @@
 // integer positions by a replay of every call in parallel.  They leave, in HBM,
 //   * the per-call (consumed, produced) counts of every stream: [k][n] pairs;
 //   * the run's stream descriptor (FirStreamDesc, fir_kernels.h) exactly as the host planner of the bulk entry
-//     points (fir_api.cpp, launch_jobs) would have built it: outputs / frames accepted / frames retired by the
+//     points (fir_launch.cpp, launch_jobs) would have built it: outputs / frames accepted / frames retired by the
 //     run, the absolute counters it starts from, where its buffered frames are and where the tail goes;
 //   * the bitmap of outputs that take the row-1023 variant (position just below an integer, :562-564);
 //   * the stream's state after the run.

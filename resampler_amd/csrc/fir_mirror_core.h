@@ -16,7 +16,12 @@
 // increments).  A call is ~12 runs instead of hundreds of dependent adds.
 #pragma once
 
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define RSMP_HD __host__ __device__
+#else   // a host compiler (the planner's stand-alone tests): no qualifiers there
+#define RSMP_HD
+#endif
 
 #include <cmath>
 #include <cstddef>
@@ -52,19 +57,19 @@ struct FirCallCounts {
 // Largest k >= 0 with p0 + k*inc < bound, given p0 < bound, inc > 0, every p0 + k*inc up to the bound
 // exactly representable, and a seed `est` (any value; the two loops make the answer exact).
 template <class Idx>
-__host__ __device__ inline Idx mirror_refine_last_below(double p0, double inc, double bound, double est) {
+RSMP_HD inline Idx mirror_refine_last_below(double p0, double inc, double bound, double est) {
     Idx k = est >= 1.0 ? static_cast<Idx>(est) : Idx(0);
     while (k > 0 && fma(static_cast<double>(k), inc, p0) >= bound) --k;
     while (fma(static_cast<double>(k + 1), inc, p0) < bound) ++k;
     return k;
 }
 
-__host__ __device__ inline uint64_t mirror_bits(double v) {
+RSMP_HD inline uint64_t mirror_bits(double v) {
     union { double d; uint64_t u; } x;
     x.d = v;
     return x.u;
 }
-__host__ __device__ inline double mirror_from_bits(uint64_t u) {
+RSMP_HD inline double mirror_from_bits(uint64_t u) {
     union { double d; uint64_t u; } x;
     x.u = u;
     return x.d;
@@ -77,7 +82,7 @@ __host__ __device__ inline double mirror_from_bits(uint64_t u) {
 // floor() picks the previous frame) to the sink, leaves the last deviation in st.drift and returns the new next_int
 // (outputs from the END of the run to the next integer position).  Requires next_int < run.
 template <class Idx, class Sink>
-__host__ __device__ inline Idx mirror_run_wraps(FirMirrorState& st, Idx next_int, Idx count, Idx run, double pos, double inc,
+RSMP_HD inline Idx mirror_run_wraps(FirMirrorState& st, Idx next_int, Idx count, Idx run, double pos, double inc,
                                                 Idx den, double den_d, Sink& sink) {
     const Idx n_int = (run - 1 - next_int) / den + 1;
     const double next_d = static_cast<double>(next_int);
@@ -126,7 +131,7 @@ __host__ __device__ inline Idx mirror_run_wraps(FirMirrorState& st, Idx next_int
 // The output loop of one call (:542-590) in closed form.  Idx = uint32_t when the output capacity
 // is below 2^31 (32-bit integer and conversion instructions on the device), uint64_t otherwise.
 template <class Idx, class Sink>
-__host__ __device__ inline uint64_t mirror_output_loop(FirMirrorState& st, Idx output_capacity, double limit,
+RSMP_HD inline uint64_t mirror_output_loop(FirMirrorState& st, Idx output_capacity, double limit,
                                                        double& pos_io, Sink& sink) {
     Idx count = 0;
     double pos = pos_io;
@@ -191,7 +196,7 @@ __host__ __device__ inline uint64_t mirror_output_loop(FirMirrorState& st, Idx o
 }
 
 template <class Sink>
-__host__ __device__ inline FirCallCounts mirror_call(FirMirrorState& st, uint64_t input_frames,
+RSMP_HD inline FirCallCounts mirror_call(FirMirrorState& st, uint64_t input_frames,
                                                      uint64_t output_capacity, Sink& sink) {
     // resampler_fir.rs:524-528
     const uint64_t write_position = st.read_position + st.available;

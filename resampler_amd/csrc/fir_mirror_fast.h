@@ -56,7 +56,7 @@ struct MirrorBinades {
     double half0;                 // 2^e0
     double inc[kPredBinades];     // the ratio rounded to binade i's grid; 0: a tie there, no closed form
 };
-__host__ __device__ inline MirrorBinades mirror_binades(double ratio, uint32_t e0) {
+RSMP_HD inline MirrorBinades mirror_binades(double ratio, uint32_t e0) {
     MirrorBinades b;
     b.half0 = mirror_from_bits(static_cast<uint64_t>(1023 + e0) << 52);
     double half = b.half0;
@@ -71,14 +71,14 @@ __host__ __device__ inline MirrorBinades mirror_binades(double ratio, uint32_t e
 }
 
 // first binade with at least four outputs (the closed form needs three points of a run inside it)
-__host__ __device__ inline uint32_t mirror_first_binade(double ratio) {
+RSMP_HD inline uint32_t mirror_first_binade(double ratio) {
     uint32_t e = 0;
     double b = 1.0;
     while (b < 4.0 * ratio && e < 40) { b *= 2.0; ++e; }
     return e;
 }
 
-__host__ __device__ inline MirrorRunBase mirror_run_base(const FirMirrorState& st, uint32_t in_frames, uint32_t calls) {
+RSMP_HD inline MirrorRunBase mirror_run_base(const FirMirrorState& st, uint32_t in_frames, uint32_t calls) {
     MirrorRunBase b;
     b.abs_out0 = st.abs_out;
     b.abs_consumed0 = st.abs_consumed;
@@ -96,12 +96,12 @@ __host__ __device__ inline MirrorRunBase mirror_run_base(const FirMirrorState& s
 }
 
 // ceil(x * den / num): the number of outputs m >= 0 with m * num / den < x
-__host__ __device__ inline uint64_t mirror_outputs_below(uint64_t x, uint64_t num, uint64_t den) {
+RSMP_HD inline uint64_t mirror_outputs_below(uint64_t x, uint64_t num, uint64_t den) {
     return (x * den + num - 1) / num;
 }
 
 // The structure of call c (0-based) of the run, in exact arithmetic.
-__host__ __device__ inline MirrorPred mirror_predict(const MirrorRunBase& b, uint32_t c) {
+RSMP_HD inline MirrorPred mirror_predict(const MirrorRunBase& b, uint32_t c) {
     MirrorPred pr;
     const uint64_t a_prev = b.abs_consumed0 + b.avail0 + static_cast<uint64_t>(c) * b.in_frames;   // frames accepted before the call
     const uint64_t a_now = a_prev + b.in_frames;
@@ -167,12 +167,12 @@ struct MirrorEdges {
     uint64_t q[kPredBinades + 1];   // floor(2^(e0+i) den / num)
     uint32_t r[kPredBinades + 1];   // ... and the remainder (< num < 2^21)
 };
-__host__ __device__ inline void mirror_edge(const MirrorRunBase& b, uint32_t i, uint64_t& q, uint32_t& r) {
+RSMP_HD inline void mirror_edge(const MirrorRunBase& b, uint32_t i, uint64_t& q, uint32_t& r) {
     const uint64_t t = (1ull << (b.e0 + i)) * b.den;   // < 2^40 * 2^21
     q = t / b.num;
     r = static_cast<uint32_t>(t - q * b.num);
 }
-__host__ __device__ inline MirrorPred mirror_predict_edges(const MirrorRunBase& b, const MirrorEdges& ed, uint32_t c) {
+RSMP_HD inline MirrorPred mirror_predict_edges(const MirrorRunBase& b, const MirrorEdges& ed, uint32_t c) {
     MirrorPred pr;
     const uint64_t a_prev = b.abs_consumed0 + b.avail0 + static_cast<uint64_t>(c) * b.in_frames;
     const uint64_t a_now = a_prev + b.in_frames;
@@ -244,7 +244,7 @@ __host__ __device__ inline MirrorPred mirror_predict_edges(const MirrorRunBase& 
 // (abs_out one ahead of the prediction, the frames retired as predicted -- so only while ratio < 1, where the output
 // behind an integer position shares its input frame) drops it from the structure.
 template <class OnRun>
-__host__ __device__ inline bool mirror_call_fast(FirMirrorState& st, uint32_t in_frames, uint64_t output_capacity,
+RSMP_HD inline bool mirror_call_fast(FirMirrorState& st, uint32_t in_frames, uint64_t output_capacity,
                                                  const MirrorPred& pr, const MirrorBinades& bn, FirCallCounts& out, OnRun&& on_run) {
     // resampler_fir.rs:524-528: the whole offer must be accepted
     const uint64_t write_position = st.read_position + st.available;
@@ -317,13 +317,13 @@ __host__ __device__ inline bool mirror_call_fast(FirMirrorState& st, uint32_t in
 // no tie binade (mirror_chain_ready): two dependent operations per binade, no checks -- those are mirror_call_fast's,
 // which the replay of the call (mirror_replay_wraps) runs in parallel afterwards.  The caller has made sure that the
 // state is where the prediction starts (abs_out == m0, abs_consumed == c0) and that the whole offer is accepted.
-__host__ __device__ inline bool mirror_chain_ready(const MirrorBinades& bn) {
+RSMP_HD inline bool mirror_chain_ready(const MirrorBinades& bn) {
     bool ok = true;
 #pragma unroll
     for (uint32_t i = 0; i < kPredBinades; ++i) ok = ok && bn.inc[i] != 0.0;
     return ok;
 }
-__host__ __device__ inline void mirror_call_chain(FirMirrorState& st, uint32_t in_frames, const MirrorPred& pr,
+RSMP_HD inline void mirror_call_chain(FirMirrorState& st, uint32_t in_frames, const MirrorPred& pr,
                                                   const MirrorBinades& bn, FirCallCounts& out) {
     const uint64_t avail = st.available + in_frames;
     const double ratio = st.ratio;
@@ -375,7 +375,7 @@ struct ChainPlan {
 };
 // What a call's prediction says about the chain's shape.  kChainLean: the chain below applies -- no output at the call's
 // limit, no clamped count, the binades below the top one full, n_low small.
-__host__ __device__ inline ChainPlan mirror_chain_plan(const MirrorPred& pr) {
+RSMP_HD inline ChainPlan mirror_chain_plan(const MirrorPred& pr) {
     ChainPlan p;
     uint32_t top = 0, n_top = pr.n[0];
     bool any = false, full = true;
@@ -399,7 +399,7 @@ __host__ __device__ inline ChainPlan mirror_chain_plan(const MirrorPred& pr) {
 // (UNIFORM: every lane of the wave runs the SAME call -- the retired count is taken through a scalar register; false: a call per lane,
 // the parallel chain of fir_lockstep_run.hip)
 template <uint32_t L, bool TIES, bool UNIFORM = true>
-__host__ __device__ inline uint32_t mirror_chain_step(double& pos_io, ChainScalars& sc, uint32_t in_frames, double ratio,
+RSMP_HD inline uint32_t mirror_chain_step(double& pos_io, ChainScalars& sc, uint32_t in_frames, double ratio,
                                                       const MirrorBinades& bn, uint32_t n_total, uint32_t ctl, uint32_t n_last,
                                                       const double (&m)[kPredBinades]) {
     double pos = pos_io;
@@ -449,7 +449,7 @@ __host__ __device__ inline uint32_t mirror_chain_step(double& pos_io, ChainScala
 }
 // (host: the shape as a run-time value)
 template <bool TIES, uint32_t L = 0>
-__host__ inline uint32_t mirror_chain_step_any(uint32_t shape, double& pos, ChainScalars& sc, uint32_t in_frames, double ratio,
+inline uint32_t mirror_chain_step_any(uint32_t shape, double& pos, ChainScalars& sc, uint32_t in_frames, double ratio,
                                                const MirrorBinades& bn, uint32_t n_total, const ChainPlan& p) {
     if constexpr (L < kPredBinades) {
         if (shape == L) return mirror_chain_step<L, TIES>(pos, sc, in_frames, ratio, bn, n_total, p.ctl, p.n_last, p.m);
@@ -464,7 +464,7 @@ __host__ inline uint32_t mirror_chain_step_any(uint32_t shape, double& pos, Chai
 // mirror_call; st.drift / st.periodic_ok are updated as mirror_call updates them.  Returns whether the call had an
 // output at an integer position (so that st.drift is this call's).
 template <class Sink>
-__host__ __device__ inline bool mirror_replay_wraps(FirMirrorState& st, uint32_t in_frames, const MirrorPred& pr,
+RSMP_HD inline bool mirror_replay_wraps(FirMirrorState& st, uint32_t in_frames, const MirrorPred& pr,
                                                     const MirrorBinades& bn, Sink& sink, bool* checks_ok = nullptr) {
     // (st.abs_out may be one ahead of the prediction: see mirror_call_fast)
     const uint32_t ahead = static_cast<uint32_t>(st.abs_out - pr.m0);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "fir_kernels.h"
+#include "fir_periodic_plan.h"
 #include "fir_plan.h"
 
 namespace rsmp {
@@ -103,9 +104,6 @@ struct PeriodicState {
     double table_drift = 0.0;
 };
 
-bool periodic_supported(const FirMirror& m, size_t channels, size_t taps, int kernel_mode);
-bool periodic_worthwhile(const FirMirror& planned, size_t produced_frames, int kernel_mode);
-
 // Makes sure `st` holds the geometry and the device class table matching the stream's rate pair
 // and its current f64 drift (host build + one upload, cached per device and shared by every
 // stream with the same polyphase table, rate pair and drift).
@@ -120,12 +118,6 @@ int periodic_bind(PeriodicState& st, int device, const std::vector<float>& table
 struct HostClassTable;
 int class_table_for(int device, const std::vector<float>& table, const PeriodicGeometry& g, double drift,
                     ClassTable* out, const HostClassTable* prebuilt = nullptr);
-
-// Bitmap of wrapped outputs for one launch: bit K <-> the output with absolute index
-// (abs_out / den + K) * den.  Returns the number of 32-bit words.
-size_t periodic_wrap_words(uint64_t abs_out, uint32_t n_out, uint64_t den);
-void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_out, uint64_t den,
-                             uint32_t* words, size_t n_words);
 
 // One launch per geometry: d_descs[0..n_streams) all use `geo`; grid = (max_blocks, n_streams).
 // `d_work_counter` is a zero-initialised 64-bit device word owned by the caller; the kernel leaves it

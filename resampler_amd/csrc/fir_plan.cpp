@@ -9,8 +9,9 @@
 #include <cstring>
 #include <numeric>
 
-#include "common.h"
+#include "errors.h"
 #include "filter_design.h"
+#include "fir_hostplan.h"
 #include "fir_mirror_fast.h"
 
 #pragma STDC FP_CONTRACT OFF
@@ -115,29 +116,18 @@ extern "C" int rsmp_fir_plan_call(rsmp_fir_plan* p, size_t input_frames,
     return RSMP_OK;
 }
 
-// The driver loop of resample/src/main.rs:226-254 on the mirror alone (what rsmp_fir_resample_bulk plans,
-// fir_api.cpp plan_job_uncached): every call offers min(chunk, remaining) frames and the full output
-// capacity; stops after max_calls calls (0 = no limit) or when the input is used up.
+// The driver loop of resample/src/main.rs:226-254 on the mirror alone (what rsmp_fir_resample_bulk plans: the same
+// loop, drive_bulk in fir_hostplan.cpp, here keeping no runs): every call offers min(chunk, remaining) frames and the
+// full output capacity; stops after max_calls calls (0 = no limit) or when the input is used up.
 extern "C" int rsmp_fir_plan_bulk(rsmp_fir_plan* p, size_t in_frames, size_t chunk_frames, size_t max_calls,
                                   size_t* frames_accepted, size_t* frames_produced, size_t* n_calls) {
     if (!p || chunk_frames == 0) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_plan_bulk: invalid argument");
-    const size_t cap_frames = p->mirror.buffer_size_output_frames();
-    size_t offset = 0, produced = 0, calls = 0;
-    while (offset < in_frames && (max_calls == 0 || calls < max_calls)) {
-        const size_t remaining = in_frames - offset;
-        const rsmp::FirCallResult c =
-            p->mirror.call(remaining < chunk_frames ? remaining : chunk_frames, cap_frames, 0, 0, nullptr, nullptr);
-        produced += c.produced;
-        offset += c.accepted;
-        ++calls;
-        if (c.accepted == 0) break;
-    }
-    if (frames_accepted) *frames_accepted = offset;
-    if (frames_produced) *frames_produced = produced;
-    if (n_calls) *n_calls = calls;
+    const rsmp::BulkTotals t = rsmp::drive_bulk(p->mirror, in_frames, chunk_frames, max_calls, nullptr, nullptr, nullptr);
+    if (frames_accepted) *frames_accepted = t.accepted;
+    if (frames_produced) *frames_produced = t.produced;
+    if (n_calls) *n_calls = t.calls;
     return RSMP_OK;
 }
-
 
 // Self-test of the run planner's fast path (fir_mirror_fast.h) against mirror_call, on the host: `calls` calls of
 // `in_frames` frames from the plan's current state, predicted in runs of `run_len` calls.  Every call is done both ways

@@ -374,6 +374,99 @@ def test_batch_with_two_rate_pairs_and_mixed_kernels():
             assert rms(d_out[i][: produced[i]].cpu().numpy(), yr) <= RMS_TOL, (step, i)
 
 
+def test_launch_workspace_paths_without_a_host_sync():
+    """The three ways a launch's workspace (stream descriptors, position runs, tile index, wrap bitmaps) reaches the kernels
+    -- read from mapped host memory (at most 16 KiB), uploaded into the slot's HBM buffer, found there already -- through a
+    ring of four slots per leading handle: seven launches led by ONE handle on ONE stream, nothing waited for in between.
+      (a) slot 0: three streams, mapped;
+      (b) slot 1: 96 streams from the fresh state, uploaded.  The stream count: sizeof(FirStreamDesc) is 184 bytes (twelve
+          pointers, eleven 32-bit words, padding to 8, three 64-bit counters, the f64 drift, two more words), so 96
+          descriptors alone are 17664 bytes -- past the 16 KiB of the mapped path whatever the plans' arrays add (a batch of
+          89 or fewer could fit).  Two-channel 44.1 -> 48 k streams of 2000 .. 2950 frames, no two alike, and two
+          44100 -> 48001 streams (generic kernel: runs and tile index in the image as well);
+      (c) slot 2: (b) again after reset(), same buffers: uploaded again (this slot's HBM is new);
+      (d) slot 3: (b) again WITHOUT reset, buffers of its own: every stream continues, the image is another one;
+      (e) slot 0 again: the three streams continue from where (c) and (d) left them -- the slot's event from (a) is waited
+          for on the host, the only wait;
+      (e2) slot 1: (e) once more, the streams continuing: mapped, so (b)'s image there is forgotten;
+      (f) slot 2 again: (b) after reset(), (c)'s buffers: the image is the one slot 2 holds since (c) -- no upload.  It is
+          the same image only because every handle is back at the history buffer it had at (c): a launch swaps a handle's
+          two history buffers and reset() does not swap them back, and between (c) and (f) the first three handles made
+          four launches (c, d, e, e2) and the others two (c, d).  (Without (e2), (f) would meet (b)'s slot with the
+          other 93 handles' buffers swapped: an image of its own, uploaded.)
+    The outputs of (b) and (c) are set aside by device copies on the stream and the shared buffers overwritten with NaN
+    before the next launch into them.  After ONE synchronise: every stream of every launch against the oracle's driver
+    loop, exact counts."""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    n_big, n_small, chunk = 96, 3, 512
+    odd = (2, 50)   # the 44100 -> 48001 streams: one of them in the small batch too
+    gs, xs_big, xs_small, caps = [], [], [], []
+    for i in range(n_big):
+        out_hz = 48001 if i in odd else 48000
+        gs.append(ra.ResamplerFir.new_from_hz(2, 44100, out_hz, ra.Latency.Sample64, ra.Attenuation.Db90))
+        xs_big.append(synth.fast_noise(2 * (2000 + 10 * i), seed=4000 + i))
+        caps.append(2 * (int((2950 + 4096) * out_hz / 44100) + 16))   # whatever is buffered (<= 4096 frames) plus the longest input
+    for i in range(n_small):
+        xs_small.append(synth.fast_noise(2 * (1500 + 277 * i), seed=4200 + i))
+    # the oracle, once: (a) from the fresh state; (b) = (c) = (f) from the fresh state, then (d), (e) and (e2) carried on from (c)
+    want = {k: [] for k in ("a", "b", "d", "e", "e2")}
+    for i in range(n_big):
+        out_hz = 48001 if i in odd else 48000
+        r = o.OracleFir(2, 44100, out_hz, 128, 90, ORACLE_KIND)
+        want["b"].append(r.resample_all(xs_big[i], chunk)[0])
+        want["d"].append(r.resample_all(xs_big[i], chunk)[0])
+        if i < n_small:
+            want["e"].append(r.resample_all(xs_small[i], chunk)[0])
+            want["e2"].append(r.resample_all(xs_small[i], chunk)[0])
+            r.reset()
+            want["a"].append(r.resample_all(xs_small[i], chunk)[0])
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        in_big = [torch.from_numpy(x).to(dev) for x in xs_big]
+        in_small = [torch.from_numpy(x).to(dev) for x in xs_small]
+        new_outs = lambda n: [torch.full((caps[i],), float("nan"), device=dev) for i in range(n)]
+        out = {"a": new_outs(n_small), "b": new_outs(n_big), "d": new_outs(n_big), "e": new_outs(n_small), "e2": new_outs(n_small)}
+        torch.cuda.synchronize()
+        small, big = ra.FirBatch(gs[:n_small]), ra.FirBatch(gs)   # gs[0] leads both: one ring of slots
+        small.device_planner = big.device_planner = False        # (the host planner's launches are the ones under test)
+        handle = ra.torch_stream(stream)
+        counts, kept = {}, {}
+
+        def launch(name, batch, d_in, d_out):
+            batch.bind(d_in, d_out)
+            c, p = batch.resample_bulk_device(chunk, handle)
+            counts[name] = (np.array(c), np.array(p))
+
+        launch("a", small, in_small, out["a"])
+        big.reset()
+        launch("b", big, in_big, out["b"])
+        kept["b"] = [t.clone() for t in out["b"]]
+        for t in out["b"]:
+            t.fill_(float("nan"))
+        big.reset()
+        launch("c", big, in_big, out["b"])
+        kept["c"] = [t.clone() for t in out["b"]]
+        for t in out["b"]:
+            t.fill_(float("nan"))
+        launch("d", big, in_big, out["d"])
+        launch("e", small, in_small, out["e"])
+        launch("e2", small, in_small, out["e2"])
+        big.reset()
+        launch("f", big, in_big, out["b"])
+        stream.synchronize()
+    got = {"a": out["a"], "b": kept["b"], "c": kept["c"], "d": out["d"], "e": out["e"], "e2": out["e2"], "f": out["b"]}
+    ref = {"a": want["a"], "b": want["b"], "c": want["b"], "d": want["d"], "e": want["e"], "e2": want["e2"], "f": want["b"]}
+    for name in got:
+        xs = xs_small if name in ("a", "e", "e2") else xs_big
+        consumed, produced = counts[name]
+        for i, x in enumerate(xs):
+            yr = ref[name][i]
+            assert consumed[i] == x.size and produced[i] == yr.size, (name, i, consumed[i], produced[i], yr.size)
+            e = rms(got[name][i][: yr.size].cpu().numpy(), yr)
+            assert e <= RMS_TOL, (name, i, e)
+
+
 def test_repeated_launches_are_bit_identical():
     """The periodic kernels are full of dynamic scheduling (work queues, claims, producer / consumer
     flags): whatever the interleaving, a launch must produce the same bits.  40 launches of a

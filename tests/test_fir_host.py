@@ -113,6 +113,25 @@ def test_plan_matches_oracle_counts_and_state(in_hz, out_hz):
 
 
 @pytest.mark.parametrize("in_hz,out_hz", RATE_PAIRS)
+def test_plan_bulk_matches_the_oracle_driver_loop(in_hz, out_hz):
+    """rsmp_fir_plan_bulk runs the one bulk driver loop of the library (the loop rsmp_fir_resample_bulk plans with, here
+    keeping no runs) against the oracle's main.rs:226-254 loop: frames accepted / produced and the number of calls, for
+    calls of 1, 512 and 4096 frames over 0, 1, one chunk, one chunk + 1 and 10 chunks + 7 frames, without a limit on the
+    calls and stopped after three (the oracle's first three calls then)."""
+    for chunk in (1, 512, 4096):
+        for total in (0, 1, chunk, chunk + 1, 10 * chunk + 7):
+            ref = o.OracleFir(1, in_hz, out_hz, 128, 90)
+            out, calls = ref.resample_all(np.zeros(total, np.float32), chunk)
+            assert calls.shape[0] == (total + chunk - 1) // chunk and int(calls[:, 1].sum()) == out.size
+            plan = ra.FirPlan(in_hz, out_hz, ra.Latency.Sample64)
+            assert plan.bulk(total, chunk, 0) == (int(calls[:, 0].sum()), out.size, calls.shape[0]), (chunk, total)
+            assert plan.state() == ref.state(), (chunk, total)
+            first = calls[:3]
+            plan3 = ra.FirPlan(in_hz, out_hz, ra.Latency.Sample64)
+            assert plan3.bulk(total, chunk, 3) == (int(first[:, 0].sum()), int(first[:, 1].sum()), first.shape[0]), (chunk, total)
+
+
+@pytest.mark.parametrize("in_hz,out_hz", RATE_PAIRS)
 def test_plan_segments_reproduce_the_f64_recurrence_exactly(in_hz, out_hz):
     taps = 128
     plan = ra.FirPlan(in_hz, out_hz, ra.Latency.Sample64)
