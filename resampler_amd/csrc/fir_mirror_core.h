@@ -18,10 +18,8 @@
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#define RSMP_HD __host__ __device__
-#else   // a host compiler (the planner's stand-alone tests): no qualifiers there
-#define RSMP_HD
 #endif
+#include "rsmp_hd.h"   // (a host compiler -- the planner's stand-alone tests -- sees no qualifiers)
 
 #include <cmath>
 #include <cstddef>

@@ -19,24 +19,16 @@
 
 #include <hip/hip_ext.h>
 
-#include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <tuple>
 
 #include "common.h"
-#include "filter_design.h"
+#include "fir_kernel_launch.h"
+#include "fir_periodic_consts.h"
 
 namespace rsmp {
 
 namespace {
-
-constexpr uint32_t kLdsTwoPerCu = 80 * 1024;   // two workgroups per CU
-constexpr uint32_t kLdsMax = 160 * 1024;
 
 struct GeoArgs {
     uint32_t a, b, r, row_len, n_tiles, lp, pw, row_stride, waves, channels, xprev_len;
@@ -937,12 +929,7 @@ static_assert(kDbMaxImages * 7 <= 32, "control arrays end where the item posts b
 // control words: seven arrays of kDbMaxImages (see fir_periodic_db_kernel) + one item post per image
 constexpr uint32_t kDbPostBase = 32;   // kDbMaxImages posts of kPostWords words follow
 constexpr uint32_t kDbMailBase = 64;   // producer 0 -> other producers: the claimed item, one slot per s & 3
-constexpr uint32_t kDbCtrlWords = 80;
-// floats per image (frame-before-period block + rows), a 16-byte multiple
-__host__ __device__ inline uint32_t db_image_len(uint32_t xprev_len, uint32_t pw, uint32_t row_stride) {
-    // + 96: the matrix-core units prefetch up to 11 steps (88 dwords) past a window's end
-    return (xprev_len + (pw + 1) * row_stride + 96 + 3) / 4 * 4;
-}
+static_assert(kDbMailBase + 4 <= kDbCtrlWords, "the control words (fir_periodic_consts.h: the host sizes the LDS by them) hold the mail slots");
 
 __device__ __forceinline__ uint32_t lds_load_acquire(uint32_t* p) {
     return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -955,10 +942,6 @@ __device__ __forceinline__ void lds_store_release(uint32_t* p, uint32_t v) {
 // MFMAs.  Must divide 12 (the window is a multiple of 12 steps) so that a step's ring slot is the
 // same in every unit.
 constexpr uint32_t kRing = 4;
-// Wrap classes per super period the matrix-core path handles inside the kernel (b = r * den, r <= this).
-constexpr uint32_t kMfmaWrapMax = 2;
-// per image: {ch0, ch1, take, -} per period and wrap class
-__host__ __device__ inline uint32_t mfma_wrap_words(uint32_t pw) { return kMfmaWrapMax * ((pw + 15) / 16 * 16) * 4; }
 
 // Everything about a unit that can be computed ahead of its MFMAs.
 template <int G>
@@ -1665,14 +1648,8 @@ __global__ __launch_bounds__(256) void fir_wrap_fixup_kernel(const FirStreamDesc
     }
 }
 
-// LDS prefix: [4 dwords: dynamic tile counter] [pw][C] previous-frame samples, 16-byte multiple.
-uint32_t xprev_len_of(uint32_t pw, uint32_t channels) { return 4 + (pw * channels + 3) / 4 * 4; }
-
 GeoArgs to_args(const PeriodicGeometry& g) {
-    static const uint32_t debug = [] {
-        const char* e = rsmp::knob("RSMP_FIR_DEBUG");
-        return e ? static_cast<uint32_t>(atoi(e)) : 0u;
-    }();
+    const uint32_t debug = fir_debug_knob();
     constexpr uint32_t stagger = 1200;   // 12 us, in 10 ns units
     const uint32_t channels = g.lp * g.cg;
     return GeoArgs{g.a, g.b, g.b / g.den, g.row_len, g.mfma ? g.n_units : g.n_tiles, g.lp, g.pw, g.row_stride, g.waves,
@@ -1681,470 +1658,31 @@ GeoArgs to_args(const PeriodicGeometry& g) {
                    g.inline_wraps ? 1u : 0u, debug, stagger, nullptr, nullptr, 0u, 0u, nullptr, 0u, NfArgs{nullptr, 0u, 0u}};
 }
 
-// Device class tables, shared by every stream on a device with the same polyphase table, rate
-// pair, geometry and drift.
-struct ClassTableKey {
-    int device;
-    const void* table;
-    uint32_t den, a, b, row_len, mfma;
-    uint64_t drift_bits;
-    bool operator<(const ClassTableKey& o) const {
-        return std::tie(device, table, den, a, b, row_len, mfma, drift_bits) <
-               std::tie(o.device, o.table, o.den, o.a, o.b, o.row_len, o.mfma, o.drift_bits);
-    }
-};
-struct ClassTableCache {
-    std::mutex mu;
-    struct Entry { ClassTable ct; uint64_t used; };
-    std::map<ClassTableKey, Entry> tables;
-    uint64_t tick = 0;
-    static constexpr size_t kMaxTables = 96;    // (a geometry's table is 0.1-0.4 MB)
-};
-ClassTableCache& class_cache() {
-    static ClassTableCache* c = new ClassTableCache;
-    return *c;
-}
-// Device allocations of tables nobody holds any more.  Kernels enqueued earlier may still read them, so they are freed in
-// batches, behind a hipDeviceSynchronize (class_table_for, on its slow path: a table is being built anyway).
-struct ClassTableGraveyard {
-    std::mutex mu;
-    std::vector<std::pair<int, void*>> dead;   // (device, allocation)
-    static constexpr size_t kPurgeAt = 32;
-};
-ClassTableGraveyard& class_graveyard() {
-    static ClassTableGraveyard* g = new ClassTableGraveyard;
-    return *g;
-}
-void purge_class_graveyard(int device) {
-    ClassTableGraveyard& gy = class_graveyard();
-    std::vector<std::pair<int, void*>> mine;
-    {
-        std::lock_guard<std::mutex> lock(gy.mu);
-        if (gy.dead.size() < ClassTableGraveyard::kPurgeAt) return;
-        for (auto it = gy.dead.begin(); it != gy.dead.end();) {
-            if (it->first == device) { mine.push_back(*it); it = gy.dead.erase(it); }
-            else ++it;
-        }
-    }
-    if (mine.empty()) return;
-    (void)hipDeviceSynchronize();   // (the current device is `device`: the callers' DeviceGuard)
-    for (auto& d : mine) (void)hipFree(d.second);
-}
-
-constexpr double kDriftQuantum = 2e-9;  // positions this close share a class table
-
-inline uint32_t class_offset(const PeriodicGeometry& g, uint32_t j) {
-    return static_cast<uint32_t>((static_cast<uint64_t>(j) * g.a) / g.b);
-}
-
 }  // namespace
-
-namespace {
-// RSMP_FIR_MFMA: 0 = vector kernels only; 1 / 2 / 4 = exact-f32 matrix-core kernel with that many 16-period
-// groups per work unit; 3 (default) = split-bf16 matrix kernel (fir_split.hip) where its geometry exists,
-// else as 2.  Two interleaved channels only.
-int mfma_knob() {
-    static const int knob = [] {
-        const char* e = rsmp::knob("RSMP_FIR_MFMA");
-        return e ? atoi(e) : 3;
-    }();
-    return knob;
-}
-
-PeriodicGeometry geometry_for(uint64_t num, uint64_t den, uint32_t taps, uint32_t channels,
-                              bool want_mfma) {
-    PeriodicGeometry g;
-    if (num == 0 || den == 0 || channels == 0 || channels > 64) return g;
-    if (num > (1u << 20) || den > (1u << 20)) return g;
-    const int knob_mfma = mfma_knob() == 3 ? 2 : mfma_knob();   // 3: this is the fallback of the split kernel
-    const uint32_t ct = want_mfma ? kMfmaClassTile : kClassTile;
-    // max in-tile shift: off(j) = floor(j*num/den); tiles start at multiples of the class tile.
-    const uint32_t shift = static_cast<uint32_t>(((ct - 1) * num + den - 1) / den);
-    g.taps = taps;
-    g.den = static_cast<uint32_t>(den);
-    // whole 8-tap chunks (fir_periodic_kernel) / three blocks of four 4-tap MFMA steps
-    g.row_len = want_mfma ? (taps + shift + 47) / 48 * 48 : (taps + shift + 7) / 8 * 8;
-    // super period: a >= row_len (a window spans at most two rows) and b >= one class tile
-    uint64_t r = (g.row_len + num - 1) / num;
-    if (den * r < ct) r = (ct + den - 1) / den;
-    const uint64_t a = num * r, b = den * r;
-    if (a > 4096 || b > (1u << 16)) return g;
-    g.a = static_cast<uint32_t>(a);
-    g.b = static_cast<uint32_t>(b);
-    g.n_tiles = (g.b + ct - 1) / ct;
-    g.n_units = g.n_tiles;
-    // wrap variant inside the kernel: vector kernels den >= 8 (one wrap class per 8-class tile at
-    // most); matrix-core path den >= 16 and at most kMfmaWrapMax wrap classes per super period
-    // (only the register-resident variant picks the results up: windows <= 144 taps, 1-2 groups/unit)
-    static const bool ring_forced = rsmp::knob("RSMP_FIR_MFMA_RING") != nullptr;
-    // (144 taps at most: with a 192-tap tile in registers the register-resident build spilled)
-    const bool mfma_regs = want_mfma && knob_mfma <= 2 && g.row_len <= 144 && !ring_forced;
-    g.inline_wraps = want_mfma ? (mfma_regs && den >= kMfmaClassTile && r <= kMfmaWrapMax) : den >= kClassTile;
-
-    bool two_per_cu = false;   // set by fit(): the single-image vector kernel with two workgroups per CU
-    auto fit = [&](uint32_t cg) -> bool {
-        two_per_cu = false;
-        if (channels % cg != 0) return false;
-        const uint32_t lp = channels / cg;
-        if (lp > 64) return false;
-        const uint32_t pw_max = 64 / lp;
-        // odd number of frames per row: the lane stride then hits every LDS bank once (and with two
-        // channels per lane, 2 * odd dwords keeps every lane's ds_read_b64 8-byte aligned)
-        const uint32_t stride = (g.a | 1u) * channels;
-        const uint32_t row_bytes = stride * 4;
-        const uint32_t fixed = (64 * channels + 16) * 4;  // xprev
-        auto rows_in = [&](uint32_t budget) -> uint32_t {
-            if (budget <= fixed + 2 * row_bytes) return 0;
-            return (budget - fixed) / row_bytes - 1;
-        };
-        g.cg = cg;
-        g.lp = lp;
-        g.row_stride = stride;
-        if (want_mfma) {
-            // Two images in one workgroup (fir_periodic_db_kernel), if that keeps >= 75 % of the lanes
-            // busy; else periodic_geometry() retries with the vector kernels.  Per image: + 96 floats of
-            // read-ahead padding + the wrap results.  (A ring of four 32-period images, one per producer,
-            // measured equal: the doubled per-item work ate what the extra slack gained.  The same
-            // workgroup around the vector tile code measured slower than two single-image workgroups
-            // per CU: 12 consumer waves cannot hide the scalar-cache latency that 24 can.)
-            auto db_bytes = [&](uint32_t pw) -> uint32_t {
-                return (kDbCtrlWords + 2 * (db_image_len(xprev_len_of(pw, channels), pw, stride) + mfma_wrap_words(pw))) * 4;
-            };
-            uint32_t pw = pw_max;
-            while (pw * 4 >= pw_max * 3 && db_bytes(pw) > kLdsMax) --pw;
-            if (pw * 4 < pw_max * 3) return false;
-            g.images = 2;
-            g.pw = pw;
-            g.producers = 4;
-            g.lds_bytes = db_bytes(pw);
-            g.mfma = static_cast<uint32_t>(knob_mfma);
-            // a work unit spans knob_mfma groups of 16 periods
-            const uint32_t groups = (pw + 15) / 16;
-            g.n_units = g.n_tiles * ((groups + g.mfma - 1) / g.mfma);
-            // 4 producers + 8 consumers: two consumer waves per SIMD keep the matrix pipe busy, more only
-            // add arbitration (and 12 waves are the __launch_bounds__(768) of the kernel)
-            g.waves = 12;
-            return true;
-        }
-        uint32_t pw = rows_in(kLdsTwoPerCu);
-        two_per_cu = pw * 4 >= pw_max * 3;
-        if (!two_per_cu) pw = rows_in(kLdsMax);  // < 75% of the lanes: use the whole LDS
-        if (pw > pw_max) pw = pw_max;
-        if (pw * 2 < pw_max || pw == 0) return false;
-        g.pw = pw;
-        g.producers = 0;
-        g.lds_bytes = (xprev_len_of(pw, channels) + (pw + 1) * stride) * 4;
-        // waves per workgroup: a multiple of the 4 SIMDs, at most 12 (__launch_bounds__(768, 6));
-        // tiles are claimed dynamically, so the count need not divide n_tiles
-        g.waves = g.n_tiles >= 12 ? 12u : (g.n_tiles >= 8 ? 8u : 4u);
-        return true;
-    };
-    if (want_mfma) {   // the matrix-core kernel is written for two channels per lane group
-        if (!fit(2)) return g;
-    } else {
-        // Two channels per lane make every v_pk_fma_f32 count twice, but with many channels a period row is long
-        // and only one single-image workgroup fits a CU -- staging and arithmetic then take turns.  One channel per
-        // lane halves the periods per image: where that is what lets two workgroups share a CU it is faster
-        // (8 channels 96 -> 44.1 kHz: 0.73 -> 0.62 ms per 20 M frames).
-        const bool ok2 = fit(2);
-        if (!ok2 || !two_per_cu) {
-            const PeriodicGeometry g2 = g;
-            if (!(fit(1) && (two_per_cu || !ok2))) {
-                if (!ok2) return g;
-                g = g2;
-            }
-        }
-    }
-    g.ok = true;
-    return g;
-}
-}  // namespace
-
-PeriodicGeometry periodic_geometry(uint64_t num, uint64_t den, uint32_t taps, uint32_t channels,
-                                   bool allow_matrix, bool allow_split) {
-    int knob = mfma_knob();
-    if (knob == 3) {   // split-bf16 matrix kernel where its geometry exists
-        if (allow_matrix && allow_split) {
-            const PeriodicGeometry g = split_geometry(num, den, taps, channels);
-            if (g.ok) return g;
-        }
-        knob = 2;
-    }
-    if (allow_matrix && channels == 2 && (knob == 1 || knob == 2 || knob == 4)) {
-        const PeriodicGeometry g = geometry_for(num, den, taps, channels, true);
-        if (g.ok) return g;   // else: two images do not fit the LDS for this rate pair
-    }
-    return geometry_for(num, den, taps, channels, false);
-}
-
-bool periodic_supported(const FirMirror& m, size_t channels, size_t taps, int kernel_mode) {
-    if (kernel_mode == RSMP_FIR_KERNEL_GENERIC) return false;
-    if (!m.periodic_ok()) return false;
-    return periodic_geometry(m.num(), m.den(), static_cast<uint32_t>(taps), static_cast<uint32_t>(channels),
-                             kernel_mode != RSMP_FIR_KERNEL_PERIODIC_VECTOR,
-                             kernel_mode != RSMP_FIR_KERNEL_PERIODIC_F32).ok;
-}
-
-bool periodic_worthwhile(const FirMirror& planned, size_t produced_frames, int kernel_mode) {
-    if (kernel_mode == RSMP_FIR_KERNEL_PERIODIC || kernel_mode == RSMP_FIR_KERNEL_PERIODIC_VECTOR ||
-        kernel_mode == RSMP_FIR_KERNEL_PERIODIC_F32)
-        return produced_frames > 0;
-    // AUTO: a launch shorter than a few workgroup spans leaves most lanes idle.
-    (void)planned;
-    return produced_frames >= 16384;
-}
-
-uint32_t periodic_blocks(const PeriodicGeometry& geo, uint64_t abs_out, uint32_t n_out) {
-    if (n_out == 0) return 0;
-    const uint64_t q_first = abs_out / geo.b;
-    const uint64_t q_last = (abs_out + n_out - 1) / geo.b;
-    return static_cast<uint32_t>((q_last - q_first) / geo.pw + 1);
-}
-
-size_t periodic_wrap_words(uint64_t abs_out, uint32_t n_out, uint64_t den) {
-    if (n_out == 0) return 1;
-    const uint64_t k0 = abs_out / den, k1 = (abs_out + n_out - 1) / den;
-    return static_cast<size_t>((k1 - k0) / 32 + 1);
-}
-
-void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_out, uint64_t den,
-                             uint32_t* words, size_t n_words) {
-    std::memset(words, 0, n_words * sizeof(uint32_t));
-    const uint64_t k0 = abs_out / den;
-    for (uint32_t n : wraps) {
-        const uint64_t k = (abs_out + n) / den - k0;
-        words[k >> 5] |= 1u << (k & 31);
-    }
-}
-
-HostClassTable build_class_table(const std::vector<float>& coeffs, const PeriodicGeometry& g,
-                                 double drift) {
-    const uint32_t taps = g.taps;
-    const uint32_t ct = g.mfma ? kMfmaClassTile : kClassTile;
-    HostClassTable out;
-    out.coef.assign(g.mfma == 3 ? split_table_floats(g) : static_cast<size_t>(g.n_tiles) * g.row_len * ct, 0.0f);
-    out.wrap_coef.assign(static_cast<size_t>(g.n_tiles) * g.row_len, 0.0f);
-    out.meta.resize(g.n_tiles);
-    std::vector<float> mixed(taps);
-    const float* row1023 = coeffs.data() + (kPhases - 1) * taps;
-    for (uint32_t t = 0; t < g.n_tiles; ++t) {
-        TileMeta& tm = out.meta[t];
-        std::memset(&tm, 0, sizeof tm);
-        const uint32_t j0 = t * ct;
-        tm.base = class_offset(g, j0);
-        tm.wrap_col = -1;
-        tm.extra_col = -2;
-        float* base = out.coef.data() + static_cast<size_t>(t) * g.row_len * ct;
-        for (uint32_t i = 0; i < ct && j0 + i < g.b; ++i) {
-            const uint32_t j = j0 + i;
-            // exact fractional position of class j, plus the stream's current f64 drift
-            const uint64_t rem = (static_cast<uint64_t>(j) * g.a) % g.b;
-            double fract = static_cast<double>(rem) / static_cast<double>(g.b) + drift;
-            if (j % g.den == 0) fract = drift > 0.0 ? drift : 0.0;  // below-integer: wrap variant
-            if (fract < 0.0) fract = 0.0;
-            // resampler_fir.rs:562-565
-            double phase_f = fract * static_cast<double>(kPhases);
-            if (phase_f > static_cast<double>(kPhases - 1)) phase_f = static_cast<double>(kPhases - 1);
-            const size_t phase1 = static_cast<size_t>(phase_f);
-            const size_t phase2 = phase1 + 1 < kPhases - 1 ? phase1 + 1 : kPhases - 1;
-            const float frac = static_cast<float>(phase_f - static_cast<double>(phase1));
-            const float* c1 = coeffs.data() + phase1 * taps;
-            const float* c2 = coeffs.data() + phase2 * taps;
-            const float omf = 1.0f - frac;
-            for (uint32_t k = 0; k < taps; ++k) mixed[k] = c1[k] * omf + c2[k] * frac;  // avx.rs:41-45
-            const uint32_t shift = class_offset(g, j) - tm.base;
-            if (g.mfma == 3) {
-                split_store_class(out.coef, g, t, i, shift, mixed);
-                continue;
-            }
-            if (g.mfma) {
-                // A-operand order of v_mfma_f32_16x16x4_f32 (lane = 16 * (tap % 4) + class), four
-                // steps of a lane adjacent: [block = tap / 16][lane][step = (tap / 4) % 4]
-                for (uint32_t k = 0; k < taps; ++k) {
-                    const uint32_t m = k + shift;
-                    base[(m >> 4) * 256 + ((m & 3) * 16 + i) * 4 + ((m >> 2) & 3)] = mixed[k];
-                }
-                continue;
-            }
-            for (uint32_t k = 0; k < taps; ++k) base[(k + shift) * kClassTile + i] = mixed[k];
-
-            if (g.inline_wraps && j % g.den == 0) {
-                // wrap variant of class j: row 1023 on the window one frame earlier (:544, :562-564)
-                tm.wrap_col = static_cast<int32_t>(i);
-                tm.wrap_jd = j / g.den;
-                float* wc = out.wrap_coef.data() + static_cast<size_t>(t) * g.row_len;
-                const int64_t w = static_cast<int64_t>(class_offset(g, j)) - 1;
-                if (w >= static_cast<int64_t>(tm.base)) {
-                    const uint32_t ws = static_cast<uint32_t>(w - tm.base);
-                    for (uint32_t k = 0; k < taps; ++k) wc[k + ws] = row1023[k];
-                } else {  // one sample in front of the tile window
-                    for (uint32_t k = 1; k < taps; ++k) wc[k - 1] = row1023[k];
-                    tm.extra_col = static_cast<int32_t>(tm.base) - 1;
-                    tm.extra_coef = row1023[0];
-                }
-            }
-        }
-    }
-    return out;
-}
-
-int class_table_for(int device, const std::vector<float>& table, const PeriodicGeometry& g, double drift,
-                    ClassTable* out, const HostClassTable* prebuilt) {
-    ClassTableCache& cache = class_cache();
-    std::lock_guard<std::mutex> lock(cache.mu);
-    uint64_t bits;
-    std::memcpy(&bits, &drift, sizeof bits);
-    const ClassTableKey key{device, table.data(), g.den, g.a, g.b, g.row_len,
-                            g.mfma == 3 ? 8u + g.planes : (g.mfma ? 1u : 0u), bits};
-    auto it = cache.tables.find(key);
-    if (it == cache.tables.end()) {
-        purge_class_graveyard(device);
-        if (cache.tables.size() >= ClassTableCache::kMaxTables) {   // the least recently used one leaves (its holders keep it alive)
-            auto lru = cache.tables.begin();
-            for (auto e = cache.tables.begin(); e != cache.tables.end(); ++e)
-                if (e->second.used < lru->second.used) lru = e;
-            cache.tables.erase(lru);
-        }
-        const auto tb0 = std::chrono::steady_clock::now();
-        HostClassTable built;
-        if (!prebuilt) built = build_class_table(table, g, drift);   // (0.35-0.7 ms of host arithmetic; `prebuilt`: somebody did it ahead)
-        const HostClassTable& host = prebuilt ? *prebuilt : built;
-        const auto tb1 = std::chrono::steady_clock::now();
-        const size_t coef_bytes = host.coef.size() * sizeof(float);
-        const size_t wrap_bytes = host.wrap_coef.size() * sizeof(float);
-        const size_t meta_bytes = host.meta.size() * sizeof(TileMeta);
-        char* dptr = nullptr;
-        RSMP_HIP_CHECK(hipMalloc(&dptr, coef_bytes + wrap_bytes + meta_bytes));
-        RSMP_HIP_CHECK(hipMemcpy(dptr, host.coef.data(), coef_bytes, hipMemcpyHostToDevice));
-        RSMP_HIP_CHECK(hipMemcpy(dptr + coef_bytes, host.wrap_coef.data(), wrap_bytes,
-                                 hipMemcpyHostToDevice));
-        RSMP_HIP_CHECK(hipMemcpy(dptr + coef_bytes + wrap_bytes, host.meta.data(), meta_bytes,
-                                 hipMemcpyHostToDevice));
-        ClassTable ct;
-        ct.d_coef = reinterpret_cast<const float*>(dptr);
-        ct.d_wrap_coef = reinterpret_cast<const float*>(dptr + coef_bytes);
-        ct.d_meta = reinterpret_cast<const TileMeta*>(dptr + coef_bytes + wrap_bytes);
-        ct.hold = std::shared_ptr<void>(dptr, [device](void* p) {
-            ClassTableGraveyard& gy = class_graveyard();
-            std::lock_guard<std::mutex> lock(gy.mu);
-            gy.dead.emplace_back(device, p);
-        });
-        it = cache.tables.emplace(key, ClassTableCache::Entry{ct, 0}).first;
-        static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
-        if (verbose)
-            fprintf(stderr, "[rsmp] class table a=%u b=%u drift %.3g: built in %.3f ms on the host, %zu KB allocated and uploaded in %.3f ms\n", g.a, g.b, drift,
-                    std::chrono::duration<double, std::milli>(tb1 - tb0).count(), (coef_bytes + wrap_bytes + meta_bytes) >> 10,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb1).count());
-    }
-    it->second.used = ++cache.tick;
-    *out = it->second.ct;
-    return RSMP_OK;
-}
-
-int periodic_bind(PeriodicState& st, int device, const std::vector<float>& table, int kernel_mode,
-                  const FirMirror& planned, double launch_drift, uint32_t channels, hipStream_t stream) {
-    (void)stream;
-    const bool allow_matrix = kernel_mode != RSMP_FIR_KERNEL_PERIODIC_VECTOR;
-    if (!st.geo_valid || st.geo_mode != kernel_mode) {   // (rsmp_fir_set_kernel may switch between them)
-        st.geo = periodic_geometry(planned.num(), planned.den(), static_cast<uint32_t>(planned.taps()),
-                                   channels, allow_matrix, kernel_mode != RSMP_FIR_KERNEL_PERIODIC_F32);
-        st.geo_valid = true;
-        st.geo_mode = kernel_mode;
-        st.table_valid = false;
-    }
-    if (!st.geo.ok) return fail(RSMP_ERR_INVALID_ARGUMENT, "periodic kernel: unsupported geometry");
-    const double drift = std::round(launch_drift / kDriftQuantum) * kDriftQuantum;
-    if (st.table_valid && drift == st.table_drift) return RSMP_OK;
-    ClassTable ct;
-    const int rc = class_table_for(device, table, st.geo, drift, &ct);
-    if (rc != RSMP_OK) return rc;
-    st.table = ct;
-    st.table_valid = true;
-    st.table_drift = drift;
-    return RSMP_OK;
-}
 
 hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
                                const PeriodicGeometry& geo, uint32_t max_blocks,
                                unsigned long long* d_work_counter, const NfArgs& nf, hipStream_t stream,
                                bool fuse_tail, uint64_t items_key, uint32_t pcm_bits) {
     if (n_streams == 0 || max_blocks == 0) return hipSuccess;
-    const dim3 block(geo.waves * 64);
-    GeoArgs args = to_args(geo);
-    args.blocks_per_stream = max_blocks;
-    args.total_items = max_blocks * n_streams;
     int device = 0;
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess) return e;
-    static std::map<int, uint32_t> cu_count;
-    static std::mutex cu_mu;
-    uint32_t cus;
-    {
-        std::lock_guard<std::mutex> lock(cu_mu);
-        uint32_t& c = cu_count[device];
-        if (c == 0) {
-            int v = 0;
-            e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device);
-            if (e != hipSuccess) return e;
-            c = static_cast<uint32_t>(v > 0 ? v : 256);
-        }
-        cus = c;
-    }
+    const uint32_t cus = device_cus(device);
     if (geo.mfma == 3) return launch_fir_split(d_descs, n_streams, geo, max_blocks, cus, fuse_tail, nf, stream, items_key, pcm_bits);
     if (pcm_bits != 0) return hipErrorNotSupported;
-    args.nf = nf;
-    const uint32_t slots = cus * (geo.lds_bytes > kLdsTwoPerCu ? 1u : 2u);   // workgroups that fit
-    const dim3 grid(args.total_items < slots ? args.total_items : slots);
-    args.work_counter = d_work_counter;
-    // every claiming wave makes exactly one failing claim: one wave per workgroup claims (the kernel's
-    // mode in which every producer owns an image and claims for itself needs producers == images, and
-    // geometry_for() gives 4 producers for 2 images)
-    args.n_claimers = grid.x;
-    static const char* trace_path = rsmp::knob("RSMP_FIR_TRACE");
-    static unsigned long long* d_trace = nullptr;
-    const size_t trace_words = 6ull * grid.x;
-    if (trace_path) {
-        if (d_trace) (void)hipFree(d_trace);
-        if (hipMalloc(&d_trace, trace_words * 8) != hipSuccess) return hipErrorOutOfMemory;
-        (void)hipMemset(d_trace, 0, trace_words * 8);
-        args.trace = d_trace;
-    }
-    static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
-    static unsigned long long* d_wtrace = nullptr;
-    const size_t wtrace_words = static_cast<size_t>(grid.x) * kWtraceWaves * kWtraceSlots;
-    if (wtrace_path) {
-        if (d_wtrace) (void)hipFree(d_wtrace);
-        if (hipMalloc(&d_wtrace, wtrace_words * 8) != hipSuccess) return hipErrorOutOfMemory;
-        (void)hipMemset(d_wtrace, 0, wtrace_words * 8);
-        args.wtrace = d_wtrace;
-    }
-    // Dynamic LDS above 64 KiB must be opted into, once per kernel and device.
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, bool> granted;
-    // Slots of the kernel table below.  0..2 = vector kernel: two channels with one lane per period / CG 2,
-    // any even channel count / CG 1.  (4-tap chunks with 16-wave workgroups at 8 waves per SIMD measured
-    // 13 % slower than 8-tap chunks: the 64-VGPR cap spills.)  Matrix-core consumers: 3 / 4 = coefficient
-    // ring (any window length), 2 / 4 period groups per unit; 5..7 = ring timing experiments
-    // (RSMP_FIR_MFMA_DBG 1..3); 8..13 = coefficient tile in registers, 2 groups per unit, windows of
-    // 48 / 96 / 144 taps, padded (8..10) or back-to-back (11..13) rows; 14..19 = the same with 1 group.
+    // the build: a slot of the table (periodic_slot_for, fir_geometry.cpp), in its plain or its diagnostic row
     static const int mfma_dbg = [] {   // RSMP_FIR_MFMA_DBG: 1 hot coefficient line, 2 no LDS reads, 3 both
         const char* e = rsmp::knob("RSMP_FIR_MFMA_DBG");
         const int v = e ? atoi(e) : 0;
         return v >= 0 && v <= 3 ? v : 0;
     }();
-    static const bool mfma_ring = rsmp::knob("RSMP_FIR_MFMA_RING") != nullptr;   // force the ring variant
-    const uint32_t nb3 = geo.row_len % 48 == 0 && geo.row_len <= 144 ? geo.row_len / 48 : 0;   // 0..3
-    const bool flat_rows = geo.row_stride == 2 * geo.a;
-    int variant;
-    if (!geo.mfma) variant = geo.cg == 2 ? (geo.lp == 1 ? 0 : 1) : 2;
-    else if (geo.mfma == 4) variant = 4;
-    else if (geo.mfma == 1 && (!nb3 || mfma_ring)) return hipErrorInvalidValue;   // G = 1 exists only register-resident
-    else if (mfma_dbg) variant = 4 + mfma_dbg;
-    else if (nb3 && !mfma_ring) variant = (geo.mfma == 1 ? 13 : 7) + static_cast<int>(nb3) + (flat_rows ? 3 : 0);
-    else variant = 3;
-    static const char* trace_env = rsmp::knob("RSMP_FIR_TRACE");
-    static const char* wtrace_env = rsmp::knob("RSMP_FIR_WTRACE");
-    const bool diag = args.debug != 0 || trace_env != nullptr || wtrace_env != nullptr;
+    static const char* trace_path = rsmp::knob("RSMP_FIR_TRACE");
+    static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
+    GeoArgs args = to_args(geo);
+    const bool diag = args.debug != 0 || trace_path != nullptr || wtrace_path != nullptr;
+    const int slot = periodic_slot_for(geo, mfma_dbg, mfma_ring_knob());
+    if (slot < 0) return hipErrorInvalidValue;
 #define RSMP_SK(cg, c2, D) reinterpret_cast<const void*>(fir_periodic_kernel<cg, c2, 8, D>)
 #define RSMP_DB(cg, c2, mf, D) reinterpret_cast<const void*>(fir_periodic_db_kernel<cg, c2, 8, mf, D>)
 #define RSMP_MF(nb3v, flatv, D) RSMP_DB(2, true, 2 + 64 * (nb3v) + 512 * (flatv), D)
@@ -2154,27 +1692,41 @@ hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
      RSMP_DB(2, true, 2 + 16, D), RSMP_DB(2, true, 2 + 32, D), RSMP_DB(2, true, 2 + 48, D), RSMP_MF(1, 0, D),          \
      RSMP_MF(2, 0, D), RSMP_MF(3, 0, D), RSMP_MF(1, 1, D), RSMP_MF(2, 1, D), RSMP_MF(3, 1, D), RSMP_MF1(1, 0, D),      \
      RSMP_MF1(2, 0, D), RSMP_MF1(3, 0, D), RSMP_MF1(1, 1, D), RSMP_MF1(2, 1, D), RSMP_MF1(3, 1, D)}
-    static const void* const fns_all[2][20] = {RSMP_FNS(false), RSMP_FNS(true)};
-    const void* const* fns = fns_all[diag ? 1 : 0];
+    static const void* const fns_all[2][kPeriodicSlots] = {RSMP_FNS(false), RSMP_FNS(true)};
 #undef RSMP_FNS
 #undef RSMP_SK
 #undef RSMP_DB
 #undef RSMP_MF
 #undef RSMP_MF1
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        bool& have = granted[{device, variant * 2 + (diag ? 1 : 0)}];
-        if (!have) {
-            e = hipFuncSetAttribute(fns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-            if (e != hipSuccess) return e;
-            have = true;
-        }
+    const void* const fn = fns_all[diag ? 1 : 0][slot];
+    if ((e = grant_dynamic_lds(device, fn, kLdsMax)) != hipSuccess) return e;
+
+    const dim3 block(geo.waves * 64);
+    args.blocks_per_stream = max_blocks;
+    args.total_items = max_blocks * n_streams;
+    args.nf = nf;
+    const uint32_t slots = cus * (geo.lds_bytes > kLdsTwoPerCu ? 1u : 2u);   // workgroups that fit
+    const dim3 grid(args.total_items < slots ? args.total_items : slots);
+    args.work_counter = d_work_counter;
+    // every claiming wave makes exactly one failing claim: one wave per workgroup claims (the kernel's
+    // mode in which every producer owns an image and claims for itself needs producers == images, and
+    // geometry_for() gives 4 producers for 2 images)
+    args.n_claimers = grid.x;
+    static TraceBuffer trace, wtrace;
+    if (trace_path) {
+        if ((e = trace.renew(6ull * grid.x)) != hipSuccess) return e;
+        (void)hipMemset(trace.d, 0, trace.words * 8);
+        args.trace = trace.d;
+    }
+    if (wtrace_path) {
+        if ((e = wtrace.renew(static_cast<size_t>(grid.x) * kWtraceWaves * kWtraceSlots)) != hipSuccess) return e;
+        (void)hipMemset(wtrace.d, 0, wtrace.words * 8);
+        args.wtrace = wtrace.d;
     }
     static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
     if (verbose) {
         int blocks = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fns[variant], geo.waves * 64,
-                                                           geo.lds_bytes);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, geo.waves * 64, geo.lds_bytes);
         fprintf(stderr,
                 "[rsmp] periodic launch: a=%u b=%u row_len=%u tiles=%u cg=%u lp=%u pw=%u stride=%u "
                 "waves=%u lds=%u items=%u grid=%u occupancy=%d blocks/CU\n",
@@ -2182,33 +1734,23 @@ hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
                 geo.waves, geo.lds_bytes, args.total_items, grid.x, blocks);
     }
     void* kargs[2] = {&d_descs, &args};
-    e = hipLaunchKernel(fns[variant], grid, block, kargs, geo.lds_bytes, stream);
+    e = hipLaunchKernel(fn, grid, block, kargs, geo.lds_bytes, stream);
     if (e != hipSuccess) return e;
-    if (trace_path) {
-        (void)hipStreamSynchronize(stream);
-        std::vector<unsigned long long> h(trace_words);
-        (void)hipMemcpy(h.data(), d_trace, trace_words * 8, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(trace_path, "w")) {
-            for (size_t i = 0; i < trace_words / 6; ++i)
+    if (trace_path)
+        trace.dump(trace_path, stream, [](FILE* f, const std::vector<unsigned long long>& h) {
+            for (size_t i = 0; i < h.size() / 6; ++i)
                 fprintf(f, "%zu %llu %llu %llu %llu %llu %llu\n", i, h[6 * i], h[6 * i + 1], h[6 * i + 2],
                         h[6 * i + 3], h[6 * i + 4], h[6 * i + 5]);
-            fclose(f);
-        }
-    }
-    if (wtrace_path) {   // one line per wave: block wave event...
-        (void)hipStreamSynchronize(stream);
-        std::vector<unsigned long long> h(wtrace_words);
-        (void)hipMemcpy(h.data(), d_wtrace, wtrace_words * 8, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(wtrace_path, "w")) {
-            for (size_t w = 0; w < wtrace_words / kWtraceSlots; ++w) {
+        });
+    if (wtrace_path)   // one line per wave: block wave event...
+        wtrace.dump(wtrace_path, stream, [](FILE* f, const std::vector<unsigned long long>& h) {
+            for (size_t w = 0; w < h.size() / kWtraceSlots; ++w) {
                 fprintf(f, "%zu %zu", w / kWtraceWaves, w % kWtraceWaves);
                 for (uint32_t i = 0; i < kWtraceSlots && h[w * kWtraceSlots + i]; ++i)
                     fprintf(f, " %llu:%llu", h[w * kWtraceSlots + i] >> 8, h[w * kWtraceSlots + i] & 255);
                 fprintf(f, "\n");
             }
-            fclose(f);
-        }
-    }
+        });
     return hipGetLastError();
 }
 

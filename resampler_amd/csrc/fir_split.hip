@@ -40,27 +40,18 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <map>
-#include <type_traits>
 #include <vector>
 #include <mutex>
 
 #include "common.h"
+#include "fir_kernel_launch.h"
+#include "fir_split_consts.h"
 
 namespace rsmp {
 
 namespace {
 
-constexpr uint32_t kProducers = 6, kConsumers = 10, kWaves = 16;   // five stagers + one wrap-only producer
-constexpr uint32_t kCtrlBytes = 256;                 // staged[2], done[2]
-constexpr uint32_t kWrapBytes = 4 * 16 * 16;         // up to four slots x 16 periods x (ch0, ch1, take, -)
-constexpr uint32_t kTouchBytes = 3 * 256;              // landing zone of the consumers' L2 prefetch touches
-constexpr uint32_t kImageBase = kCtrlBytes + kWrapBytes + kTouchBytes;
-// An image row: per channel and plane one 32-byte plane row (16 periods x 16 bits), + 32 bytes of padding.
-// In 32-byte units the stride is 7 (three bf16 planes) or 5 (two fp16 planes): odd, so the eight rows a
-// transposed read touches per 32 lanes fall on distinct bank groups (64 banks x 4 B = 8 units).
-__host__ __device__ constexpr uint32_t row_bytes(int planes) { return planes == 3 ? 7u * 32u : 5u * 32u; }
 // Two-plane split: the operands are scaled by powers of two before they are cut into fp16 planes, so that
 // samples down to 2^-26 and taps down to 2^-27 keep their full relative precision (fp16 normals start at
 // 2^-14); samples of magnitude >= 16 overflow to infinity there -- the launch's non-finite check then has
@@ -69,14 +60,10 @@ constexpr float kXScale = 4096.0f;        // 2^12 (the sample scale of an item w
 constexpr uint32_t kPeakHeadroom = 4;     // a predicted scale leaves 2^4 above the pair's latest peak
 constexpr uint32_t kPeakQuiet = 10;       // an item whose peak lies more than 2^-10 below what its scale allows (2^-6 below the prediction) is redone
 constexpr uint32_t kPeakMax = 138;        // no scale is derived from a peak of 2^11 and above (samples of 2^13 and above overflow the planes: redone)
-constexpr float kCScale = 8192.0f;        // 2^13
 constexpr uint32_t kTouchAhead = 3;                    // items between a touch and the producers' loads of the same frames
-constexpr uint32_t kLdsLimit = 160 * 1024;
 #ifndef RSMP_POLL_SLEEP
 #define RSMP_POLL_SLEEP 1   // s_sleep units (64 cycles) between two polls of an LDS counter
 #endif
-constexpr int kWrapTaps = 8;                         // taps of the wrap variant per lane (16 lanes per period)
-constexpr uint32_t kStagers = 5;                          // (row block, period pair) combos in flight per producer
 
 struct SplitArgs {
     uint32_t a, b, taps, n_tiles, rows, slots, lds_bytes, blocks_per_stream, total_items, debug;
@@ -229,7 +216,6 @@ struct Item {
 // item): every one of a workgroup's sixteen waves walks the same items, and deriving an item from its index -- stream,
 // block, pair, tile group, period, output and frame offsets, whether its frames lie inside the input -- was several
 // hundred cycles of scalar 64-bit arithmetic per wave and item (round 2's phase clocks: "find next" / "next item").
-constexpr uint32_t kItemWords = 8;   // stream | flags << 24, pair | group << 8, n_block0, k_block0, f0 (2), off0, -
 constexpr uint32_t kItemValid = 1, kItemInterior = 2;
 struct Cursor {
     uint32_t item;                  // the next item to look at
@@ -320,7 +306,6 @@ __global__ __launch_bounds__(256) void split_items_kernel(const FirStreamDesc* _
 // the jobs in proportion to their work; a workgroup finds its job from its index and is then exactly the workgroup
 // `wg` of `n_wgs` of a launch of that job alone.  (A run of config 4 is six rate pairs: six launches of this kernel, of
 // the item kernel in front and of the repair kernel behind cost a run of 16 calls more than the work itself.)
-constexpr uint32_t kMaxSplitJobs = 8;
 struct SplitMulti {
     SplitArgs g[kMaxSplitJobs];
     const FirStreamDesc* descs[kMaxSplitJobs];
@@ -1599,7 +1584,6 @@ __global__ __launch_bounds__(1024) void fir_split_multi_kernel(const SplitMulti 
 // fir_split_multi_kernel and runs the body of the job's build.  One launch per run instead of three: the two-round builds'
 // jobs are a quarter of the batch, alone they do not fill the chip (a 128-stream shard: 99 + 38 + 34 us one after the
 // other, each with its own ramp-up and tail), side by side they end with the one-round jobs.
-constexpr uint32_t kSplitBuild5x1 = 0, kSplitBuild5x2 = 1, kSplitBuild6x2 = 2;
 __global__ __launch_bounds__(1024) void fir_split_all_kernel(const SplitMulti m) {
     uint32_t begin;
     const uint32_t j = __builtin_amdgcn_readfirstlane(split_job_of(m.wg_end, m.n_jobs, blockIdx.x, begin));
@@ -1610,153 +1594,7 @@ __global__ __launch_bounds__(1024) void fir_split_all_kernel(const SplitMulti m)
     else fir_split_body<6, 2, false, 0, 2>(m.descs[j], m.g[j], blockIdx.x - begin, m.wg_end[j] - begin);
 }
 
-inline uint32_t split_class_offset(uint32_t a, uint32_t b, uint32_t j) {
-    return static_cast<uint32_t>((static_cast<uint64_t>(j) * a) / b);
-}
-
 }  // namespace
-
-// Geometry of the split kernel for num/den, or !ok.  A super period of a = r num input frames and b = r den outputs:
-// r = 1 for 16 .. 320 classes; a ratio with a power-of-two denominator below 16 (48 <-> 96 kHz: exact in f64, so no
-// output ever takes the row-1023 variant and every class of the super period is an ordinary one) takes the largest r
-// with a, b <= 320.  Up to ten class tiles per tile group (one tile per consumer wave), up to two groups; periods of up
-// to 160 frames in one round of lane tasks, up to 320 in two (two-channel streams); window of <= 160 taps (192 with
-// two rounds); two to four images within the LDS.
-// RSMP_FIR_SPLIT_PLANES = 3 selects the three-plane bf16 split (every f32 operand exactly), default 2: two
-// fp16 planes per operand, three matrix products instead of six.
-static uint32_t split_planes_knob() {
-    static const uint32_t v = [] {
-        const char* e = rsmp::knob("RSMP_FIR_SPLIT_PLANES");
-        return e && atoi(e) == 3 ? 3u : 2u;
-    }();
-    return v;
-}
-
-PeriodicGeometry split_geometry(uint64_t num, uint64_t den, uint32_t taps, uint32_t channels) {
-    PeriodicGeometry g;
-    // (three planes: the two-channel kernel only -- the channel-pair, one-channel and odd-count builds keep two)
-    const uint32_t planes = channels == 2 ? split_planes_knob() : 2u;
-    const uint32_t kRowBytes = row_bytes(static_cast<int>(planes));
-    // two channels, or (RSMP_FIR_SPLIT_WIDE=0 turns it off) an even number up to 16 taken as channel pairs, two pairs per
-    // 16-byte load (6, 10, 14 channels: the last pair alone -- its load reaches 8 bytes into the next frame)
-    static const bool wide_ok = [] { const char* e = rsmp::knob("RSMP_FIR_SPLIT_WIDE"); return !e || atoi(e) != 0; }();
-    static const bool long_ok = [] { const char* e = rsmp::knob("RSMP_FIR_SPLIT_LONG"); return !e || atoi(e) != 0; }();   // 0: round 2's geometries only
-    if (channels != 2 && (channels > 16 || !wide_ok)) return g;
-    constexpr uint32_t kMaxAB = 320;
-    if (num == 0 || den == 0 || num > kMaxAB || den > kMaxAB) return g;
-    uint32_t r = 1;
-    if (den < 16) {
-        if ((den & (den - 1)) != 0) return g;   // (the wrap variant exists for class 0 only: exact ratios need none)
-        r = static_cast<uint32_t>(std::min(kMaxAB / num, kMaxAB / den));
-        r -= r % (16 / static_cast<uint32_t>(den));   // whole tiles
-        if (r == 0) return g;
-    }
-    const uint32_t a = static_cast<uint32_t>(num) * r, b = static_cast<uint32_t>(den) * r;
-    if (b < 16) return g;
-    const uint32_t n_tiles = (b + 15) / 16;
-    const uint32_t groups = (n_tiles + kConsumers - 1) / kConsumers;
-    const uint32_t rounds = 4 * ((a + 1) / 2) > 64 * kStagers ? 2u : 1u;
-    if (!long_ok && (groups > 1 || rounds > 1 || r > 1)) return g;
-    if (groups > 2 || (rounds == 2 && (channels % 2 != 0 || planes != 2))) return g;   // (two rounds: channel pairs, fp16 planes)
-    uint32_t shift = 0, ob_max = 0;
-    for (uint32_t t = 0; t < n_tiles; ++t) {
-        const uint32_t ob = split_class_offset(a, b, 16 * t);
-        if (ob > ob_max) ob_max = ob;
-        for (uint32_t i = 0; i < 16 && 16 * t + i < b; ++i) {
-            const uint32_t s = split_class_offset(a, b, 16 * t + i) - ob;
-            if (s > shift) shift = s;
-        }
-    }
-    const uint32_t kpad = (taps + shift + 31) / 32 * 32;
-    if (kpad / 32 < 1 || kpad / 32 > (rounds == 2 ? 6u : 5u) || taps > 16 * kWrapTaps) return g;
-    if (rounds == 2 && kpad / 32 < 5) return g;   // (the two-round kernels exist for windows of 160 and 192 taps: 128-tap filters)
-    // Rows a plane really needs: the last tile's window ends at ob_max + taps + shift.  The MFMA steps read
-    // on to ob_max + kpad with zero coefficients -- into the rows that follow in LDS (the next plane, the next
-    // image, the pad after the last image: always finite values, the whole LDS is zeroed at the start).
-    const uint32_t rows = ob_max + taps + shift;
-    if (4 * ((a + 1) / 2) > 64 * kStagers * rounds || rows < a || rows > 2 * a) return g;   // (rows beyond a repeat the next period)
-    const uint32_t pad = (kpad - (taps + shift)) * kRowBytes;
-    uint32_t slots = (kLdsLimit - kImageBase - pad) / (rows * kRowBytes);   // ring of images: slack between producers and consumers
-    if (slots > 4) slots = 4;
-    if (slots < 2) return g;
-    const uint32_t lds = kImageBase + slots * rows * kRowBytes + pad;
-    g.a = a;
-    g.b = b;
-    g.den = static_cast<uint32_t>(den);   // the true period of the phase pattern (b = r den)
-    g.taps = taps;
-    g.row_len = kpad;
-    g.n_tiles = n_tiles;
-    g.n_units = n_tiles;
-    g.cg = channels == 1 ? 1 : (channels % 2 ? 3 : 2);   // (1: one channel, a pair with a phantom second channel; 3: odd count, the last pair likewise)
-    g.lp = (channels + 1) / 2;      // channel pairs of a frame (an item of the launch = one pair of a block)
-    g.pw = 16;
-    g.row_stride = rows;       // rows of an image (frames of a period + window reach)
-    g.waves = kWaves;
-    g.producers = kProducers;
-    g.images = slots;
-    g.mfma = 3;
-    g.planes = planes;
-    g.groups = groups;
-    g.rounds = rounds;
-    g.lds_bytes = lds;
-    g.inline_wraps = true;
-    g.ok = true;
-    return g;
-}
-
-// Class-table image for the split kernel: [tile][k step][plane][lane][8 x 16 bit]; lane (class m =
-// lane & 15, k group = lane >> 4) element j holds window position 32 s + 16 (j >> 2) + 4 (lane >> 4) +
-// (j & 3) -- the order in which the transposed LDS reads deliver the frames.  Three planes: bf16 by
-// truncation (c == p1 + p2 + p3 exactly); two planes: fp16, round to nearest, of 2^13 c.
-void split_store_class(std::vector<float>& coef, const PeriodicGeometry& g, uint32_t tile, uint32_t m,
-                       uint32_t shift, const std::vector<float>& mixed) {
-    const uint32_t nk = g.row_len / 32;
-    const uint32_t planes = g.planes;
-    uint32_t* words = reinterpret_cast<uint32_t*>(coef.data());
-    for (uint32_t s = 0; s < nk; ++s)
-        for (uint32_t grp = 0; grp < 4; ++grp)
-            for (uint32_t j = 0; j < 8; ++j) {
-                const uint32_t pos = 32 * s + 16 * (j >> 2) + 4 * grp + (j & 3);
-                float c = 0.f;
-                if (pos >= shift && pos - shift < g.taps) c = mixed[pos - shift];
-                uint32_t p[3] = {0, 0, 0};
-                if (planes == 3) {
-                    uint32_t u;
-                    std::memcpy(&u, &c, 4);
-                    p[0] = u >> 16;
-                    float h;
-                    uint32_t hu = u & 0xFFFF0000u;
-                    std::memcpy(&h, &hu, 4);
-                    const float r1 = c - h;
-                    std::memcpy(&u, &r1, 4);
-                    p[1] = u >> 16;
-                    hu = u & 0xFFFF0000u;
-                    std::memcpy(&h, &hu, 4);
-                    const float r2 = r1 - h;
-                    std::memcpy(&u, &r2, 4);
-                    p[2] = u >> 16;
-                } else {
-                    const float sc = c * kCScale;
-                    const _Float16 h1 = static_cast<_Float16>(sc);
-                    const _Float16 h2 = static_cast<_Float16>(sc - static_cast<float>(h1));
-                    uint16_t b1, b2;
-                    std::memcpy(&b1, &h1, 2);
-                    std::memcpy(&b2, &h2, 2);
-                    p[0] = b1;
-                    p[1] = b2;
-                }
-                const uint32_t lane = 16 * grp + m;
-                for (uint32_t pl = 0; pl < planes; ++pl) {
-                    const size_t dword = ((((static_cast<size_t>(tile) * nk + s) * planes + pl) * 64 + lane) * 4) + (j >> 1);
-                    const uint32_t sh = (j & 1) * 16;
-                    words[dword] = (words[dword] & ~(0xFFFFu << sh)) | (p[pl] << sh);
-                }
-            }
-}
-
-size_t split_table_floats(const PeriodicGeometry& g) {
-    return static_cast<size_t>(g.n_tiles) * (g.row_len / 32) * g.planes * 64 * 4;
-}
 
 // The item tables' workspaces, one per (device, stream) that has launched the split kernel.
 namespace {
@@ -1779,13 +1617,6 @@ void split_release_stream(int device, hipStream_t stream) {
 }
 
 namespace {
-uint32_t split_debug_knob() {
-    static const uint32_t debug = [] {
-        const char* e = rsmp::knob("RSMP_FIR_DEBUG");
-        return e ? static_cast<uint32_t>(atoi(e)) : 0u;
-    }();
-    return debug;
-}
 // The kernel's arguments for the streams of one geometry (everything but the item table's address).
 SplitArgs make_split_args(const PeriodicGeometry& geo, uint32_t n_streams, uint32_t max_blocks, bool fuse_tail, const NfArgs& nf) {
     const uint32_t pairs = geo.lp;
@@ -1795,7 +1626,7 @@ SplitArgs make_split_args(const PeriodicGeometry& geo, uint32_t n_streams, uint3
     const uint32_t qpairs = pairs / quads;
     const uint32_t groups = geo.groups ? geo.groups : 1u, per_group = max_blocks * n_streams * qpairs;
     return SplitArgs{geo.a, geo.b, geo.taps, geo.n_tiles, geo.row_stride, geo.images, geo.lds_bytes, max_blocks, per_group * groups * quads,
-                     split_debug_knob(), n_streams, fuse_tail ? 1u : 0u, geo.cg == 1 ? 1u : (geo.cg == 3 ? 2 * pairs - 1 : 2 * pairs), pairs,
+                     fir_debug_knob(), n_streams, fuse_tail ? 1u : 0u, geo.cg == 1 ? 1u : (geo.cg == 3 ? 2 * pairs - 1 : 2 * pairs), pairs,
                      groups, per_group, quads, qpairs, wide ? 1u : 0u,
                      // (b = r den with r > 1: a super period of an exact ratio.  WIDE builds only: the two-channel tile-group
                      // kernel got SLOWER without the fetches -- 2 ch 48 -> 96 kHz 0.59 -> 0.66 ms)
@@ -1825,105 +1656,59 @@ hipError_t items_workspace(int device, hipStream_t stream, size_t need, uint64_t
     slot.items = items;
     return hipSuccess;
 }
-uint32_t device_cus(int device) {
-    static std::mutex mu;
-    static std::map<int, uint32_t> count;
-    std::lock_guard<std::mutex> lock(mu);
-    uint32_t& c = count[device];
-    if (c == 0) {
-        int v = 0;
-        (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device);
-        c = static_cast<uint32_t>(v > 0 ? v : 256);
-    }
-    return c;
+}  // namespace
+
+// Every instantiation of fir_split_kernel, by its template arguments (split_build_for, fir_geometry.cpp, names the one a
+// geometry runs on).
+namespace {
+const void* split_kernel_for(const SplitBuild& build) {
+#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
+#define RSMP_SPLIT_1TO5(P, D, W) RSMP_SPLIT(1, P, D, W, 1, 0), RSMP_SPLIT(2, P, D, W, 1, 0), RSMP_SPLIT(3, P, D, W, 1, 0), RSMP_SPLIT(4, P, D, W, 1, 0), RSMP_SPLIT(5, P, D, W, 1, 0)
+#define RSMP_SPLIT_PCM(B) RSMP_SPLIT(5, 2, false, 0, 1, B), RSMP_SPLIT(5, 2, false, 0, 2, B), RSMP_SPLIT(6, 2, false, 0, 2, B)
+    static const struct { SplitBuild build; const void* fn; } table[] = {
+        // two channels: two or three planes, plain and diagnostic
+        RSMP_SPLIT_1TO5(2, false, 0), RSMP_SPLIT_1TO5(2, true, 0), RSMP_SPLIT_1TO5(3, false, 0), RSMP_SPLIT_1TO5(3, true, 0),
+        // channel pairs, one channel, an odd channel count (no diagnostic build; two planes only)
+        RSMP_SPLIT_1TO5(2, false, 1), RSMP_SPLIT_1TO5(2, false, 2), RSMP_SPLIT_1TO5(2, false, 3),
+        // two rounds of lane tasks (periods of 161 .. 320 frames): windows of 5 or 6 steps
+        RSMP_SPLIT(5, 2, false, 0, 2, 0), RSMP_SPLIT(6, 2, false, 0, 2, 0), RSMP_SPLIT(5, 2, false, 1, 2, 0), RSMP_SPLIT(6, 2, false, 1, 2, 0),
+        // (diagnostic builds: config 5's geometry, the 192-tap window; config 4's two-channel streams)
+        RSMP_SPLIT(5, 2, true, 0, 2, 0), RSMP_SPLIT(6, 2, true, 0, 2, 0), RSMP_SPLIT(6, 2, true, 1, 2, 0),
+        // PCM input: the two-channel fp16 builds of the 128-tap windows
+        RSMP_SPLIT_PCM(16), RSMP_SPLIT_PCM(24), RSMP_SPLIT_PCM(32)};
+#undef RSMP_SPLIT_PCM
+#undef RSMP_SPLIT_1TO5
+#undef RSMP_SPLIT
+    for (const auto& e : table)
+        if (e.build == build) return e.fn;
+    return nullptr;
 }
 }  // namespace
 
 hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, const PeriodicGeometry& geo,
                             uint32_t max_blocks, uint32_t cus, bool fuse_tail, const NfArgs& nf, hipStream_t stream,
                             uint64_t items_key, uint32_t pcm_bits) {
-    const uint32_t debug = split_debug_knob();
-    const uint32_t pairs = geo.lp;
-    const bool wide = pairs > 1 || geo.cg == 1;
-    SplitArgs args = make_split_args(geo, n_streams, max_blocks, fuse_tail, nf);
-    const uint32_t groups = args.groups;
     static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
-    const bool diag = debug != 0 || wtrace_path != nullptr;
-#define RSMP_SPLIT_FNS(P, D, W)                                                                              \
-    {reinterpret_cast<const void*>(fir_split_kernel<1, P, D, W>), reinterpret_cast<const void*>(fir_split_kernel<2, P, D, W>), \
-     reinterpret_cast<const void*>(fir_split_kernel<3, P, D, W>), reinterpret_cast<const void*>(fir_split_kernel<4, P, D, W>), \
-     reinterpret_cast<const void*>(fir_split_kernel<5, P, D, W>)}
-    static const void* const fns_all[2][2][5] = {{RSMP_SPLIT_FNS(2, false, 0), RSMP_SPLIT_FNS(2, true, 0)},
-                                                 {RSMP_SPLIT_FNS(3, false, 0), RSMP_SPLIT_FNS(3, true, 0)}};
-    static const void* const fns_wide[1][5] = {RSMP_SPLIT_FNS(2, false, 1)};   // (no diagnostic build; two planes only)
-    static const void* const fns_mono[1][5] = {RSMP_SPLIT_FNS(2, false, 2)};
-    static const void* const fns_odd[1][5] = {RSMP_SPLIT_FNS(2, false, 3)};
-#undef RSMP_SPLIT_FNS
-    const bool one_channel = geo.cg == 1;
-    const bool odd_count = geo.cg == 3;
-    // two rounds of lane tasks (periods of 161 .. 320 frames): two-channel fp16 kernel, windows of 5 or 6 steps
-    static const void* const fns_long[4][6] = {{nullptr, nullptr, nullptr, nullptr,
-                                                reinterpret_cast<const void*>(fir_split_kernel<5, 2, false, 0, 2>),
-                                                reinterpret_cast<const void*>(fir_split_kernel<6, 2, false, 0, 2>)},
-                                               {nullptr, nullptr, nullptr, nullptr,
-                                                reinterpret_cast<const void*>(fir_split_kernel<5, 2, false, 1, 2>),
-                                                reinterpret_cast<const void*>(fir_split_kernel<6, 2, false, 1, 2>)},
-                                               // (diagnostic builds: config 5's geometry, the 192-tap window; config 4's two-channel streams)
-                                               {nullptr, nullptr, nullptr, nullptr,
-                                                reinterpret_cast<const void*>(fir_split_kernel<5, 2, true, 0, 2>),
-                                                reinterpret_cast<const void*>(fir_split_kernel<6, 2, true, 0, 2>)},
-                                               {nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                reinterpret_cast<const void*>(fir_split_kernel<6, 2, true, 1, 2>)}};
-    const bool two_rounds = geo.rounds == 2;
-    const bool diag_long = two_rounds && diag && (geo.row_len / 32 == 6 || (geo.row_len / 32 == 5 && !wide));
-    const void* const* fns = two_rounds  ? fns_long[(wide ? 1 : 0) + (diag_long ? 2 : 0)]
-                             : one_channel ? fns_mono[0]
-                             : odd_count ? fns_odd[0]
-                             : wide      ? fns_wide[0]
-                                         : fns_all[geo.planes == 3 ? 1 : 0][diag ? 1 : 0];
-    const uint32_t nk = geo.row_len / 32;
-    if (nk < 1 || nk > (two_rounds ? 6u : 5u) || fns[nk - 1] == nullptr) return hipErrorInvalidValue;
-    // PCM input (FirStreamDesc::in_bits): the two-channel fp16 builds of the 128-tap windows -- 160 taps in one round
-    // (44.1 <-> 48 kHz) or two, 192 taps in two rounds (96 -> 44.1 kHz) -- exist for the three widths; hipErrorNotSupported
-    // for any other geometry (the caller converts with rsmp_pcm_to_stereo_f32_device first).
-    const void* fn = fns[nk - 1];
-    if (pcm_bits != 0) {
-#define RSMP_PCM_FNS(B)                                                                                                   \
-    {reinterpret_cast<const void*>(fir_split_kernel<5, 2, false, 0, 1, B>), reinterpret_cast<const void*>(fir_split_kernel<5, 2, false, 0, 2, B>), \
-     reinterpret_cast<const void*>(fir_split_kernel<6, 2, false, 0, 2, B>)}
-        static const void* const fns_pcm[3][3] = {RSMP_PCM_FNS(16), RSMP_PCM_FNS(24), RSMP_PCM_FNS(32)};
-#undef RSMP_PCM_FNS
-        const int v = !two_rounds && nk == 5 ? 0 : two_rounds && nk == 5 ? 1 : two_rounds && nk == 6 ? 2 : -1;
-        if (wide || one_channel || odd_count || geo.planes != 2 || diag || v < 0 || (pcm_bits != 16 && pcm_bits != 24 && pcm_bits != 32))
-            return hipErrorNotSupported;
-        fn = fns_pcm[pcm_bits == 16 ? 0 : pcm_bits == 24 ? 1 : 2][v];
-    }
+    const bool diag = fir_debug_knob() != 0 || wtrace_path != nullptr;
+    const SplitChoice choice = split_build_for(geo, diag, pcm_bits);
+    if (choice.error != BuildError::kNone) return choice.error == BuildError::kInvalid ? hipErrorInvalidValue : hipErrorNotSupported;
+    const void* fn = split_kernel_for(choice.build);
+    if (fn == nullptr) return hipErrorInvalidValue;
     int device = 0;
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess) return e;
-    static std::mutex mu;
-    static std::map<std::pair<int, uint32_t>, bool> granted;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        bool& have = granted[{device, ((((nk * 8 + geo.planes) * 2 + ((diag && !wide) || diag_long ? 1u : 0u)) * 4 + (one_channel ? 2u : odd_count ? 3u : wide ? 1u : 0u)) * 2 + (two_rounds ? 1u : 0u)) * 64 + pcm_bits}];
-        if (!have) {
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-            if (e != hipSuccess) return e;
-            have = true;
-        }
-    }
+    if ((e = grant_dynamic_lds(device, fn, kLdsLimit)) != hipSuccess) return e;
+    SplitArgs args = make_split_args(geo, n_streams, max_blocks, fuse_tail, nf);
     const dim3 grid(args.total_items < cus ? args.total_items : cus);
     static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
     if (verbose)
         fprintf(stderr, "[rsmp] split launch: a=%u b=%u window=%u tiles=%u groups=%u rounds=%u rows=%u slots=%u lds=%u items=%u grid=%u\n",
-                geo.a, geo.b, geo.row_len, geo.n_tiles, groups, geo.rounds, geo.row_stride, geo.images, geo.lds_bytes, args.total_items, grid.x);
-    static unsigned long long* d_wtrace = nullptr;
-    const size_t wtrace_words = static_cast<size_t>(grid.x) * 16 * kWtraceSlots;
+                geo.a, geo.b, geo.row_len, geo.n_tiles, args.groups, geo.rounds, geo.row_stride, geo.images, geo.lds_bytes, args.total_items, grid.x);
+    static TraceBuffer wtrace;
     if (wtrace_path) {
-        if (d_wtrace) (void)hipFree(d_wtrace);
-        if (hipMalloc(&d_wtrace, wtrace_words * 8) != hipSuccess) return hipErrorOutOfMemory;
-        (void)hipMemsetAsync(d_wtrace, 0, wtrace_words * 8, stream);
-        args.wtrace = d_wtrace;
+        if ((e = wtrace.renew(static_cast<size_t>(grid.x) * 16 * kWtraceSlots)) != hipSuccess) return e;
+        (void)hipMemsetAsync(wtrace.d, 0, wtrace.words * 8, stream);
+        args.wtrace = wtrace.d;
     }
     std::unique_lock<std::mutex> launch_lock(items_launch_mu(), std::defer_lock);
     // the item table: a launch of its own in front (one thread per item), in a workspace kept per stream
@@ -1946,19 +1731,14 @@ hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, co
     e = hipLaunchKernel(fn, grid, dim3(kWaves * 64), kargs,
                         geo.lds_bytes + (wtrace_path ? 16 * kWtraceSlots * 8 : 0), stream);
     if (e != hipSuccess) return e;
-    if (wtrace_path) {   // one line per wave: block wave event...
-        (void)hipStreamSynchronize(stream);
-        std::vector<unsigned long long> h(wtrace_words);
-        (void)hipMemcpy(h.data(), d_wtrace, wtrace_words * 8, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(wtrace_path, "w")) {
-            for (size_t w = 0; w < wtrace_words / kWtraceSlots; ++w) {
+    if (wtrace_path)   // one line per wave: block wave event...
+        wtrace.dump(wtrace_path, stream, [](FILE* f, const std::vector<unsigned long long>& h) {
+            for (size_t w = 0; w < h.size() / kWtraceSlots; ++w) {
                 fprintf(f, "%zu %zu", w / 16, w % 16);
                 for (uint32_t i = 0; i < kWtraceSlots; ++i) fprintf(f, " %llu", h[w * kWtraceSlots + i]);
                 fprintf(f, "\n");
             }
-            fclose(f);
-        }
-    }
+        });
     return hipGetLastError();
 }
 
@@ -1979,7 +1759,7 @@ hipError_t launch_fir_split_multi(const SplitJob* jobs, size_t n_jobs, hipStream
     // and LDS, nothing runs BESIDE it on that CU: the run planner of a small lock-step batch, fir_lockstep_api.cpp)
     const uint32_t cus_all = device_cus(device);
     const uint32_t cus = reserve_cus < cus_all / 2 ? cus_all - reserve_cus : cus_all;
-    static const bool diag = split_debug_knob() != 0 || rsmp::knob("RSMP_FIR_WTRACE") != nullptr;
+    static const bool diag = fir_debug_knob() != 0 || rsmp::knob("RSMP_FIR_WTRACE") != nullptr;
     static const bool multi_on = [] { const char* v = rsmp::knob("RSMP_FIR_SPLIT_MULTI"); return !v || atoi(v) != 0; }();
     // the multi-job builds: two channels, two fp16 planes; windows of 1 .. 5 steps in one round, 5 or 6 in two
     static const void* const fns_multi[2][6] = {
@@ -2072,73 +1852,17 @@ hipError_t launch_fir_split_multi(const SplitJob* jobs, size_t n_jobs, hipStream
             if (done[i0]) continue;
             SplitMulti m{};
             uint32_t idx[kMaxSplitJobs], nb = 0, lds = 0;
-            double weight[kMaxSplitJobs], weight_sum = 0.0;
-            uint64_t items_sum = 0;
+            DealJob deal[kMaxSplitJobs];
             for (uint32_t i = i0; i < n; ++i) {
                 if (done[i] || fn[i] != fn[i0]) continue;
                 done[i] = true;
                 idx[nb] = i;
-                // (items x frames of a period.  Round 6 tried the items' costs measured job by job instead -- 2.46 .. 4.39 us per item,
-                // profiles/r05/channels_bench.txt, by which this deal gives the two-round jobs 30 % too many workgroups: config 4 got
-                // 2 % SLOWER, 3.48 against 3.41 us per step in one lease; inside the shared launch the jobs do not cost what they cost alone)
-                weight[nb] = static_cast<double>(args[i].total_items) * args[i].a;
-                weight_sum += weight[nb];
-                items_sum += args[i].total_items;
+                deal[nb] = DealJob{args[i].total_items, args[i].a, args[i].groups};
                 lds = std::max(lds, args[i].lds_bytes);
                 ++nb;
             }
-            const uint32_t wgs = static_cast<uint32_t>(std::min<uint64_t>(cus, items_sum));
-            if (wgs < nb) {   // (fewer items than jobs cannot be: every job has at least one)
-                return hipErrorInvalidValue;
-            }
-            // at least one workgroup per job, no more than it has items; the rest by weight (largest remainder)
-            uint32_t share[kMaxSplitJobs], given = 0;
-            double frac[kMaxSplitJobs];
-            for (uint32_t b = 0; b < nb; ++b) {
-                const double ideal = weight[b] / weight_sum * wgs;
-                uint32_t w = static_cast<uint32_t>(ideal);
-                w = std::max<uint32_t>(1u, std::min<uint32_t>(w, args[idx[b]].total_items));
-                share[b] = w;
-                frac[b] = ideal - w;
-                given += w;
-            }
-            // A job with two tile groups: its item order makes workgroups w and w + n / 2 stage the same frames at about the
-            // same time (tiles 0 .. 9 / 10 .. 19 of the same blocks), and the second of them finds the frames in L2 only if
-            // both sit on one XCD -- workgroups go round the eight XCDs, so n / 2 must be a multiple of 8.  (Without this the
-            // two such pairs of config 4 read their input twice from HBM: 0.37 GB of 2.35 per run.)
-            bool two_groups[kMaxSplitJobs];
-            for (uint32_t b = 0; b < nb; ++b) {
-                two_groups[b] = args[idx[b]].groups > 1;
-                if (two_groups[b] && wgs >= 16) {
-                    const uint32_t r16 = std::max<uint32_t>(16u, (share[b] + 8u) / 16u * 16u);
-                    given = given - share[b] + r16;
-                    frac[b] += static_cast<double>(share[b]) - static_cast<double>(r16);
-                    share[b] = r16;
-                }
-            }
-            auto step_of = [&](uint32_t b) { return two_groups[b] && wgs >= 16 ? 16u : 1u; };
-            while (given > wgs) {   // (over: take from the job with the most to spare, a plain one if there is one)
-                int big = -1;
-                for (uint32_t b = 0; b < nb; ++b)
-                    if (share[b] > step_of(b) && !(two_groups[b] && wgs >= 16) && (big < 0 || share[b] > share[big])) big = static_cast<int>(b);
-                if (big < 0)
-                    for (uint32_t b = 0; b < nb; ++b)
-                        if (share[b] > step_of(b) && (big < 0 || share[b] > share[big])) big = static_cast<int>(b);
-                if (big < 0) break;
-                const uint32_t st = std::min(step_of(big), share[big] - 1);
-                share[big] -= st;
-                frac[big] += st;
-                given -= st;
-            }
-            while (given < wgs) {
-                int best = -1;
-                for (uint32_t b = 0; b < nb; ++b)
-                    if (step_of(b) == 1u && share[b] < args[idx[b]].total_items && (best < 0 || frac[b] > frac[best])) best = static_cast<int>(b);
-                if (best < 0) break;   // (only jobs that move in sixteens are left: the odd workgroups stay away)
-                ++share[best];
-                frac[best] -= 1.0;
-                ++given;
-            }
+            uint32_t share[kMaxSplitJobs];
+            if (!split_deal(deal, nb, cus, share)) return hipErrorInvalidValue;
             uint32_t end = 0;
             for (uint32_t b = 0; b < nb; ++b) {
                 m.g[b] = args[idx[b]];
@@ -2148,16 +1872,7 @@ hipError_t launch_fir_split_multi(const SplitJob* jobs, size_t n_jobs, hipStream
                 m.wg_end[b] = end;
             }
             m.n_jobs = nb;
-            static std::mutex mu;
-            static std::map<std::pair<int, const void*>, bool> granted;
-            {
-                std::lock_guard<std::mutex> lock(mu);
-                bool& have = granted[{device, fn[i0]}];
-                if (!have) {
-                    if ((e = hipFuncSetAttribute(fn[i0], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit)) != hipSuccess) return e;
-                    have = true;
-                }
-            }
+            if ((e = grant_dynamic_lds(device, fn[i0], kLdsLimit)) != hipSuccess) return e;
             static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
             if (verbose)
                 for (uint32_t b = 0; b < nb; ++b)

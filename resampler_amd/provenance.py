@@ -8,7 +8,8 @@ import hashlib
 import os
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-_FIR = ["fir_split.hip", "fir_periodic.hip", "fir_periodic.h", "fir_kernels.h", "fir_nonfinite.h"]
+_FIR = ["fir_split.hip", "fir_periodic.hip", "fir_split_consts.h", "fir_periodic_consts.h", "fir_periodic_plan.h", "fir_periodic.h",
+        "fir_kernels.h", "fir_nonfinite.h"]
 SOURCES = {
     "fir": _FIR,
     "c5": _FIR,

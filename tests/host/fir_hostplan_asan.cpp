@@ -1,7 +1,7 @@
 // fir_hostplan_asan.cpp -- the host planner under AddressSanitizer + UBSan: a stand-alone program
-// (tests/test_host_programs.py builds it with fir_hostplan.cpp, fir_plan.cpp, filter_design.cpp and common.cpp, none of which
-// includes a HIP header, and runs it).  The four periodic_* rules the planner asks about live beside the kernels
-// (fir_periodic.hip); this program answers them itself instead of linking a kernel file: `g_periodic` picks the plan's kind.
+// (tests/test_host_programs.py builds it with fir_hostplan.cpp, fir_plan.cpp, fir_geometry.cpp, filter_design.cpp and common.cpp,
+// none of which includes a HIP header, and runs it).  The periodic_* rules the planner asks about are the library's own
+// (fir_geometry.cpp): the rate pair and the length of the job pick the plan's kind.
 #include <cstdio>
 #include <memory>
 
@@ -9,23 +9,11 @@
 #include "fir_hostplan.h"
 #include "fir_periodic_plan.h"
 
-static bool g_periodic = false;
-namespace rsmp {
-bool periodic_supported(const FirMirror&, size_t, size_t, int) { return g_periodic; }
-bool periodic_worthwhile(const FirMirror&, size_t, int) { return true; }
-size_t periodic_wrap_words(uint64_t, uint32_t n_out, uint64_t den) { return (n_out / den + 1 + 31) / 32; }
-void periodic_fill_wrap_bits(const std::vector<uint32_t>&, uint64_t, uint64_t, uint32_t* words, size_t n_words) {
-    for (size_t w = 0; w < n_words; ++w) words[w] = 0;
-}
-}  // namespace rsmp
-
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } } while (0)
 
-// A 10-chunk bulk job of a fresh two-channel stream (another chunk size per kind of plan: the kind is no part of the cache's key,
-// in the library it follows from the key), planned twice: the second is the cached plan, with the same counts,
+// A 10-chunk bulk job of a fresh two-channel stream, planned twice: the second is the cached plan, with the same counts,
 // and they are the counts of the loop run directly (what rsmp_fir_plan_bulk does).
 static int plan_twice(uint32_t in_hz, uint32_t out_hz, size_t chunk_frames, bool periodic) {
-    g_periodic = periodic;
     const size_t ch = 2, taps = 128, frames = 10 * chunk_frames;
     const rsmp::FirMirror fresh(in_hz, out_hz, taps);
     const rsmp::PlanRequest q{fresh, ch, taps, in_hz, out_hz, 0, frames * ch, 1u << 20, chunk_frames * ch};
@@ -48,7 +36,9 @@ static int plan_twice(uint32_t in_hz, uint32_t out_hz, size_t chunk_frames, bool
 }
 
 int main() {
-    if (plan_twice(44100, 48000, 512, false) || plan_twice(44100, 48000, 256, true) || plan_twice(44100, 48001, 512, false)) return 1;
+    // 44.1 -> 48 kHz has a periodic geometry: 5120 frames are too few outputs to be worth it (periodic_worthwhile), 20480 are
+    // enough; 44100 / 48001 does not reduce to a period any kernel holds (periodic_supported)
+    if (plan_twice(44100, 48000, 512, false) || plan_twice(44100, 48000, 2048, true) || plan_twice(44100, 48001, 512, false)) return 1;
     // more distinct requests than the cache holds: the oldest entries are overwritten in place
     for (size_t k = 1; k <= 80; ++k) {
         const rsmp::FirMirror fresh(48000, 44100, 128);

@@ -1,8 +1,12 @@
 """Stand-alone host programs under tests/host, built with the host compiler and a sanitizer and run as processes of their
 own (no GPU, nothing loaded into python)."""
+import hashlib
+import json
 import os
 import shutil
 import subprocess
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "resampler_amd", "csrc")
@@ -27,12 +31,12 @@ def test_host_planner_under_address_and_ub_sanitizers(tmp_path):
     """The host planner (fir_hostplan.cpp + fir_plan.cpp, no HIP header anywhere below them) built with
     -fsanitize=address,undefined: a 10-chunk bulk job planned twice -- the second is the cached plan, same counts, the counts of
     the driver loop run directly --, for a generic and a periodic plan, a request without room, and more requests than the cache
-    holds.  The periodic rules of fir_periodic.hip are answered by the program itself: no kernel file is linked."""
+    holds.  The periodic rules the planner asks about are the library's own (fir_geometry.cpp)."""
     gxx = shutil.which("g++")
     assert gxx, "g++ is needed to build tests/host/fir_hostplan_asan.cpp"
     exe = str(tmp_path / "fir_hostplan_asan")
     srcs = [os.path.join(ROOT, "tests", "host", "fir_hostplan_asan.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in ("fir_hostplan.cpp", "fir_plan.cpp", "filter_design.cpp", "common.cpp")]
+    srcs += [os.path.join(CSRC, f) for f in ("fir_hostplan.cpp", "fir_plan.cpp", "fir_geometry.cpp", "filter_design.cpp", "common.cpp")]
     subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-I", CSRC] + srcs + ["-o", exe],
                    check=True)
@@ -40,3 +44,130 @@ def test_host_planner_under_address_and_ub_sanitizers(tmp_path):
     assert run.returncode == 0, run.stdout + run.stderr
     assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr
     assert "fir_hostplan_asan: ok" in run.stdout
+
+
+# ---- the rules that left the kernel files: geometry, kernel build, class-table image, deal of workgroups ---------------------
+SANITIZE = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
+            "-Wextra", "-I", CSRC]
+CLANGXX = "/opt/rocm/llvm/bin/clang++"   # _Float16 in plain host C++ (the system g++ has none)
+# The debug switches are read once per process: one run per setting (errors.h's knob() sees them only under RSMP_DEBUG=1).
+SETTINGS = {
+    "default": {},
+    "planes3": {"RSMP_FIR_SPLIT_PLANES": "3"},
+    "mfma0": {"RSMP_FIR_MFMA": "0"},
+    "mfma1": {"RSMP_FIR_MFMA": "1"},
+    "mfma2": {"RSMP_FIR_MFMA": "2"},
+    "mfma4": {"RSMP_FIR_MFMA": "4"},
+    "wide0": {"RSMP_FIR_SPLIT_WIDE": "0"},
+    "long0": {"RSMP_FIR_SPLIT_LONG": "0"},
+    "ring1": {"RSMP_FIR_MFMA_RING": "1"},
+}
+
+
+def _setting_env(setting):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}
+    if SETTINGS[setting]:
+        env.update(SETTINGS[setting], RSMP_DEBUG="1")
+    return env
+
+
+def _clean(run):
+    assert run.returncode == 0, run.stderr
+    err = run.stderr if isinstance(run.stderr, str) else run.stderr.decode()
+    assert "Sanitizer" not in err and "runtime error" not in err, err
+
+
+@pytest.fixture(scope="module")
+def geometry_golden():
+    """Recorded from the commit before the move (tests/golden/make_fir_geometry_fixture.py)."""
+    with open(os.path.join(ROOT, "tests", "golden", "fir_geometry.json")) as fh:
+        fx = json.load(fh)
+    assert fx["settings"] == SETTINGS
+    return fx
+
+
+@pytest.fixture(scope="module")
+def geometry_dump(tmp_path_factory):
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fir_geometry_dump.cpp"
+    exe = str(tmp_path_factory.mktemp("geo") / "fir_geometry_dump")
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_geometry_dump.cpp"), os.path.join(CSRC, "fir_geometry.cpp"),
+                                       "-o", exe], check=True)
+    return exe
+
+
+@pytest.mark.parametrize("setting", list(SETTINGS))
+def test_geometry_and_build_choice_as_before_the_move(geometry_dump, geometry_golden, setting):
+    """fir_geometry.cpp (plain C++, ASan + UBSan): every field of the geometry and the kernel build chosen for it -- the split
+    kernel's template arguments plain / diagnostic / with 16-bit PCM input, the other kernels' table slot without and with
+    RSMP_FIR_MFMA_DBG=1, or the error -- for the 90 ordered pairs of the ten sample rates and 24000 -> 16000, the tap count of
+    every Latency, 1 .. 17 channels and the three (allow_matrix, allow_split) the kernel modes produce, under one setting of
+    the switches: per (taps, channels, mode) the count of geometries and the SHA-256 of the rows equal what the commit before
+    the move gave; under the default setting the rows of the headline pair and of config 4's six pairs are compared in full."""
+    run = subprocess.run([geometry_dump], env=_setting_env(setting), capture_output=True, text=True, timeout=300)
+    _clean(run)
+    groups, full = {}, {"headline": [], "c4": []}
+    for row in run.stdout.splitlines():
+        taps, ch, mode, pair = row.split(" | ")[0].split()
+        groups.setdefault("%s %s %s" % (taps, ch, mode), []).append(row)
+        if (taps, ch) == ("128", "2"):
+            if pair == "147/160" and row not in full["headline"]:
+                full["headline"].append(row)
+            if pair in ("147/160", "160/147", "147/320", "320/147", "1/2", "2/1") and row not in full["c4"]:
+                full["c4"].append(row)
+    if setting == "default":
+        assert full == geometry_golden["rows"]
+    want = geometry_golden["geometry"][setting]
+    assert sorted(groups) == sorted(want) and len(groups) == 4 * 9 * 3
+    for key, rows in groups.items():
+        assert len(rows) == 91
+        got = [sum(r.split(" | ")[1].startswith("1 ") for r in rows), hashlib.sha256("".join(r + "\n" for r in rows).encode()).hexdigest()]
+        assert got == want[key], (setting, key)
+
+
+def _table_digests(blob):
+    out, pos = {}, 0
+    while pos < len(blob):
+        end = blob.index(b"\n", pos)
+        name, drift, part, n = blob[pos:end].decode().split()
+        out["%s %s %s" % (name, drift, part)] = hashlib.sha256(blob[end + 1:end + 1 + int(n)]).hexdigest()
+        pos = end + 1 + int(n)
+    return out
+
+
+def test_class_table_images_as_before_the_move(tmp_path, geometry_golden):
+    """fir_class_table.cpp (plain C++ with _Float16: ROCm's clang++ as a host compiler, -ffp-contract=off like the library, ASan +
+    UBSan) on the real polyphase table of filter_design.cpp: coef, wrap_coef and meta of the headline geometry in two and in
+    three planes, config 4's six pairs, an exact-f32 matrix-core geometry, a vector geometry with the wrap variant in the
+    table and one without, each at drift 0, +2e-9 and -2e-9 -- bit for bit what the commit before the move built."""
+    assert os.path.exists(CLANGXX), "ROCm's clang++ is needed to build tests/host/fir_class_table_dump.cpp"
+    exe = str(tmp_path / "fir_class_table_dump")
+    srcs = [os.path.join(ROOT, "tests", "host", "fir_class_table_dump.cpp")]
+    srcs += [os.path.join(CSRC, f) for f in ("fir_class_table.cpp", "fir_geometry.cpp", "filter_design.cpp", "common.cpp")]
+    subprocess.run([CLANGXX] + SANITIZE + srcs + ["-o", exe], check=True)
+    for setting, args, n_images in (("default", [], 9), ("planes3", ["headline"], 1)):
+        run = subprocess.run([exe] + args, env=_setting_env(setting), capture_output=True, timeout=300)
+        _clean(run)
+        got = _table_digests(run.stdout)
+        assert len(got) == n_images * 3 * 3
+        assert got == geometry_golden["class_tables"][setting], setting
+    assert any(k.startswith("headline:mfma3:planes3:") for k in geometry_golden["class_tables"]["planes3"])
+    assert any(k.startswith("headline:mfma3:planes2:") for k in geometry_golden["class_tables"]["default"])
+    assert any(k.startswith("f32_matrix:mfma2:") for k in geometry_golden["class_tables"]["default"])
+    assert any(k.startswith("vector_inline_wraps:mfma0:planes0:wraps1") for k in geometry_golden["class_tables"]["default"])
+    assert any(k.startswith("vector_fixup_wraps:mfma0:planes0:wraps0") for k in geometry_golden["class_tables"]["default"])
+
+
+def test_deal_of_workgroups(tmp_path):
+    """split_deal (fir_split_deal.cpp, plain C++, ASan + UBSan): the invariants of the deal over 400 seeded random job sets
+    (tests/host/fir_split_deal_check.cpp states them), and the shares of BASELINE config 4's six jobs at 1024 streams and at a
+    128-stream shard, on 256 CUs and on 256 less the lock-step batch's reserve, as the commit before the move dealt them on an
+    MI355X."""
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fir_split_deal_check.cpp"
+    exe = str(tmp_path / "fir_split_deal_check")
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_split_deal_check.cpp"), os.path.join(CSRC, "fir_split_deal.cpp"),
+                                       "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    _clean(run)
+    assert "fir_split_deal_check: ok" in run.stdout
