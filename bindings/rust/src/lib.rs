@@ -91,6 +91,16 @@ extern "C" {
     fn rsmp_fir_batch_resample_bulk_pcm_device(rs: *const *mut rsmp_fir, n: usize, d_pcm: *const *const std::os::raw::c_void, bits: c_int,
                                                in_lens: *const usize, chunk_len: usize, d_out: *const *mut f32, out_caps: *const usize,
                                                consumed: *mut usize, produced: *mut usize, stream: *mut std::os::raw::c_void) -> c_int;
+    // addition: the output as a WAV file stores it -- little-endian PCM of out_bits (16 / 24 / 32), quantised where the FIR kernels
+    // store their sums; d_in is interleaved f32 (in_bits = 0) or PCM of in_bits; out_caps in samples
+    fn rsmp_fir_batch_resample_bulk_pcm_out_device(rs: *const *mut rsmp_fir, n: usize, d_in: *const *const std::os::raw::c_void, in_bits: c_int,
+                                                   in_lens: *const usize, chunk_len: usize, d_out_pcm: *const *mut std::os::raw::c_void,
+                                                   out_bits: c_int, out_caps: *const usize, consumed: *mut usize, produced: *mut usize,
+                                                   stream: *mut std::os::raw::c_void) -> c_int;
+    // addition: f32 -> PCM of `bits` (round half to even of x * 2^(bits-1), saturated, NaN -> 0), host memory / device memory
+    fn rsmp_f32_to_pcm(input: *const f32, n_values: usize, bits: c_int, out_pcm: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_f32_to_pcm_device(d_in: *const f32, n_values: usize, bits: c_int, d_pcm: *mut std::os::raw::c_void,
+                              stream: *mut std::os::raw::c_void) -> c_int;
     // addition: WAV samples (resample/src/main.rs:128-137) converted inside the FFT kernel's first load
     fn rsmp_fft_batch_resample_bulk_pcm_device(rs: *const *mut rsmp_fft, n: usize, d_pcm: *const *const std::os::raw::c_void, bits: c_int,
                                                d_out: *const *mut f32, n_chunks: *const usize, stream: *mut std::os::raw::c_void) -> c_int;
@@ -194,6 +204,32 @@ impl ResamplerFir {
         status(rsmp_fir_batch_resample_bulk_pcm_device(h.as_ptr(), 1, p.as_ptr(), bits as c_int, &n_samples, chunk_len, o.as_ptr(), &out_cap,
                                                        &mut consumed, &mut produced, std::ptr::null_mut())).map(|_| (consumed, produced))
     }
+
+    /// Addition to the reference API: the same loop with the output as a WAV file stores it -- `d_out_pcm` (device memory, 4-byte
+    /// aligned, room for `out_cap` samples) receives little-endian PCM of `out_bits` (16 / 24 / 32), quantised where the kernels
+    /// store their sums (`f32_to_pcm`'s rule).  `d_in`: interleaved f32 (`in_bits` = 0) or PCM of `in_bits`, `n_values` values.
+    /// Returns (consumed, produced) in samples.
+    pub unsafe fn resample_bulk_pcm_out_device(&mut self, d_in: *const std::os::raw::c_void, in_bits: u32, n_values: usize, chunk_len: usize,
+                                               d_out_pcm: *mut std::os::raw::c_void, out_bits: u32, out_cap: usize)
+                                               -> Result<(usize, usize), ResampleError> {
+        let (h, p, o) = ([self.handle], [d_in], [d_out_pcm]);
+        let (mut consumed, mut produced) = (0usize, 0usize);
+        status(rsmp_fir_batch_resample_bulk_pcm_out_device(h.as_ptr(), 1, p.as_ptr(), in_bits as c_int, &n_values, chunk_len, o.as_ptr(),
+                                                           out_bits as c_int, &out_cap, &mut consumed, &mut produced, std::ptr::null_mut()))
+            .map(|_| (consumed, produced))
+    }
+}
+
+/// Addition to the reference API: f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host; the library's quantiser --
+/// round half to even of x * 2^(bits-1), saturated to the code range, NaN -> 0, no dither.
+pub fn f32_to_pcm(input: &[f32], bits: u32) -> Result<Vec<u8>, ResampleError> {
+    let mut out = vec![0u8; input.len() * (bits as usize / 8)];
+    status(unsafe { rsmp_f32_to_pcm(input.as_ptr(), input.len(), bits as c_int, out.as_mut_ptr() as *mut std::os::raw::c_void) }).map(|_| out)
+}
+
+/// The same on device memory (`d_in` 16-byte aligned, `d_pcm` 4-byte aligned, asynchronous on the default stream).
+pub unsafe fn f32_to_pcm_device(d_in: *const f32, n_values: usize, bits: u32, d_pcm: *mut std::os::raw::c_void) -> Result<(), ResampleError> {
+    status(rsmp_f32_to_pcm_device(d_in, n_values, bits as c_int, d_pcm, std::ptr::null_mut()))
 }
 
 /// impl fmt::Debug for ResamplerFir (src/resampler_fir.rs:203-211): channels, taps, phases, `..`

@@ -195,6 +195,19 @@ int rsmp_fir_batch_resample_bulk_device_ex(rsmp_fir* const* rs, size_t n, const 
 int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size_t n, const void* const* d_pcm, int bits,
                                             const size_t* in_lens, size_t chunk_len, float* const* d_out,
                                             const size_t* out_caps, size_t* consumed, size_t* produced, void* stream);
+/* The other half of a file-to-file pipeline: the output as a WAV file stores it.  d_out_pcm[i] receives little-endian PCM of
+ * `out_bits` (16 / 24 / 32; 24-bit packed at 3 bytes a sample), 4-byte aligned, with room for out_caps[i] SAMPLES; every value
+ * the f32 entry would have written is quantised where the kernels store it (the rule: rsmp_f32_to_pcm below), so the bytes are
+ * exactly rsmp_f32_to_pcm_device's of rsmp_fir_batch_resample_bulk_device's output and the f32 never reaches HBM.  d_in[i] is
+ * interleaved f32 (in_bits = 0) or PCM of in_bits (16 / 24 / 32) as in rsmp_fir_batch_resample_bulk_pcm_device; in_lens in
+ * values / samples.  Counts, end states, the buffered frames (f32 always) and the ordering on `stream` are those of the f32
+ * entry on the same input.  No byte outside [d_out_pcm[i], d_out_pcm[i] + out_caps[i] * out_bits / 8) is written; a capacity
+ * too small is RSMP_ERR_CAPACITY before anything is launched.  Planned on the host.  Two-channel streams; long launches need
+ * the 128-tap rate pairs of the split kernel as PCM input does, at most one launch's worth of input per stream; anything else is
+ * RSMP_ERR_INVALID_ARGUMENT before any launch -- take f32 output and convert with rsmp_f32_to_pcm_device. */
+int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
+                                                const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
+                                                const size_t* out_caps, size_t* consumed, size_t* produced, void* stream);
 
 /* reset() for every stream of a batch. */
 void rsmp_fir_batch_reset(rsmp_fir* const* rs, size_t n);
@@ -397,6 +410,18 @@ int rsmp_interp_resample_device(int mode, size_t channels, uint32_t in_hz, uint3
  * (2 channels in) or 2 * n_samples (1 channel in).  Device pointers, asynchronous on `stream`. */
 int rsmp_pcm_to_stereo_f32_device(const void* d_pcm, int bits, int channels, size_t n_samples, float* d_out,
                                   void* stream);
+/* The way back, f32 -> little-endian integer PCM of `bits` (16, packed 24, 32), n_values * bits / 8 bytes:
+ *   q = saturate(round_half_to_even(x * 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1),  NaN -> 0.
+ * The product is exact (a power of two); +inf and everything above the range give the top code, -inf and everything below the
+ * bottom one, -0.0 and denormals 0; +1.0 saturates to the top code.  No dither, no noise shaping.  Decoding with
+ * rsmp_pcm_to_stereo_f32_device and quantising again at the same width is the identity on every 16-bit and 24-bit code.  At 32
+ * bits it is NOT: the reference decodes 32-bit files with the divisor -2^31 (resample/src/main.rs:131), the scale here is
+ * +2^31 -- an f32 value means what it says --, so that round trip gives saturate(-f32(s)): polarity inverted, the bottom code
+ * saturated to the top one.
+ * rsmp_f32_to_pcm: host memory, needs no device -- the definition itself.  rsmp_f32_to_pcm_device: device pointers,
+ * asynchronous on `stream`; d_in 16-byte aligned, d_pcm 4-byte aligned, any n_values; writes exactly n_values * bits / 8 bytes. */
+int rsmp_f32_to_pcm(const float* in, size_t n_values, int bits, void* out_pcm);
+int rsmp_f32_to_pcm_device(const float* d_in, size_t n_values, int bits, void* d_pcm, void* stream);
 /* Measurement aid (no counterpart in the reference): a plain streaming copy of n_values floats, 16 bytes per lane --
  * the rate a kernel that reads as much as it writes can reach on this GPU; bench.py reports it next to every
  * roofline fraction.  16-byte aligned device pointers, n_values a multiple of 4, asynchronous on `stream`. */

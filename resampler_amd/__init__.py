@@ -177,6 +177,8 @@ _SIGNATURES = [
     ("rsmp_interp_resample_device", C.c_int,
      [C.c_int, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _szp, C.c_void_p]),
     ("rsmp_pcm_to_stereo_f32_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("rsmp_f32_to_pcm", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    ("rsmp_f32_to_pcm_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     ("rsmp_device_stream_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rsmp_fft_new", C.c_void_p, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     ("rsmp_fft_free", None, [C.c_void_p]),
@@ -196,6 +198,9 @@ _SIGNATURES = [
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _szp, C.c_void_p]),
     ("rsmp_fir_batch_resample_bulk_pcm_device", C.c_int,
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, _szp, C.c_size_t, C.POINTER(C.c_void_p), _szp, _szp, _szp, C.c_void_p]),
+    ("rsmp_fir_batch_resample_bulk_pcm_out_device", C.c_int,
+     [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, _szp, C.c_size_t, C.POINTER(C.c_void_p), C.c_int, _szp, _szp, _szp,
+      C.c_void_p]),
     ("rsmp_fft_batch_resample_bulk_pcm_device", C.c_int,
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), _szp, C.c_void_p]),
     ("rsmp_fft_plan_sizes", C.c_int,
@@ -509,6 +514,23 @@ class FirBatch:
         self._keep_pcm = (list(d_pcms), list(d_outs))
         _check(lib().rsmp_fir_batch_resample_bulk_pcm_device(self._handles, n, pin, bits, lens, chunk_len, pout, caps,
                                                              self._consumed, self._produced, C.c_void_p(stream or 0)))
+        return (np.ctypeslib.as_array(self._consumed), np.ctypeslib.as_array(self._produced))
+
+    def resample_bulk_pcm_out_device(self, d_ins, in_bits: int, d_out_pcms, out_bits: int, chunk_len: int = 512,
+                                     stream: Optional[int] = None):
+        """The bulk driver loop with the output as a WAV file stores it (rsmp_fir_batch_resample_bulk_pcm_out_device): d_out_pcms =
+        uint8 tensors that receive little-endian PCM of `out_bits` (16 / 24 / 32), quantised where the kernels store their sums
+        (f32_to_pcm's rule).  d_ins = float32 tensors (in_bits = 0) or uint8 tensors of PCM of `in_bits`."""
+        n = len(self.resamplers)
+        pin, pout = (C.c_void_p * n)(), (C.c_void_p * n)()
+        lens, caps = (C.c_size_t * n)(), (C.c_size_t * n)()
+        for i, (a, b) in enumerate(zip(d_ins, d_out_pcms)):
+            assert b.is_cuda and b.is_contiguous() and str(b.dtype) == "torch.uint8"
+            pin[i], pout[i] = (_dev_ptr(a) if in_bits == 0 else a.data_ptr()), b.data_ptr()
+            lens[i], caps[i] = (a.numel() if in_bits == 0 else a.numel() // max(1, in_bits // 8)), b.numel() // max(1, out_bits // 8)
+        self._keep_pcm = (list(d_ins), list(d_out_pcms))
+        _check(lib().rsmp_fir_batch_resample_bulk_pcm_out_device(self._handles, n, pin, in_bits, lens, chunk_len, pout, out_bits, caps,
+                                                                 self._consumed, self._produced, C.c_void_p(stream or 0)))
         return (np.ctypeslib.as_array(self._consumed), np.ctypeslib.as_array(self._produced))
 
 
@@ -846,6 +868,24 @@ def pcm_to_stereo_f32_device(d_pcm, bits: int, channels: int, d_out, stream: Opt
     assert d_out.numel() >= n * (2 if channels == 1 else 1)
     _check(lib().rsmp_pcm_to_stereo_f32_device(C.c_void_p(d_pcm.data_ptr()), bits, channels, n,
                                                C.c_void_p(d_out.data_ptr()), C.c_void_p(stream or 0)))
+
+
+def f32_to_pcm(x, bits: int) -> bytes:
+    """f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host, no device needed (rsmp_f32_to_pcm): the library's
+    quantiser -- round half to even of x * 2^(bits-1), saturated, NaN -> 0."""
+    a = _np_f32(x).reshape(-1)
+    out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8)
+    _check(lib().rsmp_f32_to_pcm(C.c_void_p(a.ctypes.data), a.size, bits, C.c_void_p(out.ctypes.data)))
+    return out.tobytes()
+
+
+def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None) -> None:
+    """The same on HBM-resident torch tensors (rsmp_f32_to_pcm_device): d_in = float32, d_pcm = uint8 with room for
+    d_in.numel() * bits / 8 bytes, 4-byte aligned; exactly those bytes are written."""
+    n = d_in.numel()
+    if bits in (16, 24, 32):
+        assert d_pcm.numel() >= n * (bits // 8)
+    _check(lib().rsmp_f32_to_pcm_device(C.c_void_p(_dev_ptr(d_in)), n, bits, C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
 
 
 def fft_plan_sizes(input_rate_hz: int, output_rate_hz: int):

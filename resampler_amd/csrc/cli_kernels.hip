@@ -4,7 +4,9 @@
 //     as the reference computes it (output index / ratio), arithmetic in the reference's order;
 //   * WAV sample conversion (resample/src/main.rs:128-156): 16 / 24 / 32-bit little-endian PCM -> f32
 //     (`s as f32 / (1 << (bits - 1)) as f32`) with mono duplicated to stereo, so a decoded file goes from
-//     its PCM bytes in HBM to the interleaved f32 frames the resamplers take in one pass.
+//     its PCM bytes in HBM to the interleaved f32 frames the resamplers take in one pass;
+//   * the way back, f32 -> 16 / 24 / 32-bit little-endian PCM (fir_pcm_quantise, fir_kernels.h: round half to even, saturate,
+//     NaN -> 0, no dither), on the host and as a streaming pass on the device.
 // Both are HBM-bound elementwise kernels: coalesced loads / stores, nothing to stage.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +16,7 @@
 #include "../../include/resampler_amd.h"
 #include "common.h"
 #include "device_util.h"
+#include "fir_kernels.h"
 
 namespace {
 
@@ -76,6 +79,36 @@ __global__ __launch_bounds__(kThreads) void pcm_kernel(const uint8_t* __restrict
         reinterpret_cast<float2*>(out)[i] = make_float2(v, v);
     } else {
         out[i] = v;
+    }
+}
+
+// f32 -> PCM: a lane takes four values (one 16-byte load) and writes their 8 / 12 / 16 bytes -- whole words at a 4-byte aligned
+// address, since the lane's first byte is 8 / 12 / 16 x its index from a 4-byte aligned base; the last lane of the buffer takes the
+// n % 4 values left over one by one, each with stores of the sample's own bytes.  Every byte is written once, by the lane that
+// owns it, and none past n * BITS / 8.
+template <int BITS>
+__global__ __launch_bounds__(kThreads) void f32_to_pcm_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, uint64_t n) {
+    typedef float v4f_in __attribute__((ext_vector_type(4)));
+    const uint64_t n4 = n / 4, stride = static_cast<uint64_t>(gridDim.x) * kThreads;
+    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(kThreads) + threadIdx.x; i <= n4; i += stride) {
+        if (i == n4) {   // the 0 .. 3 values behind the last whole four
+            for (uint64_t k = 4 * n4; k < n; ++k) rsmp::fir_pcm_store(out, BITS, k, in[k]);
+            break;
+        }
+        const v4f_in x = reinterpret_cast<const v4f_in*>(in)[i];
+        const uint32_t q0 = static_cast<uint32_t>(rsmp::fir_pcm_quantise(x.x, BITS)), q1 = static_cast<uint32_t>(rsmp::fir_pcm_quantise(x.y, BITS));
+        const uint32_t q2 = static_cast<uint32_t>(rsmp::fir_pcm_quantise(x.z, BITS)), q3 = static_cast<uint32_t>(rsmp::fir_pcm_quantise(x.w, BITS));
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + i * (BITS / 2));
+        if constexpr (BITS == 16) {
+            o[0] = (q0 & 0xFFFFu) | (q1 << 16);
+            o[1] = (q2 & 0xFFFFu) | (q3 << 16);
+        } else if constexpr (BITS == 24) {
+            o[0] = (q0 & 0xFFFFFFu) | (q1 << 24);
+            o[1] = ((q1 >> 8) & 0xFFFFu) | (q2 << 16);
+            o[2] = ((q2 >> 16) & 0xFFu) | (q3 << 8);
+        } else {
+            o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
+        }
     }
 }
 
@@ -150,6 +183,42 @@ extern "C" int rsmp_pcm_to_stereo_f32_device(const void* d_pcm, int bits, int ch
     if (bits == 16) hipLaunchKernelGGL(pcm_kernel<16>, grid, dim3(kThreads), 0, s, p, d_out, static_cast<uint64_t>(n_samples), mono);
     else if (bits == 24) hipLaunchKernelGGL(pcm_kernel<24>, grid, dim3(kThreads), 0, s, p, d_out, static_cast<uint64_t>(n_samples), mono);
     else hipLaunchKernelGGL(pcm_kernel<32>, grid, dim3(kThreads), 0, s, p, d_out, static_cast<uint64_t>(n_samples), mono);
+    RSMP_HIP_CHECK(hipGetLastError());
+    return RSMP_OK;
+}
+
+// The definition itself, on the host (no device needed).
+extern "C" int rsmp_f32_to_pcm(const float* in, size_t n_values, int bits, void* out_pcm) {
+    if ((bits != 16 && bits != 24 && bits != 32) || (n_values != 0 && (!in || !out_pcm)))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm: 16 / 24 / 32 bits, non-null buffers");
+    uint8_t* o = static_cast<uint8_t*>(out_pcm);
+    const size_t bytes = static_cast<size_t>(bits) / 8;
+    for (size_t i = 0; i < n_values; ++i) {
+        const uint32_t q = static_cast<uint32_t>(rsmp::fir_pcm_quantise(in[i], static_cast<uint32_t>(bits)));
+        for (size_t b = 0; b < bytes; ++b) o[i * bytes + b] = static_cast<uint8_t>(q >> (8 * b));   // little-endian
+    }
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_f32_to_pcm_device(const float* d_in, size_t n_values, int bits, void* d_pcm, void* stream) {
+    if ((bits != 16 && bits != 24 && bits != 32) || (n_values != 0 && (!d_in || !d_pcm)))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_device: 16 / 24 / 32 bits, non-null buffers");
+    if (reinterpret_cast<uintptr_t>(d_in) % 16 != 0 || reinterpret_cast<uintptr_t>(d_pcm) % 4 != 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_device: d_in 16-byte aligned, d_pcm 4-byte aligned");
+    if (int rc = check_device()) return rc;
+    if (n_values == 0) return RSMP_OK;
+    int cus = 256;
+    int device = 0;
+    (void)hipGetDevice(&device);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    const uint64_t lanes = n_values / 4 + 1;
+    const uint64_t blocks = (lanes + kThreads - 1) / kThreads, most = static_cast<uint64_t>(cus) * 8u;   // (eight workgroups of 256 a CU walk the buffer side by side)
+    const dim3 grid(static_cast<uint32_t>(blocks < most ? blocks : most));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* o = static_cast<uint8_t*>(d_pcm);
+    if (bits == 16) hipLaunchKernelGGL(f32_to_pcm_kernel<16>, grid, dim3(kThreads), 0, s, d_in, o, static_cast<uint64_t>(n_values));
+    else if (bits == 24) hipLaunchKernelGGL(f32_to_pcm_kernel<24>, grid, dim3(kThreads), 0, s, d_in, o, static_cast<uint64_t>(n_values));
+    else hipLaunchKernelGGL(f32_to_pcm_kernel<32>, grid, dim3(kThreads), 0, s, d_in, o, static_cast<uint64_t>(n_values));
     RSMP_HIP_CHECK(hipGetLastError());
     return RSMP_OK;
 }

@@ -238,7 +238,8 @@ int run_staged(rsmp_fir* r, const float* in, size_t in_len, float* out, size_t o
 
 // One launch of a list of streams: a plan per distinct (state, amount of input), then launch_jobs led by the first handle.
 int batch_bulk_piece(rsmp_fir* const* rs, size_t n, const float* const* d_in, const size_t* in_lens, size_t chunk_len,
-                     float* const* d_out, const size_t* out_caps, size_t* consumed, size_t* produced, void* stream, uint32_t pcm_bits = 0) {
+                     float* const* d_out, const size_t* out_caps, size_t* consumed, size_t* produced, void* stream, uint32_t pcm_bits = 0,
+                     uint32_t out_bits = 0) {
     switch (rsmp::batch_handles_fault(rs, n)) {
         case rsmp::BatchFault::NullOrOtherDevice: return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "batch streams must share one device");
         case rsmp::BatchFault::Duplicate: return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "batch lists the same stream twice");
@@ -298,7 +299,7 @@ int batch_bulk_piece(rsmp_fir* const* rs, size_t n, const float* const* d_in, co
                               j.plan->produced_frames * rs[i]->channels, out_caps[i]);
     }
     const auto t_planned = std::chrono::steady_clock::now();
-    const int rc = launch_jobs(rs[0], jobs, s, pcm_bits);
+    const int rc = launch_jobs(rs[0], jobs, s, pcm_bits, out_bits);
     if (rc != RSMP_OK) return rc;
     if (verbose_t) {
         const auto t_end = std::chrono::steady_clock::now();
@@ -626,4 +627,35 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
         in[i] = static_cast<const float*>(d_pcm[i]);
     }
     return batch_bulk_piece(rs, n, in.data(), in_lens, chunk_len, d_out, out_caps, consumed, produced, stream, static_cast<uint32_t>(bits));
+}
+
+// The same with the output as a WAV file stores it: d_out_pcm[i] receives little-endian PCM of `out_bits` (16 / 24 / 32; 24-bit
+// packed), every sum quantised where the kernels store it (fir_pcm_quantise, fir_kernels.h) -- the split kernel's pending, full and
+// per-frame stores, the generic kernels, the repair pass.  Input: interleaved f32 (in_bits = 0) or PCM as above.  Counts, end states
+// and buffered frames (f32) are those of rsmp_fir_batch_resample_bulk_device; the bytes are rsmp_f32_to_pcm_device's of that
+// entry's output, without the f32 ever reaching HBM (f32 written, f32 read, PCM written: two passes less).
+extern "C" int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
+                                                           const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
+                                                           const size_t* out_caps, size_t* consumed, size_t* produced, void* stream) {
+    if (n == 0) return RSMP_OK;
+    if (!rs || !d_in || !in_lens || !d_out_pcm || !out_caps || chunk_len == 0 || (in_bits != 0 && in_bits != 16 && in_bits != 24 && in_bits != 32) ||
+        (out_bits != 16 && out_bits != 24 && out_bits != 32))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: null / zero argument, in_bits not 0 / 16 / 24 / 32 or "
+                                                     "out_bits not 16 / 24 / 32 (any other format: f32 output and rsmp_f32_to_pcm_device)");
+    std::vector<const float*> in(n);
+    std::vector<float*> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!rs[i] || rs[i]->channels != 2)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: two-channel streams only "
+                                                         "(any other count: f32 output and rsmp_f32_to_pcm_device)");
+        if ((in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) || reinterpret_cast<uintptr_t>(d_out_pcm[i]) % 4 != 0)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input and output must be 4-byte aligned");
+        // (one launch: a stream offered more than a launch's worth of input goes through the f32 entry point, which cuts it)
+        if (chunk_len % 2 == 0 && in_lens[i] % 2 == 0 && in_lens[i] > rsmp::launch_input_values(rs[i]->mirror.ratio(), 2, chunk_len))
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: more than one launch's worth of input (46 M outputs)");
+        in[i] = static_cast<const float*>(d_in[i]);
+        out[i] = static_cast<float*>(d_out_pcm[i]);
+    }
+    return batch_bulk_piece(rs, n, in.data(), in_lens, chunk_len, out.data(), out_caps, consumed, produced, stream, static_cast<uint32_t>(in_bits),
+                            static_cast<uint32_t>(out_bits));
 }

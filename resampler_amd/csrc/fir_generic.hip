@@ -43,7 +43,9 @@ __device__ __forceinline__ float load_sample(const FirStreamDesc& d, int64_t v, 
 
 // fuse_tail: the first workgroup of every stream also copies the stream's still-buffered frames into hist_next
 // (the job of fir_tail_copy_kernel: a second launch is a fifth of a streaming call's latency).
-__global__ __launch_bounds__(kBlock) void fir_generic_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
+// OUT: the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes (fir_pcm_store).
+template <bool OUT>
+__device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
     const FirStreamDesc d = descs[blockIdx.y];
     const uint32_t tile = blockIdx.x;
     const uint32_t tile_first = tile * kFirTile;
@@ -122,9 +124,16 @@ __global__ __launch_bounds__(kBlock) void fir_generic_kernel(const FirStreamDesc
             // per-lane lerp, then horizontal sum (avx.rs:41-58)
             const float part = a1 * one_minus_frac + a2 * frac;
             const float y = group_sum8(part);
-            if (live && g == 0) d.out[static_cast<size_t>(n) * channels + c] = y;
+            if (live && g == 0) fir_out_store<OUT>(d, static_cast<size_t>(n) * channels + c, y);
         }
     }
+}
+
+__global__ __launch_bounds__(kBlock) void fir_generic_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
+    fir_generic_body<false>(descs, fuse_tail);
+}
+__global__ __launch_bounds__(kBlock) void fir_generic_pcm_out_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
+    fir_generic_body<true>(descs, fuse_tail);
 }
 
 __global__ __launch_bounds__(kBlock) void fir_tail_copy_kernel(const FirStreamDesc* __restrict__ descs) {
@@ -144,6 +153,8 @@ __global__ __launch_bounds__(kBlock) void fir_tail_copy_kernel(const FirStreamDe
 // stream's class table was built for -- the same phase rows and frac the periodic kernel pre-mixed -- and
 // outputs at an integer position take the previous frame and row 1023 where the wrap bitmap says so
 // (resampler_fir.rs:544, :562-565).
+// OUT: the marked chunks lie in a PCM buffer (FirStreamDesc::out_bits) and are rewritten as PCM.
+template <bool OUT>
 __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict__ descs, uint32_t n_streams, const NfArgs& nf) {
     if (__hip_atomic_load(nf.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nf.tag) return;
     const int g = threadIdx.x & (kLanesPerFrame - 1);
@@ -206,7 +217,7 @@ __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict_
                 }
                 const float part = a1 * one_minus_frac + a2 * frac;
                 const float y = group_sum8(part);
-                if (live && g == 0) d.out[static_cast<size_t>(n) * channels + c] = y;
+                if (live && g == 0) fir_out_store<OUT>(d, static_cast<size_t>(n) * channels + c, y);
             }
         }
         __syncthreads();
@@ -215,7 +226,11 @@ __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict_
 }
 __global__ __launch_bounds__(kBlock) void fir_repair_kernel(const FirStreamDesc* __restrict__ descs,
                                                             uint32_t n_streams, NfArgs nf) {
-    fir_repair_body(descs, n_streams, nf);
+    fir_repair_body<false>(descs, n_streams, nf);
+}
+__global__ __launch_bounds__(kBlock) void fir_repair_pcm_out_kernel(const FirStreamDesc* __restrict__ descs,
+                                                                    uint32_t n_streams, NfArgs nf) {
+    fir_repair_body<true>(descs, n_streams, nf);
 }
 struct RepairMulti {
     const FirStreamDesc* descs[kMaxRepairJobs];
@@ -226,7 +241,8 @@ struct RepairMulti {
     const FirStreamDesc* tail_descs;
     uint32_t n_tail, n_jobs;
 };
-__global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMulti m) {   // grid = (blocks, jobs [+ 1])
+template <bool OUT>
+__device__ __forceinline__ void fir_repair_multi_body(const RepairMulti& m) {   // grid = (blocks, jobs [+ 1])
     if (blockIdx.y >= m.n_jobs) {   // the tail row: a workgroup per stream, round the row
         for (uint32_t s = blockIdx.x; s < m.n_tail; s += gridDim.x) {
             const FirStreamDesc d = m.tail_descs[s];
@@ -240,28 +256,32 @@ __global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMu
         }
         return;
     }
-    fir_repair_body(m.descs[blockIdx.y], m.n_streams[blockIdx.y], m.nf[blockIdx.y]);
+    fir_repair_body<OUT>(m.descs[blockIdx.y], m.n_streams[blockIdx.y], m.nf[blockIdx.y]);
 }
+__global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMulti m) { fir_repair_multi_body<false>(m); }
+__global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_out_kernel(const RepairMulti m) { fir_repair_multi_body<true>(m); }
 
 }  // namespace
 
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done, bool* done_attached) {
+                             hipEvent_t done, bool* done_attached, uint32_t out_bits) {
     if (n_streams == 0 || !nf.words || nf.chunks == 0) return hipSuccess;
     const uint32_t total = n_streams * nf.chunks;
+    const auto kernel = out_bits != 0 ? fir_repair_pcm_out_kernel : fir_repair_kernel;
     if (done && done_attached) {
-        hipExtLaunchKernelGGL(fir_repair_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, nullptr, done, 0,
+        hipExtLaunchKernelGGL(kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, nullptr, done, 0,
                               d_descs, n_streams, nf);
         *done_attached = true;
     } else {
-        hipLaunchKernelGGL(fir_repair_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf);
+        hipLaunchKernelGGL(kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs,
-                                   uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached) {
+                                   uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached, uint32_t out_bits) {
     if (done_attached) *done_attached = false;
+    const auto kernel = out_bits != 0 ? fir_repair_multi_pcm_out_kernel : fir_repair_multi_kernel;
     bool tail_left = tail_descs != nullptr && n_tail != 0 && max_tail_values != 0;
     for (size_t j = 0; j < n_jobs;) {
         RepairMulti m{};
@@ -285,10 +305,10 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
         }
         const dim3 grid(max_total < 512 ? max_total : 512, n + (with_tail ? 1u : 0u));
         if (done && done_attached && j >= n_jobs && !tail_left) {   // (the last launch of the lot: it completes `done` itself)
-            hipExtLaunchKernelGGL(fir_repair_multi_kernel, grid, dim3(kBlock), 0, stream, nullptr, done, 0, m);
+            hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, nullptr, done, 0, m);
             *done_attached = true;
         } else {
-            hipLaunchKernelGGL(fir_repair_multi_kernel, grid, dim3(kBlock), 0, stream, m);
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, m);
         }
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
@@ -297,11 +317,11 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
 }
 
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail) {
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, uint32_t out_bits) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
     const uint32_t cz = (max_channels + kChannelsPerBlock - 1) / kChannelsPerBlock;
     const dim3 grid((max_out + kFirTile - 1) / kFirTile, n_streams, cz ? cz : 1);
-    hipLaunchKernelGGL(fir_generic_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u);
+    hipLaunchKernelGGL(out_bits != 0 ? fir_generic_pcm_out_kernel : fir_generic_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u);
     return hipGetLastError();
 }
 

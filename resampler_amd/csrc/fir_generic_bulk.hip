@@ -94,7 +94,8 @@ struct BulkPass {
     bool live;
 };
 
-template <int CH, bool FULL>   // FULL: 128 taps (every lane's four chunks exist: no tests, every LDS offset an immediate)
+// OUT: the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes (fir_pcm_store).
+template <int CH, bool FULL, bool OUT>   // FULL: 128 taps (every lane's four chunks exist: no tests, every LDS offset an immediate)
 __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkMeta* meta, const uint16_t* sorted, const float* win, uint32_t n0,
                                              uint32_t nt, uint32_t lane, uint32_t wave) {
     const uint32_t ch = CH ? static_cast<uint32_t>(CH) : d.channels, taps = d.taps;
@@ -106,6 +107,18 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
     const uint32_t chunks = FULL ? 32u : taps / 4;   // float4 chunks per row (4 .. 32); lane g owns g, g + 8, g + 16, g + 24
     const GRow coeffs = (GRow)d.coeffs;
     const GOut out = (GOut)d.out;
+    auto store1 = [&](size_t i, float y) {
+        if constexpr (OUT) fir_pcm_store(d.out, d.out_bits, i, y);
+        else out[i] = y;
+    };
+    auto store2 = [&](size_t i, float y0, float y1) {   // (two channels: i even)
+        if constexpr (OUT) {
+            fir_pcm_store(d.out, d.out_bits, i, y0);
+            fir_pcm_store(d.out, d.out_bits, i + 1, y1);
+        } else {
+            *(GOut2)(out + i) = v2f{y0, y1};
+        }
+    };
     auto fetch = [&](uint32_t base, BulkPass& p) {
         p.live = base + slot < end;
         p.i = sorted[p.live ? base + slot : begin];
@@ -138,7 +151,7 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
             }
             const v2f part = a1 * one_minus_frac + a2 * frac;
             const float y0 = bulk_sum8(part.x), y1 = bulk_sum8(part.y);
-            if (p.live && g == 0) *(GOut2)(out + n * 2) = v2f{y0, y1};
+            if (p.live && g == 0) store2(n * 2, y0, y1);
             return;
         }
         uint32_t c = 0;
@@ -166,8 +179,8 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
             const float y0 = bulk_sum8(a1.x * one_minus_frac + a2.x * frac);
             const float y1 = bulk_sum8(a1.y * one_minus_frac + a2.y * frac);
             if (p.live && g == 0) {
-                if constexpr (CH == 2) *(GOut2)(out + n * 2) = v2f{y0, y1};
-                else { out[n * ch + c] = y0; out[n * ch + c + 1] = y1; }
+                if constexpr (CH == 2) store2(n * 2, y0, y1);
+                else { store1(n * ch + c, y0); store1(n * ch + c + 1, y1); }
             }
         }
         if (CH != 2 && c < ch) {   // one channel, or an odd count's last
@@ -184,7 +197,7 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
                 }
             }
             const float y = bulk_sum8(a1 * one_minus_frac + a2 * frac);
-            if (p.live && g == 0) out[n * ch + c] = y;
+            if (p.live && g == 0) store1(n * ch + c, y);
         }
     };
     if constexpr (CH == 0 || !FULL) {   // (any channel count / fewer taps: one set of registers -- with two the general loop spills)
@@ -208,9 +221,8 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
 
 // CH: 1 / 2 = every stream of the launch has that many channels; 0 = any counts (a kernel each: side by side in one kernel the three
 // bodies shared a register allocation and spilled)
-template <int CH, bool FULL>
-__global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
-                                                                      uint32_t window_cap_frames) {
+template <int CH, bool FULL, bool OUT>
+__device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames, uint32_t window_cap_frames) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const FirStreamDesc d = descs[blockIdx.y];
     const uint32_t n0 = blockIdx.x * tile_frames;
@@ -315,7 +327,18 @@ __global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_kernel(const FirS
     __syncthreads();
 
     // ---- D: the outputs in phase order, a contiguous stretch of the list per wave, eight lanes per output frame
-    bulk_outputs<CH, FULL>(d, meta, sorted, win, n0, nt, lane, wave);
+    bulk_outputs<CH, FULL, OUT>(d, meta, sorted, win, n0, nt, lane, wave);
+}
+template <int CH, bool FULL>
+__global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
+                                                                      uint32_t window_cap_frames) {
+    fir_generic_bulk_body<CH, FULL, false>(descs, tile_frames, window_cap_frames);
+}
+// PCM output: two-channel streams (the only ones the entry admits)
+template <bool FULL>
+__global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_pcm_out_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
+                                                                              uint32_t window_cap_frames) {
+    fir_generic_bulk_body<2, FULL, true>(descs, tile_frames, window_cap_frames);
 }
 
 }  // namespace
@@ -334,8 +357,10 @@ uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double 
 }
 
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
-                                   uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels, uint32_t uniform_taps) {
+                                   uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels, uint32_t uniform_taps,
+                                   uint32_t out_bits) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
+    if (out_bits != 0 && uniform_channels != 2) return hipErrorNotSupported;
     const uint32_t tile = fir_generic_bulk_tile(max_channels, max_taps, max_ratio);
     if (tile == 0) return hipErrorNotSupported;
     const uint32_t cap = kBulkWindowBytes / (4u * max_channels);
@@ -347,9 +372,11 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
         {reinterpret_cast<const void*>(fir_generic_bulk_kernel<0, false>), reinterpret_cast<const void*>(fir_generic_bulk_kernel<0, true>)},
         {reinterpret_cast<const void*>(fir_generic_bulk_kernel<1, false>), reinterpret_cast<const void*>(fir_generic_bulk_kernel<1, true>)},
         {reinterpret_cast<const void*>(fir_generic_bulk_kernel<2, false>), reinterpret_cast<const void*>(fir_generic_bulk_kernel<2, true>)}};
-    const void* fn = fns[ci][full ? 1 : 0];
-    static bool granted[3][2] = {};   // (the attribute is per function and process: set once)
-    bool& have = granted[ci][full ? 1 : 0];
+    static const void* const fns_pcm_out[2] = {reinterpret_cast<const void*>(fir_generic_bulk_pcm_out_kernel<false>),
+                                               reinterpret_cast<const void*>(fir_generic_bulk_pcm_out_kernel<true>)};
+    const void* fn = out_bits != 0 ? fns_pcm_out[full ? 1 : 0] : fns[ci][full ? 1 : 0];
+    static bool granted[4][2] = {};   // (the attribute is per function and process: set once)
+    bool& have = granted[out_bits != 0 ? 3 : ci][full ? 1 : 0];
     if (!have) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;

@@ -291,13 +291,15 @@ void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_ou
 // PCM input (FirStreamDesc::in_bits): the two-channel fp16 builds of the 128-tap windows -- 160 taps in one round
 // (44.1 <-> 48 kHz) or two, 192 taps in two rounds (96 -> 44.1 kHz) -- exist for the three widths; kNotSupported
 // for any other geometry (the caller converts with rsmp_pcm_to_stereo_f32_device first).
-SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits) {
+// PCM output (FirStreamDesc::out_bits): the same three windows, from f32 or PCM input, as builds of their own that read the
+// width from the descriptor; kNotSupported for any other geometry (the caller converts with rsmp_f32_to_pcm_device afterwards).
+SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits) {
     const bool one_channel = geo.cg == 1, odd_count = geo.cg == 3;
     const bool wide = geo.lp > 1 || one_channel;
     const bool two_rounds = geo.rounds == 2;
     const int nk = static_cast<int>(geo.row_len / 32);
     const bool diag_long = two_rounds && diag && (nk == 6 || (nk == 5 && !wide));
-    SplitBuild b{nk, 2, false, 0, two_rounds ? 2 : 1, 0};
+    SplitBuild b{nk, 2, false, 0, two_rounds ? 2 : 1, 0, false};
     if (two_rounds) {
         b.wide = wide ? 1 : 0;
         b.diag = diag_long;
@@ -309,11 +311,13 @@ SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm
         b.diag = diag;
     }
     if (nk < 1 || nk > (two_rounds ? 6 : 5) || (two_rounds && nk < 5)) return {b, BuildError::kInvalid};
-    if (pcm_bits != 0) {
+    if (pcm_bits != 0 || out_bits != 0) {
         const bool window_ok = nk == 5 || (two_rounds && nk == 6);
-        if (wide || one_channel || odd_count || geo.planes != 2 || diag || !window_ok || (pcm_bits != 16 && pcm_bits != 24 && pcm_bits != 32))
+        const auto width_ok = [](uint32_t w) { return w == 16 || w == 24 || w == 32; };
+        if (wide || one_channel || odd_count || geo.planes != 2 || diag || !window_ok || (pcm_bits != 0 && !width_ok(pcm_bits)) ||
+            (out_bits != 0 && !width_ok(out_bits)))
             return {b, BuildError::kNotSupported};
-        b = SplitBuild{nk, 2, false, 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits)};
+        b = SplitBuild{nk, 2, false, 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0};
     }
     return {b, BuildError::kNone};
 }

@@ -18,7 +18,7 @@ namespace rsmp {
 struct FirStreamDesc {
     const float* in;               // frames accepted in this launch (device)
     const float* hist;             // frames buffered before the launch (device)
-    float* out;                    // output frames (device)
+    float* out;                    // output frames (device): interleaved f32, or PCM bytes (out_bits)
     const float* coeffs;           // [1024][taps] polyphase table (device)
     const rsmp_fir_segment* segs;  // exact position runs, sorted by out_start (device)
     const uint32_t* tile_seg;      // index of the run containing output frame tile*kFirTile
@@ -47,7 +47,10 @@ struct FirStreamDesc {
     // a frame, converted where it is read as resample/src/main.rs:128-137 converts it (fir_pcm_value below); `hist`
     // -- the frames an earlier launch left buffered -- is f32 always.
     uint32_t in_bits;
-    uint32_t pad_bits;
+    // 0: `out` receives interleaved f32.  16 / 24 / 32: `out` receives little-endian PCM of that width (24-bit packed, three
+    // bytes a sample), every sum quantised where it is stored (fir_pcm_quantise below); one width for all the streams of a
+    // launch.  `hist_next` -- the frames that stay buffered -- is f32 always.
+    uint32_t out_bits;
 };
 
 // One sample of a stream's `in`, index `i` in values (frame * channels + channel).
@@ -63,11 +66,48 @@ __device__ __forceinline__ float fir_in_value(const FirStreamDesc& d, size_t i) 
     return d.in_bits == 0 ? d.in[i] : fir_pcm_value(d.in, d.in_bits, i);
 }
 
+// f32 -> PCM code of `bits` (16 / 24 / 32): round_half_to_even(x * 2^(bits-1)), saturated to [-2^(bits-1), 2^(bits-1) - 1]; NaN -> 0.
+// The product is exact (a power of two; an overflow to +-inf saturates like any other value out of range), +inf is the top code
+// and -inf the bottom one, -0.0 and denormals give 0.  No dither.  The 32-bit top code 2^31 - 1 is no f32 value: the comparison
+// saturates, not a clamp in f32.  Decoding a code with fir_pcm_value and quantising it again at the same width is the identity
+// for 16 and 24 bits.  For 32 bits it is NOT: the reference's input divisor is -2^31 (main.rs:131), the scale here is +2^31 -- an
+// f32 value means what it says on the way out --, so that round trip gives saturate(-f32(s)): polarity inverted, the bottom
+// code saturated to the top one.
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise(float x, uint32_t bits) {
+    const float v = rintf(x * (bits == 16 ? 32768.0f : bits == 24 ? 8388608.0f : 2147483648.0f));
+    if (!(v == v)) return 0;
+    if (bits == 32) return v >= 2147483648.0f ? INT32_MAX : v <= -2147483648.0f ? INT32_MIN : static_cast<int32_t>(v);
+    const float top = bits == 16 ? 32767.0f : 8388607.0f, bottom = bits == 16 ? -32768.0f : -8388608.0f;
+    return static_cast<int32_t>(v > top ? top : v < bottom ? bottom : v);
+}
+// One sample of a stream's PCM `out`, index `i` in values: the lane writes the sample's own bytes and no others.
+__device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y) {
+    const int32_t q = fir_pcm_quantise(y, bits);
+    if (bits == 16) {
+        static_cast<int16_t*>(out)[i] = static_cast<int16_t>(q);
+    } else if (bits == 32) {
+        static_cast<int32_t*>(out)[i] = q;
+    } else {
+        uint8_t* p = static_cast<uint8_t*>(out) + 3 * i;
+        p[0] = static_cast<uint8_t>(q);
+        p[1] = static_cast<uint8_t>(q >> 8);
+        p[2] = static_cast<uint8_t>(q >> 16);
+    }
+}
+// Value `i` of a stream's output.  OUT: the PCM-output builds of the generic kernels and of the repair pass (out_bits != 0); the
+// f32 builds do not read the field.
+template <bool OUT>
+__device__ __forceinline__ void fir_out_store(const FirStreamDesc& d, size_t i, float y) {
+    if constexpr (OUT) fir_pcm_store(d.out, d.out_bits, i, y);
+    else d.out[i] = y;
+}
+
 constexpr uint32_t kFirTile = 32;   // output frames per workgroup tile (generic kernel): one pass of 32 x 8 lanes
 
 // Generic kernel: any ratio, reference-form two-row interpolation; grid = (max tiles, streams).
+// (out_bits, here and below: FirStreamDesc::out_bits of the launch's streams -- != 0 selects the builds that store PCM)
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false);
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, uint32_t out_bits = 0);
 // The same arithmetic for LONG launches (fir_generic_bulk.hip): tiles of up to 4096 output frames per workgroup, their outputs sorted
 // by phase row, the tile's input window in LDS.  hipErrorNotSupported where no tile fits the LDS (fir_generic_bulk_tile == 0);
 // does not copy the tails (launch_fir_tail_copy).
@@ -75,14 +115,15 @@ uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double 
 // (uniform_channels: 1 / 2 = every stream has that many channels -- the builds for them --, anything else = any counts)
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels = 0,
-                                   uint32_t uniform_taps = 0);   // (uniform_taps: 128 = every stream has 128 taps)
+                                   uint32_t uniform_taps = 0,    // (uniform_taps: 128 = every stream has 128 taps)
+                                   uint32_t out_bits = 0);       // (PCM output: two-channel streams only, hipErrorNotSupported otherwise)
 constexpr uint32_t kFirBulkMinOut = 8192;   // launches whose longest generic stream produces fewer frames keep fir_generic_kernel
 // Re-evaluates, in the reference's two-row form, the output chunks a periodic launch marked as non-finite
 // (fir_nonfinite.h); exits at once when the launch marked nothing.
 // (done / done_attached, here and in launch_fir_tail_copy: as in launch_fir_repair_multi below -- the launch completes `done`
 // itself; *done_attached stays false when there was nothing to launch)
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done = nullptr, bool* done_attached = nullptr);
+                             hipEvent_t done = nullptr, bool* done_attached = nullptr, uint32_t out_bits = 0);
 // The same for up to eight groups of streams (each with its own marks) in one launch.
 struct RepairJob {
     const FirStreamDesc* d_descs;
@@ -95,7 +136,8 @@ constexpr uint32_t kMaxRepairJobs = 8;
 // (done / done_attached: an event the LAST of these launches completes itself -- hipExtLaunchKernel's stop event, no packet of its
 // own behind the kernel as hipEventRecord puts there; *done_attached = false: there was no such launch, record it yourself)
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs = nullptr,
-                                   uint32_t n_tail = 0, uint32_t max_tail_values = 0, hipEvent_t done = nullptr, bool* done_attached = nullptr);
+                                   uint32_t n_tail = 0, uint32_t max_tail_values = 0, hipEvent_t done = nullptr, bool* done_attached = nullptr,
+                                   uint32_t out_bits = 0);
 // Copies the still-buffered tail of [hist|in] into hist_next; grid = (blocks, streams).
 hipError_t launch_fir_tail_copy(const FirStreamDesc* d_descs, uint32_t n_streams,
                                 uint32_t max_tail_values, hipStream_t stream, hipEvent_t done = nullptr, bool* done_attached = nullptr);

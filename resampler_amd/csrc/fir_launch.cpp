@@ -58,7 +58,7 @@ struct Launch {
     rsmp_fir* const leader;
     std::vector<FirJob>& jobs;
     const hipStream_t stream;
-    const uint32_t pcm_bits;
+    const uint32_t pcm_bits, out_bits;
     const size_t n;
     // launch order: generic jobs, then periodic jobs grouped by geometry (one launch per geometry)
     std::vector<size_t> order;
@@ -79,7 +79,8 @@ struct Launch {
     bool tail_fused = false;   // the last main kernel copies the tails as well: no tail-copy launch
     hipEvent_t done = nullptr;
     bool done_attached = false;
-    Launch(rsmp_fir* l, std::vector<FirJob>& j, hipStream_t s, uint32_t bits) : leader(l), jobs(j), stream(s), pcm_bits(bits), n(j.size()) {}
+    Launch(rsmp_fir* l, std::vector<FirJob>& j, hipStream_t s, uint32_t bits, uint32_t obits)
+        : leader(l), jobs(j), stream(s), pcm_bits(bits), out_bits(obits), n(j.size()) {}
 };
 
 int order_streams(Launch& L) {
@@ -109,17 +110,24 @@ int bind_and_group(Launch& L) {
         if (!found) L.groups.push_back(Group{j.r->periodic.geo, {i}});
     }
     for (const Group& g : L.groups) for (size_t i : g.members) L.order.push_back(i);
-    if (L.pcm_bits != 0) {
+    // PCM input and PCM output have one admission rule: two-channel streams; periodic groups on the split kernel's builds for them
+    if (L.pcm_bits != 0 || L.out_bits != 0) {
         for (const FirJob& j : jobs)
-            if (j.r->channels != 2) return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input: two-channel streams only");
+            if (j.r->channels != 2)
+                return fail(RSMP_ERR_INVALID_ARGUMENT, L.pcm_bits != 0 ? "PCM input: two-channel streams only"
+                                                                       : "PCM output: two-channel streams only (convert with rsmp_f32_to_pcm_device afterwards)");
         for (const Group& g : L.groups) {
             const uint32_t nk = g.geo.row_len / 32;
             const bool ok = g.geo.mfma == 3 && g.geo.planes == 2 && g.geo.lp == 1 && g.geo.cg == 2 &&
                             ((g.geo.rounds == 1 && nk == 5) || (g.geo.rounds == 2 && (nk == 5 || nk == 6)));
-            if (!ok)
+            if (!ok && L.pcm_bits != 0)
                 return fail(RSMP_ERR_INVALID_ARGUMENT,
                             "PCM input is read in place by the two-channel split kernel of the 128-tap rate pairs only "
                             "(44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): convert with rsmp_pcm_to_stereo_f32_device first");
+            if (!ok)
+                return fail(RSMP_ERR_INVALID_ARGUMENT,
+                            "PCM output is written in place by the two-channel split kernel of the 128-tap rate pairs only "
+                            "(44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): take f32 output and convert with rsmp_f32_to_pcm_device");
         }
     }
     return RSMP_OK;
@@ -253,6 +261,7 @@ int fill_descriptors(Launch& L) {
         ds.abs_out = r->mirror.abs_out();
         ds.abs_consumed = r->mirror.abs_consumed();
         ds.in_bits = L.pcm_bits;
+        ds.out_bits = L.out_bits;
         if (ds.tail_frames * ch > L.max_tail_values) L.max_tail_values = ds.tail_frames * ch;
         if (!pl.periodic) {
             ds.segs = reinterpret_cast<const rsmp_fir_segment*>(L.d + pp.seg_off);
@@ -309,10 +318,10 @@ int launch_generic(Launch& L) {
         RSMP_HIP_CHECK(launch_fir_generic_bulk(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic,
                                                L.max_taps_generic, L.max_ratio_generic, L.stream,
                                                L.min_ch_generic == L.max_ch_generic ? L.max_ch_generic : 0u,
-                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u));
+                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.out_bits));
     } else if (L.n_generic)
         RSMP_HIP_CHECK(launch_fir_generic(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic, L.stream,
-                                          L.tail_fused));
+                                          L.tail_fused, L.out_bits));
     return RSMP_OK;
 }
 
@@ -380,13 +389,13 @@ int launch_periodic_groups(Launch& L) {
         if (++leader->nf_tag == 0) leader->nf_tag = 1;
         rp.nf.tag = leader->nf_tag;
         const uint64_t key = items_key(L, g, max_blocks);
-        if (L.groups.size() > 1 && g.geo.mfma == 3 && L.pcm_bits == 0) {
+        if (L.groups.size() > 1 && g.geo.mfma == 3 && L.pcm_bits == 0 && L.out_bits == 0) {
             // several rate pairs in one batch: those of the split kernel share launches (launch_fir_split_multi: one item
             // table launch, one kernel launch per kernel build among them), as in rsmp_fir_lockstep_run
             split_jobs.push_back(SplitJob{L.d_descs + first, static_cast<uint32_t>(g.members.size()), &g.geo, max_blocks, rp.nf});
         } else {
             RSMP_HIP_CHECK(launch_fir_periodic(L.d_descs + first, static_cast<uint32_t>(g.members.size()), g.geo, max_blocks,
-                                               leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.pcm_bits));
+                                               leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.pcm_bits, L.out_bits));
         }
         first += g.members.size();
     }
@@ -453,11 +462,11 @@ int launch_followups(Launch& L) {
         std::vector<RepairJob> rj;
         for (const Repair& rp : L.repairs) rj.push_back(RepairJob{L.d_descs + rp.first, rp.count, rp.nf});
         RSMP_HIP_CHECK(launch_fir_repair_multi(rj.data(), rj.size(), L.stream, nullptr, 0, 0, repair_last ? L.done : nullptr,
-                                               &L.done_attached));
+                                               &L.done_attached, L.out_bits));
     } else {
         for (const Repair& rp : L.repairs)
             RSMP_HIP_CHECK(launch_fir_repair(L.d_descs + rp.first, rp.count, rp.nf, L.stream, repair_last ? L.done : nullptr,
-                                             &L.done_attached));
+                                             &L.done_attached, L.out_bits));
     }
     if (n > n_generic && L.max_wraps > 0)
         RSMP_HIP_CHECK(launch_fir_wrap_fixup(L.d_descs + n_generic, static_cast<uint32_t>(n - n_generic), L.max_wraps, L.stream,
@@ -484,8 +493,8 @@ void commit(Launch& L) {
 
 }  // namespace
 
-int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits) {
-    Launch L(leader, jobs, stream, pcm_bits);
+int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits, uint32_t out_bits) {
+    Launch L(leader, jobs, stream, pcm_bits, out_bits);
     if (int rc = order_streams(L)) return rc;
     if (int rc = bind_and_group(L)) return rc;
     lay_out_workspace(L);

@@ -16,8 +16,8 @@ struct FirJob {
     rsmp_fir* r;
     const float* d_in;
     size_t in_len;     // f32 values offered
-    float* d_out;
-    size_t out_cap;    // f32 values of room
+    float* d_out;      // (PCM output: the bytes' address)
+    size_t out_cap;    // values (samples) of room
     size_t chunk_len;  // 0: one reference call with output capacity out_cap; else bulk loop
     std::shared_ptr<Plan> plan;
     size_t consumed() const { return plan->accepted_frames * r->channels; }
@@ -43,6 +43,7 @@ int order_behind_handle(rsmp_fir* h, hipStream_t stream, const FirLaunchEvent*& 
 // `leader` owns the launch workspace.
 // pcm_bits != 0: every job's d_in is a WAV file's PCM of that width, read in place (FirStreamDesc::in_bits): two-channel
 // streams on the generic kernel (short launches) or the split kernel's PCM builds.
-int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0);
+// out_bits != 0: every job's d_out receives PCM of that width (FirStreamDesc::out_bits); the same streams and kernels.
+int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0);
 
 }  // namespace rsmp

@@ -79,8 +79,10 @@ struct SplitBuild {
     int wide;         // 0 two channels, 1 channel pairs, 2 one channel, 3 an odd channel count
     int rounds;
     int bits;         // PCM input of that width (0: f32)
+    bool pcm_out;     // PCM output (its width is the descriptor's, read at run time)
     bool operator==(const SplitBuild& o) const {
-        return nk == o.nk && planes == o.planes && diag == o.diag && wide == o.wide && rounds == o.rounds && bits == o.bits;
+        return nk == o.nk && planes == o.planes && diag == o.diag && wide == o.wide && rounds == o.rounds && bits == o.bits &&
+               pcm_out == o.pcm_out;
     }
 };
 enum class BuildError { kNone, kInvalid, kNotSupported };   // the launchers' hipErrorInvalidValue / hipErrorNotSupported
@@ -88,8 +90,8 @@ struct SplitChoice {
     SplitBuild build;
     BuildError error;
 };
-// diag: RSMP_FIR_DEBUG or RSMP_FIR_WTRACE is set; pcm_bits: FirStreamDesc::in_bits of the launch's streams.
-SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits);
+// diag: RSMP_FIR_DEBUG or RSMP_FIR_WTRACE is set; pcm_bits / out_bits: FirStreamDesc::in_bits / out_bits of the launch's streams.
+SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits = 0);
 // Slot of launch_fir_periodic's kernel table for a geometry of the vector or f32 matrix-core kernels, or -1 (no such
 // build).  mfma_dbg: RSMP_FIR_MFMA_DBG (0 .. 3); mfma_ring: mfma_ring_knob().
 constexpr int kPeriodicSlots = 20;

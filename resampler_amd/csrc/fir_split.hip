@@ -118,6 +118,7 @@ struct WaveTrace {
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -476,10 +477,13 @@ __device__ __forceinline__ uint32_t consumer_index(uint32_t w) { return w < 6 ? 
 // other's registers (two wrap passes against one + the 40 registers of a stager's loads).
 // ROUNDS: lane tasks per stager lane and item -- 2 for periods of 161 .. 320 frames (96 -> 44.1 kHz, 96 -> 48 kHz): both
 // rounds' loads are in flight together, one item ahead, like the single round's.
-template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
+// OUT: the streams' `out` is PCM (FirStreamDesc::out_bits: 16 / 24 / 32, one width per launch, read from the descriptor by
+// these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise).
+template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0, bool OUT = false>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
 __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__ descs, const SplitArgs& g,
                                                const uint32_t wg, const uint32_t n_wgs) {   // workgroup `wg` of the `n_wgs` that share g's items
     static_assert(ROUNDS == 1 || ((WIDE == 0 || WIDE == 1) && PLANES == 2), "two rounds: two channels or channel pairs, fp16 planes");
+    static_assert(!OUT || (WIDE == 0 && PLANES == 2 && !DIAG), "PCM output: the two-channel fp16 build");
     constexpr uint32_t kRowBytes = row_bytes(PLANES);
     const uint32_t fs = WIDE ? g.cstride : 2u;   // floats per frame
     const uint32_t fsb = fs * 4u;                // bytes per frame
@@ -1343,9 +1347,76 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     bool pend_ph = false;   // WIDE == 3: the pending sums are the last channel's
     bool pend = false;
     typedef v2f __attribute__((address_space(1)))* g_f2_ptr;
+    // PCM output: the launch's width (wave-uniform, in a scalar register) and the bytes of a two-channel frame
+    uint32_t out_bits = 0, out_fb = 0;
+    if constexpr (OUT) {
+        typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
+        out_bits = __builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[0].out_bits));
+        out_fb = out_bits >> 2;
+    }
+    typedef uint8_t __attribute__((address_space(1)))* g_u8_ptr;
+    typedef uint16_t __attribute__((address_space(1)))* g_u16_ptr;
+    typedef uint32_t __attribute__((address_space(1)))* g_u32_ptr;
+    // PCM output, one frame (y0, y1) at `o`: 4 bytes (4-byte aligned), 6 bytes (2-byte aligned) or 8 bytes (4-byte aligned: the
+    // buffer's own alignment is all the entry asks for)
+    auto store_frame_pcm = [&](g_f32_ptr o, float y0, float y1) {
+        const uint32_t q0 = static_cast<uint32_t>(fir_pcm_quantise(y0, out_bits)), q1 = static_cast<uint32_t>(fir_pcm_quantise(y1, out_bits));
+        if (out_bits == 16) {
+            *(g_u32_ptr)o = (q0 & 0xFFFFu) | (q1 << 16);
+        } else if (out_bits == 24) {
+            ((g_u16_ptr)o)[0] = static_cast<uint16_t>(q0);
+            ((g_u16_ptr)o)[1] = static_cast<uint16_t>(((q0 >> 16) & 0xFFu) | (q1 << 8));
+            ((g_u16_ptr)o)[2] = static_cast<uint16_t>(q1 >> 8);
+        } else {
+            typedef v2u __attribute__((address_space(1), aligned(4)))* g_u2_ptr;
+            *(g_u2_ptr)o = v2u{q0, q1};
+        }
+    };
+    // PCM output, a lane's four frames x two channels at `o`: 16 bytes (4-byte aligned), 24 bytes (2-byte aligned) or 32 bytes
+    // (4-byte aligned).  No store is wider than the alignment of its address, every byte is written once, none beside the 4 frames.
+    auto store_frames_pcm = [&](g_f32_ptr o, const v4f& lo, const v4f& hi) {
+        const float y[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t q[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) q[i] = static_cast<uint32_t>(fir_pcm_quantise(y[i], out_bits));
+        if (out_bits == 16) {
+            typedef v4u __attribute__((address_space(1), aligned(4)))* g_u4a4_ptr;
+            *(g_u4a4_ptr)o = v4u{(q[0] & 0xFFFFu) | (q[1] << 16), (q[2] & 0xFFFFu) | (q[3] << 16), (q[4] & 0xFFFFu) | (q[5] << 16), (q[6] & 0xFFFFu) | (q[7] << 16)};
+        } else if (out_bits == 24) {
+            // the 24 bytes as six words; at an address that is 2 mod 4 they leave as a half word, five words cut from neighbouring
+            // pairs (shift 16) and a half word -- otherwise as the six words (shift 0)
+            uint32_t w[6];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t a = q[4 * h] & 0xFFFFFFu, b = q[4 * h + 1] & 0xFFFFFFu, c = q[4 * h + 2] & 0xFFFFFFu, d3 = q[4 * h + 3] & 0xFFFFFFu;
+                w[3 * h] = a | (b << 24);
+                w[3 * h + 1] = (b >> 8) | (c << 16);
+                w[3 * h + 2] = (c >> 16) | (d3 << 8);
+            }
+            const uintptr_t addr = reinterpret_cast<uintptr_t>((uint8_t*)(g_u8_ptr)o);
+            const bool odd = (addr & 2u) != 0;
+            const uint32_t sh = odd ? 16u : 0u;
+            g_u32_ptr o4 = (g_u32_ptr)((g_u8_ptr)o + (odd ? 2 : 0));
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+                o4[k] = static_cast<uint32_t>(((static_cast<uint64_t>(w[k + 1]) << 32) | w[k]) >> sh);
+            if (odd) {
+                ((g_u16_ptr)o)[0] = static_cast<uint16_t>(w[0]);
+                ((g_u16_ptr)o)[11] = static_cast<uint16_t>(w[5] >> 16);
+            } else {
+                o4[5] = w[5];
+            }
+        } else {
+            typedef v4u __attribute__((address_space(1), aligned(4)))* g_u4a4_ptr;
+            ((g_u4a4_ptr)o)[0] = v4u{q[0], q[1], q[2], q[3]};
+            ((g_u4a4_ptr)o)[1] = v4u{q[4], q[5], q[6], q[7]};
+        }
+    };
     // a lane's four frames x two channels: 32 contiguous bytes, or (WIDE) 8 bytes in each of four frames
     auto store_frames = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, bool ph) {
-        if constexpr (WIDE) {
+        if constexpr (OUT) {
+            store_frames_pcm(o, lo, hi);
+        } else if constexpr (WIDE) {
             if (kOdd && ph) {   // the last channel alone: one value per frame
                 o[0] = lo.x;
                 o[fs] = lo.z;
@@ -1511,7 +1582,9 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         // a non-finite sum (inf / NaN sample, or one too large for the 16-bit planes): the chunk is redone
         // in the reference's form by the repair launch
         nf_mark(g.nf, item_bad || nf_is_bad(mono || phantom(cu.cur_pair) ? (acc0.x + acc0.y) + (acc0.z + acc0.w) : nf_sum8(acc0, acc1)), d.sidx, n0, 4, n_limit);
-        g_f32_ptr o = (g_f32_ptr)d.out + static_cast<int64_t>(n0) * fs + (WIDE ? 2 * cu.cur_pair : 0u);
+        g_f32_ptr o;
+        if constexpr (OUT) o = (g_f32_ptr)((g_u8_ptr)d.out + static_cast<int64_t>(n0) * out_fb);   // (a byte address: out_fb bytes a frame)
+        else o = (g_f32_ptr)d.out + static_cast<int64_t>(n0) * fs + (WIDE ? 2 * cu.cur_pair : 0u);
         const v4f lo = v4f{acc0.x, acc1.x, acc0.y, acc1.y};
         const v4f hi = v4f{acc0.z, acc1.z, acc0.w, acc1.w};
         if (!(dbg & 16)) {
@@ -1548,7 +1621,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                 for (int r = 0; r < 4; ++r) {
                     const int32_t n = n0 + r;
                     if (j0 + r < g.b && n >= 0 && n < n_limit) {
-                        if (mono) o[r] = v[2 * r];
+                        if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1]);
+                        else if (mono) o[r] = v[2 * r];
                         else if (phantom(cu.cur_pair)) o[fs * r] = v[2 * r];
                         else if constexpr (kOdd) *((g_f2u_ptr)(o + fs * r)) = v2f{v[2 * r], v[2 * r + 1]};
                         else *((g_f2_ptr)(o + fs * r)) = v2f{v[2 * r], v[2 * r + 1]};
@@ -1570,6 +1644,11 @@ template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0>
 __global__ __launch_bounds__(1024) void fir_split_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
     static_assert(BITS == 0 || (WIDE == 0 && PLANES == 2 && !DIAG), "PCM input: the two-channel fp16 build");
     fir_split_body<NK, PLANES, DIAG, WIDE, ROUNDS, BITS>(descs, g, blockIdx.x, gridDim.x);
+}
+// PCM output (FirStreamDesc::out_bits) from the two-channel fp16 builds of the 128-tap windows, f32 or PCM input.
+template <int NK, int ROUNDS, int BITS>
+__global__ __launch_bounds__(1024) void fir_split_pcm_out_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
+    fir_split_body<NK, 2, false, 0, ROUNDS, BITS, true>(descs, g, blockIdx.x, gridDim.x);
 }
 template <int NK, int PLANES, int WIDE, int ROUNDS>
 __global__ __launch_bounds__(1024) void fir_split_multi_kernel(const SplitMulti m) {
@@ -1662,7 +1741,9 @@ hipError_t items_workspace(int device, hipStream_t stream, size_t need, uint64_t
 // geometry runs on).
 namespace {
 const void* split_kernel_for(const SplitBuild& build) {
-#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
+#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B, false}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
+#define RSMP_SPLIT_OUT1(NK, R, B) {SplitBuild{NK, 2, false, 0, R, B, true}, reinterpret_cast<const void*>(fir_split_pcm_out_kernel<NK, R, B>)}
+#define RSMP_SPLIT_OUT(B) RSMP_SPLIT_OUT1(5, 1, B), RSMP_SPLIT_OUT1(5, 2, B), RSMP_SPLIT_OUT1(6, 2, B)
 #define RSMP_SPLIT_1TO5(P, D, W) RSMP_SPLIT(1, P, D, W, 1, 0), RSMP_SPLIT(2, P, D, W, 1, 0), RSMP_SPLIT(3, P, D, W, 1, 0), RSMP_SPLIT(4, P, D, W, 1, 0), RSMP_SPLIT(5, P, D, W, 1, 0)
 #define RSMP_SPLIT_PCM(B) RSMP_SPLIT(5, 2, false, 0, 1, B), RSMP_SPLIT(5, 2, false, 0, 2, B), RSMP_SPLIT(6, 2, false, 0, 2, B)
     static const struct { SplitBuild build; const void* fn; } table[] = {
@@ -1675,7 +1756,11 @@ const void* split_kernel_for(const SplitBuild& build) {
         // (diagnostic builds: config 5's geometry, the 192-tap window; config 4's two-channel streams)
         RSMP_SPLIT(5, 2, true, 0, 2, 0), RSMP_SPLIT(6, 2, true, 0, 2, 0), RSMP_SPLIT(6, 2, true, 1, 2, 0),
         // PCM input: the two-channel fp16 builds of the 128-tap windows
-        RSMP_SPLIT_PCM(16), RSMP_SPLIT_PCM(24), RSMP_SPLIT_PCM(32)};
+        RSMP_SPLIT_PCM(16), RSMP_SPLIT_PCM(24), RSMP_SPLIT_PCM(32),
+        // PCM output (its width read from the descriptor) from the same three builds, for f32 input and the three PCM widths
+        RSMP_SPLIT_OUT(0), RSMP_SPLIT_OUT(16), RSMP_SPLIT_OUT(24), RSMP_SPLIT_OUT(32)};
+#undef RSMP_SPLIT_OUT
+#undef RSMP_SPLIT_OUT1
 #undef RSMP_SPLIT_PCM
 #undef RSMP_SPLIT_1TO5
 #undef RSMP_SPLIT
@@ -1687,10 +1772,10 @@ const void* split_kernel_for(const SplitBuild& build) {
 
 hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, const PeriodicGeometry& geo,
                             uint32_t max_blocks, uint32_t cus, bool fuse_tail, const NfArgs& nf, hipStream_t stream,
-                            uint64_t items_key, uint32_t pcm_bits) {
+                            uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits) {
     static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
     const bool diag = fir_debug_knob() != 0 || wtrace_path != nullptr;
-    const SplitChoice choice = split_build_for(geo, diag, pcm_bits);
+    const SplitChoice choice = split_build_for(geo, diag, pcm_bits, out_bits);
     if (choice.error != BuildError::kNone) return choice.error == BuildError::kInvalid ? hipErrorInvalidValue : hipErrorNotSupported;
     const void* fn = split_kernel_for(choice.build);
     if (fn == nullptr) return hipErrorInvalidValue;

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""What PCM output fused into the FIR stores buys, at the headline shape: 64 streams x 2^20 frames, 2 ch, 44.1 -> 48 kHz,
+128 taps (Sample64 / Db90), one bulk launch per step on fresh streams.
+
+For 16- and 24-bit output, per step:
+  (a) the f32-output launch                                   rsmp_fir_batch_resample_bulk_device
+  (b) (a) + rsmp_f32_to_pcm_device over every stream's output (the two-pass route a caller has without the fused entry)
+  (c) the fused launch from f32 input                         rsmp_fir_batch_resample_bulk_pcm_out_device, in_bits = 0
+  (d) the fused launch from PCM input of the same width       ... in_bits = out_bits
+Launch times are the handle's profiling events (rsmp_fir_set_profiling: the main kernels of the launch, as bench.py's
+roofline.kernel_ms); the conversion pass of (b) is bracketed by events on the same stream.  A repetition is --burst steps enqueued
+back to back (no host synchronisation between them: the GPU stays busy, as in bench.py's timed loop) and counts as the mean of their
+event pairs; every row starts with --spinup seconds of its own steps.  Median of --reps repetitions with min / max; row (a) is
+measured again at the end (a_f32_output_again) to show what the box's drift over the run amounts to.  Prints one JSON object.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stats(v):
+    v = np.asarray(v, np.float64)
+    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(v.min()), 4), "max_ms": round(float(v.max()), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=64)
+    ap.add_argument("--frames", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--burst", type=int, default=8)
+    ap.add_argument("--spinup", type=float, default=1.0)
+    ap.add_argument("--chunk", type=int, default=512)
+    a = ap.parse_args()
+
+    import torch
+    import resampler_amd as ra
+    from resampler_amd import synth
+
+    dev = torch.device("cuda:0")
+    S, N, chunk = a.streams, a.frames, a.chunk
+    hs = [ra.ResamplerFir.new(2, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000, ra.Latency.Sample64, ra.Attenuation.Db90) for _ in range(S)]
+    batch = ra.FirBatch(hs)
+    batch.device_planner = False   # (the fused entry is planned on the host: the same planner for every row of the table)
+    base = torch.from_numpy(synth.sweep(N, 2, 44100.0)).to(dev)
+    gains = torch.linspace(0.5, 1.0, S, device=dev)
+    d_f32 = [(base * gains[i]).contiguous() for i in range(S)]
+    cap = max(h.bulk_output_bound(2 * N, chunk) for h in hs)
+    d_out = [torch.empty(cap, device=dev) for _ in range(S)]
+    batch.bind(d_f32, d_out)
+    stream = ra.torch_stream()
+    hs[0].set_profiling(True)
+    assert 1 <= a.burst <= 64   # (the handle keeps the event pairs of its last 64 launches)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.burst)]
+
+    def run(step):
+        t_end = time.perf_counter() + a.spinup
+        while time.perf_counter() < t_end:
+            batch.reset()
+            step(*ev[0])
+            torch.cuda.synchronize()
+        times = []
+        for _ in range(a.reps):
+            hs[0].set_profiling(True)   # (starts the handle's count of profiled launches again)
+            extra = False
+            for k in range(a.burst):
+                batch.reset()
+                extra = step(*ev[k])
+            torch.cuda.synchronize()
+            t, n = hs[0].mean_kernel_ms()
+            assert n == a.burst
+            if extra:
+                t += sum(e0.elapsed_time(e1) for e0, e1 in ev) / a.burst
+            times.append(t)
+        return times
+
+    result = {"streams": S, "frames": N, "reps": a.reps, "rows": {}}
+    produced = [0]
+
+    def f32_launch(e0=None, e1=None):
+        _, p = batch.resample_bulk_device(chunk, stream)
+        produced[0] = [int(v) for v in p]
+        return False
+
+    t_a = run(f32_launch)
+    result["rows"]["a_f32_output"] = stats(t_a)
+    for bits in (16, 24):
+        nb = bits // 8
+        d_pcm_out = [torch.empty(cap * nb, dtype=torch.uint8, device=dev) for _ in range(S)]
+        d_pcm_in = [torch.empty(2 * N * nb, dtype=torch.uint8, device=dev) for _ in range(S)]
+        for x, p in zip(d_f32, d_pcm_in):
+            ra.f32_to_pcm_device(x, bits, p, stream)
+
+        def two_pass(e0, e1):
+            f32_launch()
+            e0.record()
+            for o, q, n in zip(d_out, d_pcm_out, produced[0]):
+                ra.f32_to_pcm_device(o[:n], bits, q, stream)
+            e1.record()
+            return True
+
+        def fused_f32(e0, e1):
+            batch.resample_bulk_pcm_out_device(d_f32, 0, d_pcm_out, bits, chunk, stream)
+            return False
+
+        def fused_pcm(e0, e1):
+            batch.resample_bulk_pcm_out_device(d_pcm_in, bits, d_pcm_out, bits, chunk, stream)
+            return False
+
+        t_b, t_c, t_d = run(two_pass), run(fused_f32), run(fused_pcm)
+        result["rows"][f"b_f32_output_then_f32_to_pcm_{bits}"] = stats(t_b)
+        result["rows"][f"c_fused_{bits}_from_f32"] = stats(t_c)
+        result["rows"][f"d_fused_{bits}_from_pcm_{bits}"] = stats(t_d)
+        result["rows"][f"gain_b_minus_c_{bits}_ms"] = round(float(np.median(t_b) - np.median(t_c)), 4)
+        result["rows"][f"c_minus_a_{bits}_ms"] = round(float(np.median(t_c) - np.median(t_a)), 4)
+        del d_pcm_out, d_pcm_in
+    result["rows"]["a_f32_output_again"] = stats(run(f32_launch))
+    hs[0].set_profiling(False)
+    result["kernel_variant"] = hs[0].kernel_variant()
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
