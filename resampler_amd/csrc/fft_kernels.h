@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "fft_launch.h"
+
 namespace rsmp {
 
 constexpr int kMaxFftStages = 8;
@@ -40,24 +42,18 @@ struct FftStreamDesc {
     uint32_t pad;
 };
 
-// Blocks a workgroup walks in sequence (carrying the overlap on chip); the first block of a run
-// that does not start the launch recomputes its predecessor as halo.
-constexpr uint32_t kFftRun = 16;
-
 // pcm_bits != 0: every stream's `in` is PCM of that width (FftStreamDesc::in_bits); hipErrorNotSupported where no kernel
-// that reads PCM serves the plan / channel count.
+// that reads PCM serves the plan / channel count.  Which kernel, grid, block and LDS a launch gets: fft_launch.h.
 hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
                           uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
                           hipStream_t stream, uint32_t pcm_bits = 0);
-// Wave-per-transform build (fft_wave.hip) for the plans it is instantiated for; hipErrorNotSupported
-// otherwise (launch_fft_ola then falls back to the workgroup kernels by itself).
-hipError_t launch_fft_ola_wave(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
-                               uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                               hipStream_t stream);
-// One wave per two-channel stream, the frame (L, R) as the complex sample L + i R (fft_pair.hip); hipErrorNotSupported for
-// the plans it is not instantiated for.
-hipError_t launch_fft_ola_pair(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams, uint32_t max_blocks,
-                               hipStream_t stream, uint32_t pcm_bits = 0);
+// The kernel files' launchers: the build `c` names (fft_choose), launched as it says; hipErrorNotSupported where the file
+// was not built with it (the timing experiments' builds).  fft_pair.hip: one wave per two-channel stream, the frame
+// (L, R) as the complex sample L + i R; fft_wave.hip: a wave per channel; fft_kernels.hip: the workgroup kernels.
+hipError_t launch_fft_ola_pair(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream);
+hipError_t launch_fft_ola_wave(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream);
+hipError_t launch_fft_ola_workgroup(FftLaunch c, const FftRequest& rq, const FftPlanDev& plan, const FftStreamDesc* d_descs,
+                                    hipStream_t stream);
 // Whether this library's wave kernels are the operation-for-operation build (libresampler_amd_fftexact.so).
 bool fft_wave_is_exact();
 // filter_spectrum[0 .. fft_in] = forward real FFT of d_filter_time[0 .. 2*fft_in)

@@ -18,12 +18,7 @@
 // Channels are computed independently (what the reference yields per channel when its scratch
 // regions do not collide).
 #include "fft_kernels.h"
-#include "common.h"
 #include "fft_butterflies.h"
-
-#include <cmath>
-
-#include <cstdlib>
 
 namespace rsmp {
 
@@ -726,114 +721,36 @@ __global__ __launch_bounds__(kBigThreads) void fft_filter_big_kernel(FftPlanDev 
     for (uint32_t k = threadIdx.x; k <= fi; k += kBigThreads) spectrum[k] = buf[k];
 }
 
+typedef void (*OlaKernel)(FftPlanDev, const FftStreamDesc*, uint32_t);
+
+OlaKernel workgroup_kernel(const FftLaunch& c) {
+    switch (c.family) {
+        case FftFamily::kBig: return fft_ola_big_kernel;
+        case FftFamily::kCt: return c.pair == 0 ? fft_ola_kernel_ct<Plan1176, Plan1280> : fft_ola_kernel_ct<Plan1280, Plan1176>;
+        case FftFamily::kCt2: return c.pair == 0 ? fft_ola_kernel_ct2<Plan1176, Plan1280> : fft_ola_kernel_ct2<Plan1280, Plan1176>;
+        case FftFamily::kGeneric:
+            return c.block == 64 ? fft_ola_kernel<64, true> : c.block == 512 ? fft_ola_kernel<512, false>
+                   : c.block == 1024 ? fft_ola_kernel<1024, false> : fft_ola_kernel<kFftThreads, false>;
+        default: return nullptr;
+    }
+}
+
 }  // namespace
 
-// one buffer (the stages run in place) + the overlap row of the workgroup's channel
-size_t fft_big_lds_bytes(const FftPlanDev& plan) {
-    return static_cast<size_t>(plan.lds_complex) * sizeof(float2) + static_cast<size_t>(plan.fft_out) * sizeof(float);
-}
-
-size_t fft_ola_lds_bytes(const FftPlanDev& plan, uint32_t channels) {
-    return 2 * static_cast<size_t>(plan.lds_complex) * sizeof(float2) +
-           static_cast<size_t>(channels) * plan.fft_out * sizeof(float);
-}
-
-hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
-                          uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                          hipStream_t stream, uint32_t pcm_bits) {
-    if (n_streams == 0 || max_blocks == 0) return hipSuccess;
-    static const bool no_wave = rsmp::knob("RSMP_FFT_WAVE") != nullptr && atoi(rsmp::knob("RSMP_FFT_WAVE")) == 0;   // A/B
-    // (PCM input is read by the two-channel wave kernel only: FftStreamDesc::in_bits)
-    if (pcm_bits != 0 && (no_wave || max_channels != 2 || min_channels != 2)) return hipErrorNotSupported;
-    // two-channel f32 streams: a wave per stream, the frame as one complex sample (not in the exact build)
-    static const bool no_pair = rsmp::knob("RSMP_FFT_PAIR") != nullptr && atoi(rsmp::knob("RSMP_FFT_PAIR")) == 0;   // A/B
-    // (a launch of a block or two per stream is a streaming call: there the wave-per-channel kernel's two waves per stream
-    // finish sooner than one wave running both chains -- 32.6 against 36.3 us per one-block call, tools/fft_call_latency.py)
-    if (!no_wave && !no_pair && max_channels == 2 && min_channels == 2 && max_blocks >= 4 && !fft_wave_is_exact()) {
-        const hipError_t e = launch_fft_ola_pair(plan, d_descs, n_streams, max_blocks, stream, pcm_bits);
-        if (e != hipErrorNotSupported) return e;
-    }
-    if (!no_wave) {
-        const hipError_t e = launch_fft_ola_wave(plan, d_descs, n_streams, max_blocks, max_channels, min_channels, stream);
-        if (e != hipErrorNotSupported || pcm_bits != 0) return e;
-    }
-    // Blocks per workgroup: every run after a stream's first recomputes its predecessor block (1 / run
-    // extra work), and the launch ends with a partly filled round of workgroups unless their number
-    // is close to a multiple of what the chip holds at once.  Pick the run length (8..64) that
-    // maximises useful work per occupied slot.
-    auto pick_run = [&](const void* fn, uint32_t threads, size_t lds_bytes, uint32_t grid_z) {
-        uint32_t run = kFftRun;
-        int dev = 0, cus = 256, per_cu = 4;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 4;
-        const double slots = static_cast<double>(cus) * per_cu;
-        double best = -1.0;
-        for (uint32_t cand = 8; cand <= 64; ++cand) {
-            const double runs = static_cast<double>((max_blocks + cand - 1) / cand);
-            const double wgs = runs * n_streams * grid_z;
-            const double rounds = std::ceil(wgs / slots);
-            const double useful = static_cast<double>(max_blocks) / (max_blocks + runs - 1.0);   // halo blocks
-            const double score = wgs / (rounds * slots) * useful;
-            if (score > best + 1e-9) { best = score; run = cand; }
-        }
-        return run;
-    };
-    size_t lds = fft_ola_lds_bytes(plan, max_channels);
-    if (lds > 160 * 1024) {   // the two-buffer kernels do not fit: one buffer, in place, a workgroup per channel
-        const size_t big = fft_big_lds_bytes(plan);
-        if (big > 160 * 1024) return hipErrorInvalidValue;
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fft_ola_big_kernel),
+// The build fft_choose (fft_launch.cpp) names; its run follows the occupancy the runtime reports for it (fft_choose_run).
+hipError_t launch_fft_ola_workgroup(FftLaunch c, const FftRequest& rq, const FftPlanDev& plan, const FftStreamDesc* d_descs,
+                                    hipStream_t stream) {
+    const OlaKernel fn = workgroup_kernel(c);
+    if (fn == nullptr) return hipErrorNotSupported;
+    if (c.grant_lds) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
-        const uint32_t run = pick_run(reinterpret_cast<const void*>(fft_ola_big_kernel), kBigThreads, big, max_channels);
-        hipLaunchKernelGGL(fft_ola_big_kernel, dim3((max_blocks + run - 1) / run, n_streams, max_channels), dim3(kBigThreads), big,
-                           stream, plan, d_descs, run);
-        return hipGetLastError();
     }
-    const bool stereo = max_channels == 2 && min_channels == 2;
-    static const bool generic_only = rsmp::knob("RSMP_FFT_GENERIC") != nullptr;   // A/B: skip the specialised builds
-    const bool rc_full = plan.n_rc_f == plan.fft_in / 2 - 1 && plan.n_rc_i == plan.fft_out / 2 - 1;
-    typedef void (*Kernel)(FftPlanDev, const FftStreamDesc*, uint32_t);
-    Kernel fn = fft_ola_kernel<kFftThreads, false>;
-    uint32_t threads = kFftThreads, grid_z = 1;
-    if (!generic_only && rc_full && Plan1176::matches(plan.fft_in, plan.n_stages_f, plan.radix_f) &&
-        Plan1280::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
-        fn = stereo ? fft_ola_kernel_ct2<Plan1176, Plan1280> : fft_ola_kernel_ct<Plan1176, Plan1280>;
-    else if (!generic_only && rc_full && Plan1280::matches(plan.fft_in, plan.n_stages_f, plan.radix_f) &&
-             Plan1176::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
-        fn = stereo ? fft_ola_kernel_ct2<Plan1280, Plan1176> : fft_ola_kernel_ct<Plan1280, Plan1176>;
-    else {
-        // the generic pipeline: for blocks up to 512 frames (both sides) a one-wave workgroup per channel (see the
-        // kernel; 96 -> 48 kHz 1.56 -> 1.18 ms, 192 -> 48 kHz 1.48 -> 0.76 ms per 64 x 2^20 frames); above that the
-        // four-wave workgroups keep more waves on a CU for the same LDS and win (tools/fft_pairs_bench.py)
-        const size_t lds_wave = 2 * static_cast<size_t>(plan.lds_complex) * sizeof(float2) + static_cast<size_t>(plan.fft_out) * sizeof(float);
-        const bool per_channel = plan.lds_complex <= 513;
-        if (per_channel && lds_wave <= 160 * 1024) {
-            fn = fft_ola_kernel<64, true>;
-            threads = 64;
-            grid_z = max_channels;
-            lds = lds_wave;
-        } else if (lds > 80 * 1024) {
-            // the long plans: one workgroup per CU is all the LDS holds, so it is 16 waves wide, not 4
-            fn = fft_ola_kernel<1024, false>;
-            threads = 1024;
-        } else if (lds > 160 * 1024 / 3) {
-            fn = fft_ola_kernel<512, false>;   // two workgroups per CU
-            threads = 512;
-        }
-    }
-    if (fn == static_cast<Kernel>(fft_ola_kernel_ct2<Plan1176, Plan1280>) ||
-        fn == static_cast<Kernel>(fft_ola_kernel_ct2<Plan1280, Plan1176>))
-        lds = 4 * static_cast<size_t>(plan.lds_complex) * sizeof(float2) + 2 * static_cast<size_t>(plan.fft_out) * sizeof(float);
-    if (lds > 64 * 1024) {   // dynamic LDS above 64 KiB must be opted into
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    const uint32_t run = pick_run(reinterpret_cast<const void*>(fn), threads, lds, grid_z);
-    const dim3 grid((max_blocks + run - 1) / run, n_streams, grid_z);
-    hipLaunchKernelGGL(fn, grid, dim3(threads), lds, stream, plan, d_descs, run);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn), c.block, c.lds) != hipSuccess) per_cu = 0;
+    fft_choose_run(&c, rq, per_cu);
+    hipLaunchKernelGGL(fn, dim3(c.grid[0], c.grid[1], c.grid[2]), dim3(c.block), c.lds, stream, plan, d_descs, c.args[0]);
     return hipGetLastError();
 }
 

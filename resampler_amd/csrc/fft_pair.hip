@@ -31,40 +31,24 @@
 // Around that: every channel of every block is brought to its own level before the two share butterflies (PairScale: a
 // quiet or silent channel beside a loud one, a NaN in one channel); a CU holds eight waves -- two per SIMD, served oldest
 // first -- and a stream's blocks are cut into a LONG run for an old wave and a SHORT one for a young wave (the kernel body's
-// run arithmetic, launch_fft_ola_pair); the output stores and the samples' second read are non-temporal (the block's samples
+// run arithmetic; fft_launch.cpp, choose_pair); the output stores and the samples' second read are non-temporal (the block's samples
 // stay in L2 between the chains); WAV PCM is converted where the frames are loaded (BITS).  DESIGN.md 4.4.
 // Arithmetic: the reference's butterflies on other operands -- equal to the CPU path within rounding (tests/test_fft_gpu.py
 // holds it to the gate of 1e-6 RMS; measured ~1.5e-7 like the wave-per-channel kernel), not bit for bit; the exact build
 // (libresampler_amd_fftexact.so) never takes this kernel.
-#include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 #pragma clang fp contract(fast)
 
 #include "fft_butterflies_pk.h"
 #include "fft_kernels.h"
-#include "common.h"
 
 #ifndef RSMP_EXP
 #define RSMP_EXP 0
 #endif
 #define RSMP_FEAT (RSMP_EXP & 63)   // A/B builds (make exp EXPFILE=fft_pair.hip)
 
-// Diagnostic builds (tools/fft_trace.py, RSMP_EXP >> 6): 1 = every wave's start / end on the constant 100 MHz clock and where it
-// ran; 2 = also the shader-clock cycles a wave spends in each phase of its blocks.
-#if (RSMP_EXP >> 6) != 0
-#define RSMP_FFT_TRACE 1
-__device__ unsigned long long rsmp_fft_trace_buf[4096 * 16];
-extern "C" int rsmp_debug_fft_trace(unsigned long long* out, size_t words) {
-    return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(rsmp_fft_trace_buf), words * 8));
-}
-#endif
-#if (RSMP_EXP >> 6) == 2
-#define RSMP_TR(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); tr_ph[i] += t_ - tr_last; tr_last = t_; } while (0)
-#else
-#define RSMP_TR(i) do { } while (0)
-#endif
+#include "fft_trace.h"
 
 namespace rsmp {
 
@@ -244,7 +228,7 @@ __device__ __forceinline__ void wave_last_regs(const cf* buf, const cf* __restri
 template <int FI, int FO>
 struct PairBins {
     static constexpr bool kUp = FI < FO;
-    static constexpr int kNL = kUp ? FI + 1 : FO;
+    static constexpr int kNL = filter_bins(FI, FO);
     static constexpr int kPosMax = kNL - 1;
     static constexpr int kNegMin = 2 * FI - (kNL - 1);
     static constexpr int kShift = FO - FI;
@@ -260,17 +244,9 @@ struct PairBins {
 // BITS: 0 = f32 frames; 16 / 24 / 32 = little-endian WAV PCM frames of that width, converted where they are loaded
 // exactly as resample/src/main.rs:128-137 converts a sample (`sample as f32 / (1 << (bits - 1)) as f32`, the 32-bit divisor
 // an i32 literal = -2^31): bit for bit what rsmp_pcm_to_stereo_f32_device + the f32 launch give.
-// Waves per CU: eight (two per SIMD, an old and a young one) where the LDS holds the tables and eight buffers, else four.
+// Waves per CU = per workgroup: PairBudget (fft_wave_plan.h).
 template <class FWD, class INV>
-constexpr int pair_waves() {
-    constexpr size_t buf = FWD::kBuf > INV::kBuf ? FWD::kBuf : INV::kBuf;
-    constexpr size_t tables = static_cast<size_t>(FWD::kTw + INV::kTw + PairBins<FWD::N, INV::N>::kNL + FWD::N + INV::N);
-    // (plans of up to 512 points need ~105 registers: sixteen waves, four per SIMD, hide more of their many short passes)
-    if (FWD::N <= 768 && INV::N <= 512 && (tables + 16 * buf) * sizeof(cf) <= 160 * 1024) return 16;
-    // (twelve waves -- 168 registers -- for the plans of up to 1024 points: 26-55 spilled registers, 512 -> 1024 frames 0.72 ->
-    // 0.77 ms, 640 -> 882 0.76 -> 0.87: measured, not kept)
-    return (tables + 8 * buf) * sizeof(cf) <= 160 * 1024 ? 8 : (tables + 4 * buf) * sizeof(cf) <= 160 * 1024 ? 4 : 0;
-}
+constexpr int pair_waves() { return pair_budget<FWD, INV>(kWholeRows).waves; }
 template <class FWD, class INV, int BITS>
 __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 4) * 64, 1) void fft_ola_pair_kernel(FftPlanDev plan, const FftStreamDesc* __restrict__ descs,
                                                               uint32_t run0, uint32_t run1, uint32_t run2, uint32_t run3,
@@ -291,7 +267,7 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
     // tables, once per workgroup: stage twiddles (rows re-spaced as the stages read them), the filter bins in use, and
     // the two chirps w (FI values) and u (FO values)
     constexpr int kFilterEven = (NL + 1) / 2;   // even bins 0, 2, ..
-    constexpr int kTabF = 0, kTabI = kTabF + FWD::kTw, kTabFilter = kTabI + INV::kTw, kTabW = kTabFilter + NL,
+    constexpr int kTabF = 0, kTabI = kTabF + FWD::tw(kWholeRows), kTabFilter = kTabI + INV::tw(kWholeRows), kTabW = kTabFilter + NL,
                   kTabU = kTabW + FI, kTabEnd = kTabU + FO;
     cf* tab = lds2;
     {
@@ -309,7 +285,7 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
             static_for<1, PL::kStages>([&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
                 constexpr int len = PL::kR[s] - 1;
-                rows(dst + PL::tab(s), src + PL::src(s), PL::stride(s), len, PL::kFused && s == 1 ? len : fetch_count(PL::kR[s]), PL::pitch(s));
+                rows(dst + PL::tab(s, kWholeRows), src + PL::src(s), PL::stride(s), len, PL::kFused && s == 1 ? len : fetch_count(PL::kR[s]), PL::pitch(s, kWholeRows));
             });
         };
         stage_tables(tab + kTabF, reinterpret_cast<const cf*>(plan.tw_f), FWD{});
@@ -427,7 +403,7 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
             // ---- forward FI-point transform of z (even bins) or z w (odd bins)
             {
                 auto first_pass = [&](auto&& smp, auto prep) {
-                    if constexpr (FWD::kFused) wave_fused_first<FI, FWD::kR[0], FWD::kR[1], FWD::kPadJ>(buf, tw_f + FWD::tab(1), lane, smp, prep);
+                    if constexpr (FWD::kFused) wave_fused_first<FI, FWD::kR[0], FWD::kR[1], FWD::kPadJ>(buf, tw_f + FWD::tab(1, kWholeRows), lane, smp, prep);
                     else wave_first<FI, FWD::kR[0], FWD::kPadJ>(buf, lane, smp, prep);
                 };
                 if constexpr (par == 0) {
@@ -442,13 +418,13 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
             RSMP_TR(6 * par + 0);
             static_for<(FWD::kFused ? 2 : 1), SF - 1>([&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
-                wave_stage<FI, FWD::kR[s], FWD::stride(s), FI / FWD::kR[s] + FWD::in_pad(s), FWD::out_pad(s), FWD::in_period(s)>(buf, tw_f + FWD::tab(s), lane);
+                wave_stage<FI, FWD::kR[s], FWD::stride(s), FI / FWD::kR[s] + FWD::in_pad(s), FWD::out_pad(s), FWD::in_period(s)>(buf, tw_f + FWD::tab(s, kWholeRows), lane);
             });
             RSMP_TR(6 * par + 1);
             // ---- last forward stage in registers; times the filter; conj(V) of the chain into the buffer, in index order
             {
                 cf z[ITF][RLF], hv[ITF][RLF];
-                wave_last_regs<FI, RLF, MF + FWD::in_pad(SF - 1), FWD::in_period(SF - 1)>(buf, tw_f + FWD::tab(SF - 1), lane, z);
+                wave_last_regs<FI, RLF, MF + FWD::in_pad(SF - 1), FWD::in_period(SF - 1)>(buf, tw_f + FWD::tab(SF - 1, kWholeRows), lane, z);
 #pragma unroll
                 for (int it = 0; it < ITF; ++it) {
                     const int i = lane + 64 * it;
@@ -499,17 +475,17 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
                     if (ZLO <= ZHI && j >= ZLO && j <= ZHI) v = cf_make(0.f, 0.f);
                     return v;
                 };
-                if constexpr (INV::kFused) wave_fused_first<FO, INV::kR[0], INV::kR[1], INV::kPadJ>(buf, tw_i + INV::tab(1), lane, from_lds);
+                if constexpr (INV::kFused) wave_fused_first<FO, INV::kR[0], INV::kR[1], INV::kPadJ>(buf, tw_i + INV::tab(1, kWholeRows), lane, from_lds);
                 else wave_first<FO, INV::kR[0], INV::kPadJ>(buf, lane, from_lds);
             }
             RSMP_TR(6 * par + 3);
             static_for<(INV::kFused ? 2 : 1), SI - 1>([&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
-                wave_stage<FO, INV::kR[s], INV::stride(s), FO / INV::kR[s] + INV::in_pad(s), INV::out_pad(s), INV::in_period(s)>(buf, tw_i + INV::tab(s), lane);
+                wave_stage<FO, INV::kR[s], INV::stride(s), FO / INV::kR[s] + INV::in_pad(s), INV::out_pad(s), INV::in_period(s)>(buf, tw_i + INV::tab(s, kWholeRows), lane);
             });
             RSMP_TR(6 * par + 4);
             if constexpr (par == 0) {
-                wave_last_regs<FO, RLI, MI + INV::in_pad(SI - 1), INV::in_period(SI - 1)>(buf, tw_i + INV::tab(SI - 1), lane, A);
+                wave_last_regs<FO, RLI, MI + INV::in_pad(SI - 1), INV::in_period(SI - 1)>(buf, tw_i + INV::tab(SI - 1, kWholeRows), lane, A);
             } else {
                 cf B[ITI][RLI], uv[ITI][RLI];
 #pragma unroll
@@ -520,7 +496,7 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
                         for (int q = 0; q < RLI; ++q) uv[it][q] = lds_ld(chirp_u + i + q * MI);
                     }
                 }
-                wave_last_regs<FO, RLI, MI + INV::in_pad(SI - 1), INV::in_period(SI - 1)>(buf, tw_i + INV::tab(SI - 1), lane, B);
+                wave_last_regs<FO, RLI, MI + INV::in_pad(SI - 1), INV::in_period(SI - 1)>(buf, tw_i + INV::tab(SI - 1, kWholeRows), lane, B);
                 // F[n] = A + u B -> frame n = conj(F[n]) + conj(carry[n]); F[n + FO] = A - u B is the next carry
 #pragma unroll
                 for (int it = 0; it < ITI; ++it) {
@@ -578,121 +554,36 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
     }
 }
 
-typedef WavePlan<1176, 3, 7, 7, 8> W1176;   // 44.1 kHz side of the 44.1 <-> 48 kHz family
-typedef WavePlan<1280, 4, 5, 8, 8> W1280;   // 48 kHz side
-// (the other plans of up to 2048 points, as in fft_wave.hip)
-typedef WavePlan<512, 8, 8, 8> W512;
-typedef WavePlan<1024, 2, 8, 8, 8> W1024;
-typedef WavePlan<256, 4, 8, 8> W256;
-typedef WavePlan<128, 2, 8, 8> W128;
-typedef WavePlan<64, 8, 8> W64;
-typedef WavePlan<768, 3, 4, 8, 8> W768;
-typedef WavePlan<1536, 3, 8, 8, 8> W1536;
-typedef WavePlan<588, 3, 4, 7, 7> W588;
-typedef WavePlan<882, 2, 3, 3, 7, 7> W882;
-typedef WavePlan<1764, 3, 3, 4, 7, 7> W1764;
-typedef WavePlan<640, 2, 5, 8, 8> W640;
-
 typedef void (*PairKernel)(FftPlanDev, const FftStreamDesc*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 
-struct PairChoice {
-    PairKernel fn = nullptr;
-    size_t lds = 0;
-    uint32_t waves = 0;   // per workgroup = per CU
-};
+// The builds of a pair by BITS / 8 (a pair the LDS does not serve has none: the launch rules never choose it), and the
+// table over a list of pairs.
+struct PairBuilds { PairKernel bits[5]; };
 template <class FWD, class INV>
-bool pair_choice(const FftPlanDev& plan, uint32_t pcm_bits, PairChoice* out) {
-    if (!FWD::matches(plan.fft_in, plan.n_stages_f, plan.radix_f) || !INV::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
-        return false;
-    constexpr int waves = pair_waves<FWD, INV>();
-    if constexpr (waves == 0) {
-        (void)pcm_bits; (void)out;
-        return false;
-    } else {
-        constexpr size_t buf = FWD::kBuf > INV::kBuf ? FWD::kBuf : INV::kBuf;
-        constexpr size_t tables = static_cast<size_t>(FWD::kTw + INV::kTw + PairBins<FWD::N, INV::N>::kNL + FWD::N + INV::N);
-        out->fn = pcm_bits == 16 ? fft_ola_pair_kernel<FWD, INV, 16> : pcm_bits == 24 ? fft_ola_pair_kernel<FWD, INV, 24>
-                  : pcm_bits == 32 ? fft_ola_pair_kernel<FWD, INV, 32> : fft_ola_pair_kernel<FWD, INV, 0>;
-        out->lds = (tables + waves * buf) * sizeof(cf);
-        out->waves = waves;
-        return true;
-    }
+constexpr PairBuilds pair_builds() {
+    if constexpr (pair_waves<FWD, INV>() == 0) return PairBuilds{{nullptr, nullptr, nullptr, nullptr, nullptr}};
+    else return PairBuilds{{fft_ola_pair_kernel<FWD, INV, 0>, nullptr, fft_ola_pair_kernel<FWD, INV, 16>, fft_ola_pair_kernel<FWD, INV, 24>, fft_ola_pair_kernel<FWD, INV, 32>}};
 }
-
-template <class FWD, class... INVS>
-bool pair_choices(const FftPlanDev& plan, uint32_t pcm_bits, PairChoice* out) {
-    return (pair_choice<FWD, INVS>(plan, pcm_bits, out) || ...);
+template <class... Ps>
+PairKernel pair_kernel(PairList<Ps...>, int pair, int bits) {
+    static constexpr PairBuilds table[] = {pair_builds<typename Ps::Fwd, typename Ps::Inv>()...};
+    return pair < static_cast<int>(sizeof...(Ps)) ? table[pair].bits[bits / 8] : nullptr;
 }
 
 }  // namespace
 
-// One wave per two-channel stream and run of blocks.  hipErrorNotSupported when the plan is not one of the pairs above
-// (the caller then uses the wave-per-channel kernels).
-hipError_t launch_fft_ola_pair(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams, uint32_t max_blocks,
-                               hipStream_t stream, uint32_t pcm_bits) {
-    if (pcm_bits != 0 && pcm_bits != 16 && pcm_bits != 24 && pcm_bits != 32) return hipErrorNotSupported;
-    if (plan.chirp_f == nullptr || plan.chirp_i == nullptr) return hipErrorNotSupported;
-    if (plan.new_length != (plan.fft_in < plan.fft_out ? plan.fft_in + 1 : plan.fft_out)) return hipErrorNotSupported;
-    PairChoice pc;
-    const bool found = pair_choice<W1176, W1280>(plan, pcm_bits, &pc) || pair_choice<W1280, W1176>(plan, pcm_bits, &pc)
+// The build fft_choose (fft_launch.cpp) names, launched as it says.
+hipError_t launch_fft_ola_pair(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream) {
 #if RSMP_EXP != 0   // (timing experiments instantiate the 44.1 <-> 48 kHz pair alone)
-                       ;
+    const PairKernel fn = pair_kernel(HeadPairs{}, c.pair, c.bits);
 #else
-                       // (by tools/fft_pairs_bench.py, both kernels in one lease -- profiles/r05/fft_pairs_pair_vs_wave.txt: the
-                       // down-sampling pairs gain 8 - 21 %, 512 -> 1024 frames 4 %; a 1764-point inverse, 512 -> 1536 / 2048,
-                       // 768 -> 256 / 512, 882 -> 1280 and 1764 -> 1280 frames spill or run four waves and stay with fft_wave.hip)
-                       || pair_choices<W512, W64, W128, W256, W768, W1024>(plan, pcm_bits, &pc) || pair_choices<W768, W64, W128, W256, W512>(plan, pcm_bits, &pc) ||
-                       pair_choices<W1536, W64, W128>(plan, pcm_bits, &pc) || pair_choices<W588, W1280>(plan, pcm_bits, &pc) ||
-                       pair_choices<W882, W640>(plan, pcm_bits, &pc) || pair_choices<W1764, W640>(plan, pcm_bits, &pc) ||
-                       pair_choices<W640, W882>(plan, pcm_bits, &pc) || pair_choices<W1280, W588, W882>(plan, pcm_bits, &pc);
+    const PairKernel fn = pair_kernel(PairPairs{}, c.pair, c.bits);
 #endif
-    if (!found) return hipErrorNotSupported;
-    // Pairs of runs per stream: every run after a stream's first recomputes its predecessor block (1 / run extra work), and
-    // the launch ends with a partly filled round unless the number of waves is close to a multiple of what the chip holds
-    // (8 per CU).  Of a pair's blocks the old wave takes kLongShare (its share of a SIMD while both waves run).
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const uint32_t classes = pc.waves / 4;   // waves per SIMD: ages
-    const double slots = static_cast<double>(cus) * pc.waves;
-    static const double share_knob = [] { const char* e = rsmp::knob("RSMP_FFT_PAIR_SHARE"); return e ? atof(e) : 0.0; }();   // A/B
-    // the share of a SIMD each age gets while all of them run (two ages: by a sweep on the 44.1 -> 48 kHz launch; four: the
-    // same falling series, RSMP_FFT_PAIR_SHARE = its ratio)
-    double share[4] = {1.0, 0.0, 0.0, 0.0};
-    if (classes == 2) {
-        share[0] = share_knob > 0.0 && share_knob < 1.0 ? share_knob : 0.6;
-        share[1] = 1.0 - share[0];
-    } else if (classes >= 3) {
-        const double r = share_knob > 0.0 && share_knob <= 1.0 ? share_knob : 0.8;
-        double sum = 0.0;
-        for (uint32_t c = 0; c < classes; ++c) sum += std::pow(r, static_cast<double>(c));
-        for (uint32_t c = 0; c < classes; ++c) share[c] = std::pow(r, static_cast<double>(c)) / sum;
-    }
-    uint32_t both = 32;
-    double best = -1.0;
-    for (uint32_t cand = 6 * classes; cand <= 64 * classes; ++cand) {   // blocks of a group of runs (one per age)
-        const double pairs = static_cast<double>((max_blocks + cand - 1) / cand);
-        const double waves = classes * pairs * n_streams;
-        const double rounds = std::ceil(waves / slots);
-        const double useful = static_cast<double>(max_blocks) / (max_blocks + classes * pairs - 1.0);   // halo blocks
-        const double score = waves / (rounds * slots) * useful;
-        if (score > best + 1e-9) { best = score; both = cand; }
-    }
-    const uint32_t pairs_per_stream = (max_blocks + both - 1) / both;
-    // (the halo block is part of a wave's work: the shares are of both + classes)
-    uint32_t runs[4] = {0, 0, 0, 0}, given = 0;
-    for (uint32_t c = 0; c + 1 < classes; ++c) {
-        const long v = std::lround(share[c] * (both + static_cast<double>(classes)) - 1.0);
-        runs[c] = static_cast<uint32_t>(v < 1 ? 1 : v);
-        if (given + runs[c] > both) runs[c] = both - given;
-        given += runs[c];
-    }
-    runs[classes - 1] = both - given;
-    const uint32_t total_waves = pairs_per_stream * n_streams * classes;
-    const dim3 grid((total_waves + pc.waves - 1) / pc.waves);
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pc.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (fn == nullptr) return hipErrorNotSupported;
+    if (c.whole_rows != kWholeRows) return hipErrorInvalidValue;   // (the LDS bytes are for another build of this file)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pc.fn, grid, dim3(pc.waves * 64), pc.lds, stream, plan, d_descs, runs[0], runs[1], runs[2], runs[3], pairs_per_stream, total_waves);
+    hipLaunchKernelGGL(fn, dim3(c.grid[0]), dim3(c.block), c.lds, stream, plan, d_descs, c.args[0], c.args[1], c.args[2], c.args[3], c.args[4], c.args[5]);
     return hipGetLastError();
 }
 

@@ -5,7 +5,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "errors.h"
 #include "filter_design.h"
 
 #pragma STDC FP_CONTRACT OFF

@@ -29,8 +29,6 @@
 // runs ended at 66 / 80 / 97 % of the launch -- so the waves of a SIMD publish their block counts in LDS and the one behind
 // raises its priority; the two waves of a stream touch the next block's lines into L2 a block ahead.  Two-channel streams
 // of the plan pairs it is built for go to fft_pair.hip (a wave per stream, the frame as one complex sample) instead.
-#include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 // a*b + c may fuse in this file: one rounding fewer per fused pair.  The results then differ from the
@@ -43,7 +41,6 @@
 
 #include "fft_butterflies_pk.h"
 #include "fft_kernels.h"
-#include "common.h"
 
 #ifndef RSMP_EXP
 #define RSMP_EXP 0   // A/B builds (make exp EXPFILE=fft_wave.hip): timing experiments, never shipped
@@ -51,25 +48,11 @@
 // RSMP_EXP = features + 64 * trace.  Features (bits): 1 = NO priority feedback between the waves of a SIMD; 4 = NO touch of
 // the next block's samples into L2 (the two things tools/fft_trace.py found, switched off again for an A/B);
 // 8 / 16 = every LDS store / read issued twice, 32 = two more packed instructions per complex multiply (what a store, a read,
-// a vector instruction costs the launch: profiles/r05/fft_slopes.txt).  Trace (tools/fft_trace.py): 1 = every wave's start /
-// end on the constant 100 MHz clock and where it ran; 2 = also the shader-clock cycles a wave spends in each phase of its
-// blocks (the reads of the clock drain the LDS queue at every phase boundary: the phases' shares are what it is for, not the
-// total).
+// a vector instruction costs the launch: profiles/r05/fft_slopes.txt).  Trace: fft_trace.h.
 #define RSMP_FEAT (RSMP_EXP & 63)
 #define RSMP_PRIO (!(RSMP_FEAT & 1))
 #define RSMP_TOUCH (!(RSMP_FEAT & 4))
-#if (RSMP_EXP >> 6) != 0
-#define RSMP_FFT_TRACE 1
-__device__ unsigned long long rsmp_fft_trace_buf[4096 * 16];
-extern "C" int rsmp_debug_fft_trace(unsigned long long* out, size_t words) {
-    return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(rsmp_fft_trace_buf), words * 8));
-}
-#endif
-#if (RSMP_EXP >> 6) == 2
-#define RSMP_TR(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); tr_ph[i] += t_ - tr_last; tr_last = t_; } while (0)
-#else
-#define RSMP_TR(i) do { } while (0)
-#endif
+#include "fft_trace.h"
 
 namespace rsmp {
 
@@ -203,15 +186,9 @@ __device__ __forceinline__ void wave_filter_preprocess(cf* y, const cf* __restri
     lds_order();
 }
 
-// OCC waves per SIMD: 2 = two workgroups of 4 waves per CU (80 KB of LDS each: the tables + 4 buffers),
-// 3 = one workgroup of 12 waves per CU (one copy of the tables + 12 buffers = 158 KB; <= 168 registers),
-// 1 = one workgroup of as many waves (<= 8) as the CU's LDS holds buffers for (the long plans; the launch
-// decides).  (16 waves per CU for the short plans measured within 2 % of 12: the LDS is the bound, not latency.)
+// OCC waves per SIMD (fft_wave_plan.h, WaveBudget): 3 = one workgroup of 12 waves per CU, 2 = two of 4, 1 = one of as many
+// (<= 8) as the launch decides.
 constexpr int wave_group_threads(int occ) { return occ == 3 ? 768 : occ == 2 ? 256 : 512; }
-// Both transforms above 2048 points (88.2 <-> 96 kHz): four or five trips per stage in registers next to the
-// carry do not fit 256 registers -- these pairs run one wave per SIMD with the full register file instead of two
-// that spill (88.2 -> 96 kHz: 0.94 -> 0.76 ms).
-template <class FWD, class INV> constexpr bool kOneWavePerSimd = (FWD::N > 2048 && INV::N > 2048) || FWD::N > 2560 || INV::N > 2560;
 // CHM: 0 = any number of channels (a wave per channel, 4-byte accesses at the frame's stride), 1 = two channels (16-byte
 // accesses), 2 = an even number of channels taken as channel pairs (8-byte accesses at the frame's stride)
 template <class FWD, class INV, int CHM, int OCC>
@@ -244,7 +221,7 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
     // to LDS once per workgroup: the per-butterfly twiddle fetches were the kernel's main wait (48 % of the
     // wave time at s_waitcnt, vector-memory instructions in flight 4x the LDS ones).  The only barrier of
     // the kernel follows; after it the waves never meet again.
-    constexpr int kTabF = 0, kTabI = kTabF + FWD::kTw, kTabRcF = kTabI + INV::kTw, kTabRcI = kTabRcF + FWD::kRc,
+    constexpr int kTabF = 0, kTabI = kTabF + FWD::tw(kWholeRows), kTabRcF = kTabI + INV::tw(kWholeRows), kTabRcI = kTabRcF + FWD::kRc,
                   kTabFilter = kTabRcI + INV::kRc, kTabEnd = kTabFilter + kFilterLen;
     cf* tab = lds2;
     {
@@ -264,7 +241,7 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
             static_for<1, PL::kStages>([&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
                 constexpr int len = PL::kR[s] - 1;
-                rows(dst + PL::tab(s), src + PL::src(s), PL::stride(s), len, PL::kFused && s == 1 ? len : fetch_count(PL::kR[s]), PL::pitch(s));
+                rows(dst + PL::tab(s, kWholeRows), src + PL::src(s), PL::stride(s), len, PL::kFused && s == 1 ? len : fetch_count(PL::kR[s]), PL::pitch(s, kWholeRows));
             });
         };
         stage_tables(tab + kTabF, reinterpret_cast<const cf*>(plan.tw_f), FWD{});
@@ -420,7 +397,7 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
                 return v;
             };
             auto first_pass = [&](auto&& smp) {
-                if constexpr (FWD::kFused) wave_fused_first<FI, FWD::kR[0], FWD::kR[1], FWD::kPadJ, FI / 2>(buf, tw_f + FWD::tab(1), lane, smp);
+                if constexpr (FWD::kFused) wave_fused_first<FI, FWD::kR[0], FWD::kR[1], FWD::kPadJ, FI / 2>(buf, tw_f + FWD::tab(1, kWholeRows), lane, smp);
                 else wave_first<FI, FWD::kR[0], FWD::kPadJ, FI / 2>(buf, lane, smp);
             };
             if constexpr (stereo) {
@@ -495,7 +472,7 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
         RSMP_TR(1);
         static_for<(FWD::kFused ? 2 : 1), SF>([&](auto s_c) {
             constexpr int s = decltype(s_c)::value;
-            wave_stage<FI, FWD::kR[s], FWD::stride(s), FI / FWD::kR[s] + FWD::in_pad(s), FWD::out_pad(s), FWD::in_period(s)>(buf, tw_f + FWD::tab(s), lane);
+            wave_stage<FI, FWD::kR[s], FWD::stride(s), FI / FWD::kR[s] + FWD::in_pad(s), FWD::out_pad(s), FWD::in_period(s)>(buf, tw_f + FWD::tab(s, kWholeRows), lane);
             RSMP_TR(s);   // (2, 3)
         });
         wave_postprocess<FI>(buf, rc_f, lane);
@@ -506,13 +483,13 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
         // ---- inverse transform, in place; its last stage below
         {
             auto from_lds = [&](int j) -> cf { return lds_ld(buf + j); };
-            if constexpr (INV::kFused) wave_fused_first<FO, INV::kR[0], INV::kR[1], INV::kPadJ>(buf, tw_i + INV::tab(1), lane, from_lds);
+            if constexpr (INV::kFused) wave_fused_first<FO, INV::kR[0], INV::kR[1], INV::kPadJ>(buf, tw_i + INV::tab(1, kWholeRows), lane, from_lds);
             else wave_first<FO, INV::kR[0], INV::kPadJ>(buf, lane, from_lds);
         }
         RSMP_TR(6);
         static_for<(INV::kFused ? 2 : 1), (kOddLast ? SI : SI - 1)>([&](auto s_c) {
             constexpr int s = decltype(s_c)::value;
-            wave_stage<FO, INV::kR[s], INV::stride(s), FO / INV::kR[s] + INV::in_pad(s), INV::out_pad(s), INV::in_period(s)>(buf, tw_i + INV::tab(s), lane);
+            wave_stage<FO, INV::kR[s], INV::stride(s), FO / INV::kR[s] + INV::in_pad(s), INV::out_pad(s), INV::in_period(s)>(buf, tw_i + INV::tab(s, kWholeRows), lane);
         });
         RSMP_TR(7);
         // ---- last inverse stage: outputs stay in registers.  Butterfly i (k = i) yields Z[i + q*ML]; the
@@ -545,7 +522,7 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
             if ((it + 1) * 64 <= ML || i < ML) {
 #pragma unroll
                 for (int q = 0; q < RL; ++q) tl[it & 1][q] = lds_ld(buf + i + (kLastIpp ? i / (kLastIpp ? kLastIpp : 1) : 0) + q * (ML + INV::in_pad(SI - 1)));
-                twiddle_fetch<RL>(tw_i + INV::tab(SI - 1) + i * INV::row(RL), rawl[it & 1]);
+                twiddle_fetch<RL>(tw_i + INV::tab(SI - 1, kWholeRows) + i * INV::row(RL, kWholeRows), rawl[it & 1]);
             }
         };
         fetch(0);
@@ -653,81 +630,21 @@ __global__ __launch_bounds__((OCC == 1 && kOneWavePerSimd<FWD, INV> ? 256 : wave
     }
 }
 
-typedef WavePlan<1176, 3, 7, 7, 8> W1176;   // 44.1 kHz side of the 44.1 <-> 48 kHz family
-typedef WavePlan<1280, 4, 5, 8, 8> W1280;   // 48 kHz side
-typedef WavePlan<512, 8, 8, 8> W512;        // the input block of the power-of-two families (x2, /2, x4, /4, x3, x1.5 ...)
-typedef WavePlan<1024, 2, 8, 8, 8> W1024;
-typedef WavePlan<256, 4, 8, 8> W256;
-typedef WavePlan<128, 2, 8, 8> W128;
-typedef WavePlan<64, 8, 8> W64;
-typedef WavePlan<768, 3, 4, 8, 8> W768;
-typedef WavePlan<1536, 3, 8, 8, 8> W1536;
-typedef WavePlan<2048, 4, 8, 8, 8> W2048;
-typedef WavePlan<3072, 2, 3, 8, 8, 8> W3072;   // (x6: six trips per stage -- one wave per SIMD with the whole register file)
-typedef WavePlan<4096, 8, 8, 8, 8> W4096;      // (x8: three waves per CU are all the LDS holds)
-typedef WavePlan<3528, 3, 3, 7, 7, 8> W3528;   // 88.2 kHz against the 16 / 32 kHz families
-typedef WavePlan<4704, 3, 4, 7, 7, 8> W4704;   // 176.4 kHz (two waves per CU)
-typedef WavePlan<5120, 2, 5, 8, 8, 8> W5120;   // 192 kHz
-typedef WavePlan<588, 3, 4, 7, 7> W588;     // 22.05 kHz against the 48 kHz family (input side: the inverse's last radix must be even)
-typedef WavePlan<882, 2, 3, 3, 7, 7> W882;
-typedef WavePlan<1764, 3, 3, 4, 7, 7> W1764;
-typedef WavePlan<2352, 2, 3, 7, 7, 8> W2352; // 88.2 kHz
-typedef WavePlan<2560, 5, 8, 8, 8> W2560;    // 96 kHz
-typedef WavePlan<640, 2, 5, 8, 8> W640;        // 16 kHz against the 44.1 kHz family
-
 typedef void (*WaveKernel)(FftPlanDev, const FftStreamDesc*, uint32_t, uint32_t, uint32_t, uint32_t);
-struct WaveChoice {
-    WaveKernel fn = nullptr;
-    size_t lds = 0;          // bytes of a workgroup
-    uint32_t waves = 0;      // waves per workgroup
-    uint32_t resident = 0;   // waves a CU holds at once
-};
 
-// The instantiation for (FWD, INV) if the plan is that pair.  Waves per CU, by what the CU's LDS holds (one copy
-// of the tables per workgroup + a buffer per wave) and what the registers allow: two-channel streams run 12
-// (<= 168 registers) or 2 x 4 waves; streams of 4, 6, 8 .. channels run as channel pairs on the same code with 8-byte
-// accesses (2 x 4 waves); the any-channel-count build (odd counts) needs ~250 registers (strided
-// sample addressing; it spilled 290 bytes per lane under the 168 cap and ran 25-30 % slower,
-// tools/fft_channels_bench.py) and runs 2 x 4.  Plans too long for that run one workgroup of up to 8 waves.
+// The builds of a pair by CHM, at the OCC its budget gives them (a pair the LDS does not serve has none: the launch rules
+// never choose it), and the table over a list of pairs.
+struct WaveBuilds { WaveKernel chm[3]; };
 template <class FWD, class INV>
-bool wave_choice(const FftPlanDev& plan, uint32_t channels, WaveChoice* out) {
-    if (!FWD::matches(plan.fft_in, plan.n_stages_f, plan.radix_f) || !INV::matches(plan.fft_out, plan.n_stages_i, plan.radix_i))
-        return false;
-    constexpr size_t tables = static_cast<size_t>(FWD::kTw + INV::kTw + FWD::kRc + INV::kRc + (FWD::N < INV::N ? FWD::N + 1 : INV::N));   // (+ the filter bins in use)
-    constexpr size_t buf = FWD::kBuf > INV::kBuf ? FWD::kBuf : INV::kBuf;
-    constexpr size_t kCu = 160 * 1024 / sizeof(cf);
-    constexpr size_t kFlags = 32;   // cf-sized words behind the buffers: exchange flags (two 32-bit words per wave, up to 16 waves), then the waves' SIMD ids and block counts
-    constexpr bool fit12 = tables + 12 * buf + kFlags <= kCu, fit4 = 2 * (tables + 4 * buf + kFlags) <= kCu;
-    constexpr uint32_t wide_fit = (kCu - tables - kFlags) / buf < 8 ? static_cast<uint32_t>((kCu - tables - kFlags) / buf) : 8u;
-    constexpr uint32_t wide = kOneWavePerSimd<FWD, INV> && wide_fit > 4 ? 4u : wide_fit;
-    // (fewer than two waves per CU -- the longest plans in the exact build, whose twiddle rows are whole -- belong to
-    // the workgroup kernels)
-    if constexpr (!fit4 && wide < 2) {
-        (void)channels; (void)out;
-        return false;
-    } else {
-    static const bool no_c2 = rsmp::knob("RSMP_FFT_WAVE_NOC2") != nullptr;   // A/B: the any-channel-count build for two channels
-    // (an even number of channels: channel pairs on the two-channel build)
-    const bool paired = channels % 2 == 0 && !no_c2;
-    // (the pairs build addresses its frames at a run-time stride: under the 168-register cap of twelve waves per CU it
-    // spills 25 registers and runs 13 % slower than 2 x 4 waves with all of them -- 8 channels 0.84 against 0.73 ms:
-    // only the two-channel build runs twelve waves, occupancy 3; the others 2 x 4 waves (2) or one workgroup (1))
-    constexpr int occ_any = fit4 ? 2 : 1, occ_c2 = fit12 ? 3 : occ_any;
-    const bool c2 = paired && channels == 2;
-    const int occ = c2 ? occ_c2 : occ_any;
-    if (c2) out->fn = fft_ola_wave_kernel<FWD, INV, 1, occ_c2>;
-    else if (paired) out->fn = fft_ola_wave_kernel<FWD, INV, 2, occ_any>;
-    else out->fn = fft_ola_wave_kernel<FWD, INV, 0, occ_any>;
-    static const uint32_t wide_knob = [] { const char* e = rsmp::knob("RSMP_FFT_WAVE_WIDE"); return e ? static_cast<uint32_t>(atoi(e)) : 0u; }();
-    out->waves = occ == 3 ? 12u : occ == 2 ? 4u : (wide_knob >= 1 && wide_knob <= wide ? wide_knob : wide);
-    out->resident = occ == 2 ? 8u : out->waves;
-    out->lds = (tables + out->waves * buf + kFlags) * sizeof(cf);
-    return true;
-    }
+constexpr WaveBuilds wave_builds() {
+    constexpr WaveBudget b = wave_budget<FWD, INV>(kWholeRows);
+    if constexpr (!b.served) return WaveBuilds{{nullptr, nullptr, nullptr}};
+    else return WaveBuilds{{fft_ola_wave_kernel<FWD, INV, 0, b.occ_any>, fft_ola_wave_kernel<FWD, INV, 1, b.occ_c2>, fft_ola_wave_kernel<FWD, INV, 2, b.occ_any>}};
 }
-template <class FWD, class... INVS>
-bool wave_choices(const FftPlanDev& plan, uint32_t channels, WaveChoice* out) {
-    return (wave_choice<FWD, INVS>(plan, channels, out) || ...);
+template <class... Ps>
+WaveKernel wave_kernel(PairList<Ps...>, int pair, int chm) {
+    static constexpr WaveBuilds table[] = {wave_builds<typename Ps::Fwd, typename Ps::Inv>()...};
+    return pair < static_cast<int>(sizeof...(Ps)) ? table[pair].chm[chm] : nullptr;
 }
 
 }  // namespace
@@ -740,65 +657,21 @@ bool fft_wave_is_exact() {
 #endif
 }
 
-// Wave-per-transform kernels exist for the 44.1 <-> 48 kHz family (both directions) and for the families whose
-// input block is 512 frames (x2, /2, /4, /8, x3, x1.5 ...).  Returns hipErrorNotSupported when the plan is another
-// one (the caller then uses the workgroup kernels).
-hipError_t launch_fft_ola_wave(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
-                               uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                               hipStream_t stream) {
-    if (max_channels != min_channels) return hipErrorNotSupported;   // one wave layout per launch
-    if (plan.n_rc_f != plan.fft_in / 2 - 1 || plan.n_rc_i != plan.fft_out / 2 - 1) return hipErrorNotSupported;
-    if (plan.new_length != (plan.fft_in < plan.fft_out ? plan.fft_in + 1 : plan.fft_out)) return hipErrorNotSupported;
-    const uint32_t C = max_channels;
-    WaveChoice wc;
-    const bool found = wave_choices<W1176, W1280>(plan, C, &wc) || wave_choices<W1280, W1176>(plan, C, &wc)
+// The build fft_choose (fft_launch.cpp) names, launched as it says.
+hipError_t launch_fft_ola_wave(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream) {
 #if RSMP_EXP != 0   // (timing experiments instantiate the 44.1 <-> 48 kHz pair alone: 25 s instead of 160 s per build)
-                       ;
+    const WaveKernel fn = wave_kernel(HeadPairs{}, c.pair, c.chm);
 #else
-                       ||
-                       wave_choices<W512, W64, W128, W256, W768, W1024, W1536, W2048, W3072, W4096>(plan, C, &wc) ||
-                       wave_choices<W768, W64, W128, W256, W512>(plan, C, &wc) ||
-                       wave_choices<W1536, W64, W128>(plan, C, &wc) ||
-                       wave_choices<W588, W1280, W2560>(plan, C, &wc) || wave_choices<W882, W640, W1280>(plan, C, &wc) ||
-                       wave_choices<W1764, W640, W1280>(plan, C, &wc) || wave_choices<W2352, W1280, W2560>(plan, C, &wc) ||
-                       wave_choice<W1176, W2560>(plan, C, &wc) || wave_choice<W1280, W2352>(plan, C, &wc) ||
-                       wave_choices<W2560, W2352, W1176, W588>(plan, C, &wc) || wave_choices<W640, W882, W1764, W3528>(plan, C, &wc) || wave_choices<W3528, W640, W1280>(plan, C, &wc) ||
-                       wave_choices<W1280, W588, W882, W1764, W3528, W4704>(plan, C, &wc) ||
-                       wave_choices<W4704, W1280, W2560>(plan, C, &wc) || wave_choices<W5120, W1176, W2352>(plan, C, &wc) ||
-                       wave_choice<W2560, W4704>(plan, C, &wc) || wave_choice<W1176, W5120>(plan, C, &wc) ||
-                       wave_choice<W2352, W5120>(plan, C, &wc) || wave_choice<W588, W5120>(plan, C, &wc);
+    const WaveKernel fn = wave_kernel(WavePairs{}, c.pair, c.chm);
 #endif
-    if (!found) return hipErrorNotSupported;
-    const uint32_t kWavesPerGroup = wc.waves;
-    const size_t lds = wc.lds;
-    WaveKernel fn = wc.fn;
-    // Blocks per wave: every run after a stream's first recomputes its predecessor block (1 / run extra
-    // work), and the launch ends with a partly filled round unless the number of waves is close to a
-    // multiple of what the chip holds at once (3 workgroups of 4 waves per CU).
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const double slots = static_cast<double>(cus) * wc.resident;
-    uint32_t run = 16;
-    double best = -1.0;
-    for (uint32_t cand = 6; cand <= 64; ++cand) {
-        const double runs = static_cast<double>((max_blocks + cand - 1) / cand);
-        const double waves = runs * n_streams * C;
-        const double rounds = std::ceil(waves / slots);
-        const double useful = static_cast<double>(max_blocks) / (max_blocks + runs - 1.0);   // halo blocks
-        const double score = waves / (rounds * slots) * useful;
-        if (score > best + 1e-9) { best = score; run = cand; }
-    }
-    const uint32_t runs_per_stream = (max_blocks + run - 1) / run;
-    const uint32_t total_waves = runs_per_stream * n_streams * C;
-    const dim3 grid((total_waves + kWavesPerGroup - 1) / kWavesPerGroup);
-    if (lds > 64 * 1024) {   // dynamic LDS above 64 KiB must be opted into
+    if (fn == nullptr) return hipErrorNotSupported;
+    if (c.whole_rows != kWholeRows) return hipErrorInvalidValue;   // (the LDS bytes are for another build of this file)
+    if (c.grant_lds) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(fn, grid, dim3(kWavesPerGroup * 64), lds, stream, plan, d_descs, run, runs_per_stream,
-                       total_waves, C / 2);   // (channel pairs: read by the two-channel build only)
+    hipLaunchKernelGGL(fn, dim3(c.grid[0]), dim3(c.block), c.lds, stream, plan, d_descs, c.args[0], c.args[1], c.args[2], c.args[3]);
     return hipGetLastError();
 }
 

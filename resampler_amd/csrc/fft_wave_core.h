@@ -1,5 +1,5 @@
 // fft_wave_core.h -- what the wave-per-transform FFT kernels share (fft_wave.hip: a wave per channel; fft_pair.hip: a wave per
-// two-channel stream): the LDS access helpers, the plan type with its padded layouts, the Stockham stage and the fused /
+// two-channel stream): the LDS access helpers, the plan geometry (fft_wave_plan.h), the Stockham stage and the fused /
 // plain first passes.  Included inside `namespace rsmp { namespace { ... } }` of a .hip file, after fft_butterflies_pk.h
 // and after RSMP_FEAT is defined (the A/B switches of the slope experiments).
 #pragma once
@@ -46,87 +46,16 @@ __device__ __forceinline__ void lds_st(cf* p, cf v) {
 #endif
 }
 
-// A transform of N complex points in `Rs...` Stockham stages (2 .. 4 of them), as the reference's planner orders
-// them (src/fft/optimizer.rs).  Where the first two radices multiply to at most 21 values per unit (and a third
-// stage exists) they run as one register pass (wave_fused_first); every later stage but the inverse's last is a
-// wave_stage; the twiddle tables of all stages sit in LDS.
-// LDS stores go 16 lanes at a time over 32 banks (MI355X_MICROARCH.md, LDS table; tools/fft_bank_model.py counts the
-// array cycles of every pass of a plan pair).  A stage's lane i stores its value q at R (i - k) + k + q stride
-// (k = i mod stride): lanes 16 apart in i are in different blocks of `stride` columns unless stride >= 16, and a
-// block is (R - 1) stride values further than the lane index says -- two values per 16 lanes of shift keep the
-// 16 lanes of a store on distinct banks iff (R - 1) stride + pad is a multiple of 16 values.  (Radix 7, stride 21:
-// 147-value blocks, 2 values of padding; radix 8, stride 20: 4.)
-constexpr int stage_out_pad(int r, int stride) { return (16 - ((r - 1) * stride) % 16) % 16; }
-constexpr int gcd_c(int a, int b) { return b == 0 ? a : gcd_c(b, a % b); }
-// Twiddles a stage keeps per column in LDS: all R - 1 of the row, or -- radix 7 and 8 -- only w, w^2 and w^4 (the
-// stage multiplies the others out, see twiddle_expand; the tables of the 1176 <-> 1280 pair shrink from 39 to 29 KB).
-#if !defined(RSMP_FFT_WAVE_EXACT) && !defined(RSMP_FFT_WAVE_ALL_TWIDDLES)
-constexpr int fetch_count(int r) { return (r == 7 || r == 8) ? 3 : r - 1; }
+// The plan type with its padded layouts, the named plans and the pairs the kernels are built for: fft_wave_plan.h, which
+// the launch rules (fft_launch.cpp) read too.  What depends on whether radix-7 / 8 stages keep whole twiddle rows in LDS takes
+// this build's answer, kWholeRows.
+#include "fft_wave_plan.h"
+#if defined(RSMP_FFT_WAVE_EXACT) || defined(RSMP_FFT_WAVE_ALL_TWIDDLES)
+constexpr bool kWholeRows = true;
 #else
-constexpr int fetch_count(int r) { return r - 1; }
+constexpr bool kWholeRows = false;
 #endif
-template <int N_, int... Rs>
-struct WavePlan {
-    static constexpr int N = N_;
-    static constexpr int kStages = sizeof...(Rs);
-    static constexpr int kR[sizeof...(Rs)] = {Rs...};
-    static_assert(kStages >= 2 && kStages <= 5, "stages");
-    static constexpr int stride(int s) { int v = 1; for (int i = 0; i < s; ++i) v *= kR[i]; return v; }
-    static_assert(stride(kStages) == N_, "radices");
-    static constexpr bool kFused = kStages >= 3 && kR[0] * kR[1] <= 21;
-    // Stage twiddles, unique per column: stage s (s >= 1) holds stride(s) rows of R_s - 1.  In LDS the rows of a
-    // wave_stage are (R - 1) | 1 values apart: lane k reads row k, and an even row length puts lanes 16 apart
-    // (radix 7: six values = 12 dwords) on the same banks.  (The fused pass reads its rows by constant index.)
-    static constexpr int row(int r) { return fetch_count(r) | 1; }
-    static constexpr int pitch(int s) { return kFused && s == 1 ? kR[1] - 1 : row(kR[s]); }
-    static constexpr int tab(int s) { int off = 0; for (int i = 1; i < s; ++i) off += stride(i) * pitch(i); return off; }   // LDS offset of stage s
-    static constexpr int src(int s) { int off = 0; for (int i = 1; i < s; ++i) off += stride(i) * (kR[i] - 1); return off; }   // offset in the plan's array
-    static constexpr int kTw = tab(kStages);
-    static constexpr int kRc = N_ / 2 - 1;   // real <-> complex twiddles
-    // Padding between passes (LDS banks).  The first pass (fused or not) writes kUnit values per lane side by side:
-    // an even kUnit puts lanes 32 / gcd(2 kUnit, 32) apart on the same banks, so one value of padding follows every
-    // kPadJ units (20 values per unit: every 4) where the next stage's input distance is a multiple of that period.
-    // After the blocks of a later stage: stage_out_pad, where the stage that follows reads block by block.
-    // in_pad(s): what stage s's input distance N / R_s grows by; in_period(s): elements between two padding values
-    // inside that distance (0 = none).
-    static constexpr int kUnit = kFused ? kR[0] * kR[1] : kR[0];
-    static constexpr int kNext = kFused ? 2 : 1;   // the stage that reads the first pass's output
-    // (Plans above 2048 points run at the 256-register cap of their wide workgroups: the padded addressing spilled
-    // there -- 2352 -> 2560 points 0.80 -> 1.00 ms -- so they keep the plain layout, but for the radix-7 blocks.)
-    static constexpr bool kPadded = N_ <= 2048;
-    static constexpr int first_padj() {
-        if (!kPadded || kUnit % 2 != 0 || kNext >= kStages) return 0;
-        const int p = 32 / gcd_c(2 * kUnit, 32);
-        return (N_ / kR[kNext < kStages ? kNext : 0]) % (p * kUnit) == 0 ? p : 0;
-    }
-    static constexpr int kPadJ = first_padj();
-    static constexpr int out_pad(int s) {
-        if (s < 1 || s + 1 >= kStages || (kFused && s == 1)) return 0;
-        if (stride(s) >= N_ / kR[s]) return 0;   // one block
-        const int p = kPadded || (kR[s] == 7 && stride(s) == 21) ? stage_out_pad(kR[s], stride(s)) : 0;
-        return p != 0 && N_ / kR[s + 1] == stride(s + 1) ? p : 0;
-    }
-    static constexpr int in_pad(int s) {
-        if (s == kNext) return kPadJ ? (N_ / kR[s]) / (kPadJ * kUnit) : 0;
-        return s >= 2 ? out_pad(s - 1) : 0;
-    }
-    static constexpr int in_period(int s) { return s == kNext && kPadJ && N_ / kR[s] > kPadJ * kUnit ? kPadJ * kUnit : 0; }
-    static constexpr int buf_values() {   // what the wave's buffer needs: the points + bin N and its neighbour (real <-> complex passes), or the widest padded layout
-        int pad = kPadJ ? N_ / (kPadJ * kUnit) : 0;
-        for (int s = 1; s + 1 < kStages; ++s) {
-            const int p = out_pad(s) * (N_ / stride(s + 1));
-            if (p > pad) pad = p;
-        }
-        return N_ + (pad > 2 ? pad : 2);
-    }
-    static constexpr int kBuf = buf_values();
-    static bool matches(uint32_t n, uint32_t n_stages, const uint32_t* radix) {
-        if (n != static_cast<uint32_t>(N_) || n_stages != static_cast<uint32_t>(kStages)) return false;
-        for (int s = 0; s < kStages; ++s)
-            if (radix[s] != static_cast<uint32_t>(kR[s])) return false;
-        return true;
-    }
-};
+constexpr int fetch_count(int r) { return fetch_count(r, kWholeRows); }
 
 // One Stockham stage in place in the wave's LDS buffer: butterfly i reads buf[i + q*M], twiddles inputs
 // 1..R-1 with w[(i mod STRIDE)*(R-1) + q-1] and writes buf[R*i - (R-1)*k + q*STRIDE]

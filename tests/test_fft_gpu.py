@@ -371,6 +371,50 @@ def test_even_channel_counts_run_as_channel_pairs(ch, in_hz, out_hz, blocks):
 
 
 @pytest.mark.gpu
+def test_every_kernel_family_once_at_its_smallest_shape():
+    """One bulk launch per family the launch rules (fft_launch.cpp) can choose, at the smallest shape that reaches it,
+    against the reference run per channel: the pair kernel (two channels, four blocks: the streaming rule's first launch),
+    the wave kernel's two-channel, channel-pairs and any-channel builds, the one-buffer kernel of the longest plans -- and, in
+    a child process with RSMP_FFT_WAVE=0 (the switches are read once per process), the 44.1 <-> 48 kHz workgroup kernel,
+    its two-channel build and the generic kernel's one-wave workgroups (tools/fft_pair_check.py, as tests/test_knobs_gpu.py
+    runs it)."""
+    import os
+    import re
+    import subprocess
+    import sys
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    for ch, in_hz, out_hz, blocks in ((2, 44100, 48000, 4), (2, 44100, 48000, 3), (4, 44100, 48000, 7), (3, 44100, 48000, 7),
+                                      (1, 16000, 384000, 3)):
+        g = ra.ResamplerFft.new(ch, sr(in_hz), sr(out_hz))
+        n_in, n_out = g.chunk_size_input(), g.chunk_size_output()
+        x = synth.fast_noise(blocks * n_in, seed=ch + blocks)
+        ref = np.zeros((blocks, n_out // ch, ch), np.float32)
+        row = np.zeros(n_out // ch, np.float32)
+        for c in range(ch):
+            r = o.OracleFft(1, in_hz, out_hz)
+            for k in range(blocks):
+                assert r.resample(np.ascontiguousarray(x[k * n_in:(k + 1) * n_in].reshape(-1, ch)[:, c]), row) == 0
+                ref[k, :, c] = row
+        d_in = torch.from_numpy(x).to(dev)
+        d_out = torch.zeros(blocks * n_out, device=dev)
+        torch.cuda.synchronize()
+        g.resample_bulk_device(d_in, d_out, blocks)
+        torch.cuda.synchronize()
+        assert rms(d_out.cpu().numpy(), ref.reshape(-1)) <= RMS_TOL, (ch, in_hz, out_hz, blocks)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, RSMP_DEBUG="1", RSMP_FFT_WAVE="0", PYTHONPATH=root)
+    p = subprocess.run([sys.executable, os.path.join(root, "tools", "fft_pair_check.py")] + "44100 48000 1 9 44100 48000 2 9 96000 48000 1 9".split(),
+                       env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if "worst block rms" in ln]
+    assert len(lines) == 3, p.stdout
+    for ln in lines:
+        assert "bad blocks []" in ln, ln
+        assert float(re.search(r"worst block rms ([0-9.e+-]+)", ln).group(1)) <= RMS_TOL, ln
+
+
+@pytest.mark.gpu
 def test_exact_build_is_bit_identical_to_the_reference_arithmetic():
     """libresampler_amd_fftexact.so = the same library with the wave kernel compiled without fused
     multiply-adds and with every twiddle fetched (make -C resampler_amd/csrc): its output equals the CPU

@@ -171,3 +171,69 @@ def test_deal_of_workgroups(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     _clean(run)
     assert "fir_split_deal_check: ok" in run.stdout
+
+
+# ---- the FFT launch rules that left the kernel files ----------------------------------------------------------------------
+def _load_fixture_maker():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_fft_launch_fixture", os.path.join(ROOT, "tests", "golden", "make_fft_launch_fixture.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_fft_launch_rules_as_before_the_move(tmp_path):
+    """fft_launch.cpp (plain C++, g++ with ASan + UBSan, a process of its own per setting of the debug switches and per
+    library): the kernel build, grid, block, LDS bytes, whether the LDS is opted into and the scalar kernel arguments of every
+    request of tests/host/fft_launch_cases.h -- the 90 ordered pairs of the ten sample rates, (max, min) channels (1,1) (2,2)
+    (3,3) (4,4) (6,6) (8,8) (2,1), 16 / 24 / 32-bit PCM at (2,2) and at (1,1), 1 / 3 / 64 / 1024 streams, 1 .. 4096 blocks, 256 and
+    64 CUs, occupancy 1 / 2 / 4 for the workgroup kernels, the ordinary and the exact library -- equal what the kernel files of
+    the commit before the move did (tests/golden/make_fft_launch_fixture.py recorded their launches): per group the row count
+    and SHA-256, under the default setting the rows of 44100 <-> 48000 in full (the fixture keeps what a row says of the launch; its
+    request is the walk's, under the group's hash).  A row names its build by the ordinal of first
+    appearance, so equal rows mean that the builds named here and the function pointers launched there correspond one to one."""
+    maker = _load_fixture_maker()
+    with open(os.path.join(ROOT, "tests", "golden", "fft_launch.json")) as fh:
+        fx = json.load(fh)
+    assert fx["settings"] == maker.SETTINGS
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fft_launch_dump.cpp"
+    exe = str(tmp_path / "fft_launch_dump")
+    srcs = [os.path.join(ROOT, "tests", "host", "fft_launch_dump.cpp")]
+    srcs += [os.path.join(CSRC, f) for f in ("fft_launch.cpp", "fft_plan.cpp", "filter_design.cpp", "common.cpp")]
+    subprocess.run([gxx] + SANITIZE + ["-Wno-unknown-pragmas"] + srcs + ["-o", exe], check=True)
+    families, wave_builds = set(), set()
+    for setting, env_add in maker.SETTINGS.items():
+        env = {k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}
+        if env_add:
+            env.update(env_add, RSMP_DEBUG="1")
+        got, full = {}, {}
+        for exact in ("0", "1"):
+            run = subprocess.run([exe, exact], env=env, capture_output=True, text=True, timeout=300)
+            _clean(run)
+            groups, rows, kernels = maker.digest(run.stdout, setting == "default")
+            for bits in (16, 24, 32):   # PCM input of one-channel streams: no kernel reads it
+                chunk = run.stdout.split("# group %s 1 1 %d\n" % (exact, bits))[1].split("# ")[0]
+                assert chunk.count("\n") == chunk.count("| notsupported\n") == groups["%s 1 1 %d" % (exact, bits)][0] > 0
+            got.update(groups)
+            full.update(rows)
+            # build names <-> ordinals, one to one in both directions
+            assert [int(k[0]) for k in kernels] == list(range(len(kernels))) and len({k[1] for k in kernels}) == len(kernels)
+            for _, name in kernels:
+                fields = name.split()
+                families.add(fields[0])
+                if fields[0] == "wave":
+                    wave_builds.update(fields[2:4])
+        assert sorted(got) == sorted(fx["groups"][setting]) and len(got) == 2 * 13, setting
+        for key in got:
+            assert got[key] == fx["groups"][setting][key], (setting, key)
+        if setting == "default":
+            want = maker.unshared(fx)
+            assert sorted(full) == sorted(want) and sum(text.count(";") + 1 for text in want.values()) > 2000
+            for key in full:
+                assert full[key].split(";") == want[key].split(";"), key
+    # (statuses: a fixture cannot pass while empty of a path)
+    assert families == {"pair", "wave", "ct", "ct2", "generic", "big"}
+    assert wave_builds == {"chm=0", "chm=1", "chm=2", "occ=1", "occ=2", "occ=3"}
+    text = json.dumps(fx["launches"])
+    assert "notsupported" in text and "ok " in text
