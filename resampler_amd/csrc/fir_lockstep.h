@@ -23,15 +23,10 @@
 #include "fir_mirror_core.h"
 #include "fir_mirror_fast.h"
 #include "fir_kernels.h"
+#include "fir_lockstep_plan.h"
 #include "fir_periodic.h"
 
 namespace rsmp {
-
-constexpr uint32_t kLsWaves = 8;              // waves per workgroup (two workgroups per CU: <= 128 VGPRs)
-constexpr uint32_t kLsMaxSlots = 16;          // streams per workgroup
-constexpr uint32_t kLsSegCap = 40;            // exact position runs kept per stream and step
-constexpr uint32_t kLsMaxBlk = 12;            // 16-tap blocks of a tile window held in registers (row_len <= 192)
-constexpr uint32_t kLsLdsLimit = 160 * 1024;
 
 struct LockstepStream {        // per bound stream, constant between binds (HBM)
     const float* in;           // a step reads in + in_offset, in_frames frames
@@ -40,32 +35,6 @@ struct LockstepStream {        // per bound stream, constant between binds (HBM)
     float* hist_alt;           // `hist` and leaves its tail in `hist_alt`, an odd one the other way round
     const float* coeffs;       // [1024][taps] polyphase table
     uint64_t out_cap_frames;   // room of `out` per step, in frames
-};
-
-struct LockstepGroup {         // one workgroup's share: `count` streams of one geometry (HBM)
-    uint32_t first, count;     // streams [first, first + count) of the batch's internal order
-    uint32_t channels, taps;
-    uint32_t periodic;         // 0: every output in the reference's two-row form (any ratio)
-    uint32_t num, den;         // in_hz / out_hz reduced
-    uint32_t a, b;             // super period: a = r * num input frames -> b = r * den outputs
-    uint32_t row_len, n_tiles; // padded window of a 16-class tile; tiles per super period
-    uint32_t guard_frames;     // zeroed frames in front of a stream's span in LDS (>= a)
-    uint32_t span_frames;      // capacity of the span itself (buffered + new frames)
-    uint32_t region_frames;    // guard + span + zeroed tail (>= a + row_len)
-    uint32_t max_out;          // output frames one step can produce
-    uint32_t wrap_words;       // bitmap words per stream: ceil(max_out / 32)
-    uint32_t wrap_cap;         // wrap list entries per stream
-    uint32_t max_cols;         // column table entries
-    const float* class_coef;   // [tile][row_len / 16][64 lanes][4 steps] (A-operand order)
-    const TileMeta* class_meta;
-    uint32_t lds_bytes;        // what this group needs
-    uint32_t slots;            // streams per workgroup the LDS layout is sized for (>= count)
-    uint32_t split;            // 1: two-channel streams on the fp16 matrix cores with split operands (fir_split.hip's
-                               //    arithmetic): class_coef is the split table, the LDS holds a transposed fp16 image
-    uint32_t rows;             // split: rows (frames) of the image: last tile's window start + row_len
-    uint32_t row_bytes;        // split: bytes per image row: 160 (32 B of padding: conflict-free transposed reads), or
-                               //        128 where only the unpadded image leaves room for two workgroups per CU
-    uint32_t pad0;
 };
 
 struct LockstepArgs {
@@ -102,36 +71,13 @@ struct LsPlanHeader {          // head of a plan record; followed by kLsSegCap r
     FirMirrorState after;      // the stream's state after the step
     uint64_t pad1;
 };
-static_assert(sizeof(LsPlanHeader) == 160, "plan record layout");
-constexpr uint32_t kLsRecSegs = 160, kLsRecWraps = kLsRecSegs + kLsSegCap * 24;
-inline uint32_t lockstep_rec_stride(uint32_t wrap_cap) { return (kLsRecWraps + 4 * wrap_cap + 15) / 16 * 16; }
+static_assert(sizeof(LsPlanHeader) == kLsRecSegs, "plan record layout (fir_lockstep_plan.h: lockstep_rec_stride)");
 
 constexpr uint32_t kLsStatusRunOverflow = 1;   // more than kLsSegCap position runs in one step
 constexpr uint32_t kLsStatusNonFinite = 2;     // a step saw non-finite samples (reference-form path taken)
 constexpr uint32_t kLsStatusAperiodic = 4;     // the f64 drift left the class tables' tolerance
 constexpr uint32_t kLsStatusPartialAccept = 8; // rsmp_fir_lockstep_run: a call accepted fewer frames than it was offered
 constexpr uint32_t kLsStatusPlannerCheck = 16; // rsmp_fir_lockstep_run: the replay of a call found a premise of the planner's closed form violated (never observed)
-
-// Geometry of one (rate pair, taps, channels, step size) combination.
-struct LockstepGeometry {
-    bool periodic = false;
-    uint32_t num = 0, den = 0, r = 0, a = 0, b = 0, taps = 0, row_len = 0, n_tiles = 0;
-    uint32_t guard_frames = 0, span_frames = 0, region_frames = 0, max_out = 0, cols_per_stream = 0;
-    uint32_t slots = 1;        // streams per workgroup
-    uint32_t wrap_words = 0, wrap_cap = 0, max_cols = 0, lds_bytes = 0;
-    bool split = false;        // fp16x2 split operands (two-channel streams, unless exact f32 products are asked for)
-    uint32_t rows = 0;         // split: rows of the LDS image
-    uint32_t row_bytes = 0;    // split: bytes per image row (160, or 128 without padding)
-};
-// allow_split = false: exact-f32 products (RSMP_FIR_KERNEL_PERIODIC_F32 on the streams, or RSMP_LS_EXACT=1).
-LockstepGeometry lockstep_geometry(uint64_t num, uint64_t den, double ratio, uint32_t taps,
-                                   uint32_t channels, uint32_t step_frames, bool allow_split = true);
-// The PeriodicGeometry view of it that build_class_table understands (f32 matrix-core layout, or the split
-// kernel's fp16x2 layout).
-PeriodicGeometry lockstep_class_geometry(const LockstepGeometry& g);
-constexpr uint32_t kLsImageRowBytes = 160;   // split image: (2 channels x 2 planes) x 32 B + 32 B of padding (fir_split.hip)
-constexpr uint32_t kLsImageRowBytesPacked = 128;   // ... without the padding
-constexpr uint32_t kLsLdsPerWorkgroup = 80 * 1024 - 512;   // two workgroups per CU (160 KB, less the allocation granule)
 
 hipError_t launch_fir_lockstep(const LockstepArgs& args, uint32_t n_groups, uint32_t max_lds_bytes,
                                hipStream_t stream);
@@ -181,19 +127,10 @@ struct LsCommitArgs {
     uint32_t n_streams;
 };
 // parts: 1 = K1 (the predictions), 2 = K2 + K3 (chain, replay); 3 = all three in `stream`
+// What is launched -- grids, blocks, the chain's build -- is fir_lockstep_plan.h's lockstep_plan_shape(n_streams, k).
 // (commit, with part 1: K1 also does what launch_fir_lockstep_commit does -- the first thread of a stream's calls copies the
 // stream's scratch results into place -- and reads the states it predicts from out of the scratch copies: one launch less in
 // front of a run planned ahead)
-// The planner's serial kernels (chain, replay) pack kLsPlanPack streams into a workgroup -- one CU -- for batches of fewer than
-// kLsPlanPackBelow streams: the CUs they take are then few and known (lockstep_plan_cus), whoever reaches the chip first.
-constexpr uint32_t kLsPlanPack = 4, kLsPlanPackBelow = 256;   // (pack 1 / 2 / 4 / 8 at 128 streams: 0.89 / 0.71-0.86 / 0.73 / 0.83-0.95 us per step, profiles/r06/ab_c4_shard.txt: eight waves of this much CODE on one CU starve each other of instructions)
-uint32_t lockstep_plan_pack(size_t n_streams);   // (fir_lockstep_run.hip; RSMP_LS_PACK, debug: 1 / 2 / 4 / 8)
-// CUs the replay (K3) of a run of k calls takes when it has a wave per chunk (batches below kLsPlanPackBelow streams): sixteen waves a CU
-uint32_t lockstep_replay_cus(size_t n_streams, uint32_t k);   // (fir_lockstep_run.hip)
-inline uint32_t lockstep_plan_cus(size_t n_streams) {
-    const uint32_t pack = lockstep_plan_pack(n_streams);
-    return pack > 1 ? static_cast<uint32_t>((n_streams + pack - 1) / pack) : static_cast<uint32_t>((n_streams + 3) / 4);
-}
 // (k1_done, with part 1: an event the K1 launch itself completes -- hipExtLaunchKernel's stop event --, no packet of its own
 // behind it as hipEventRecord would put there)
 hipError_t launch_fir_lockstep_plan(const LsRunArgs& args, hipStream_t stream, int parts = 3, const LsCommitArgs* commit = nullptr,

@@ -30,10 +30,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
 #include "common.h"
+#include "fir_kernel_launch.h"
 
 namespace rsmp {
 
@@ -58,7 +57,6 @@ typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 constexpr uint32_t kLsPeakMax = 138;                               // no scale is derived from a peak of 2^11 and above (samples of 2^13 and above overflow: reference form)
 constexpr uint32_t kLsPlanner = kLsWaves - 1;                      // the wave that plans the next step
 constexpr uint32_t kLsStagers = kLsWaves - 2;                      // waves 1 .. kLsStagers stage the frames
-constexpr uint32_t kLsSyncBytes = 32;                              // n_cols, unit counter, image counter, early flag, ready counter
 constexpr uint32_t kLsMaxK32 = 6;                                  // 32-tap steps of a tile window (row_len <= 192)
 
 template <class T>
@@ -86,11 +84,7 @@ struct PlanLds {             // one stream's step, in LDS
     float* out;              // where the step's first output frame goes
     const void* runs;        // the step's exact position runs (SegLds[n_segs]): in LDS, or in the plan record
 };
-static_assert(sizeof(PlanLds) == 64, "PlanLds layout");
-
-static_assert(sizeof(FirMirrorState) == 88, "the stash holds 16 states of 88 bytes in 16 x 96 bytes: the last 128 bytes are the column peaks");
-constexpr uint32_t kLsPeakOff = kLsMaxSlots * 64 + kLsSyncBytes + kLsMaxSlots * 88;   // colpeak[16] (channel 0), peak counter, the columns' scales: channel 0 (4 words), channel 1 (4 words)
-constexpr uint32_t kLsPeak1Off = kLsMaxSlots * 64 + kLsSyncBytes + kLsMaxSlots * 96;  // colpeak1[16]: channel 1 (round 5: a scale per channel, as fir_split.hip)
+static_assert(sizeof(PlanLds) == kLsPlanLdsBytes, "PlanLds layout (fir_lockstep_plan.h: the front of the LDS)");
 
 struct ColLds {              // one column of the matrix product: super period q of a stream
     int32_t frame0;          // span-relative frame of absolute input frame q * a
@@ -103,28 +97,6 @@ struct SegLds {
     uint32_t first, count;
     double p0, inc;
 };
-
-struct LsLayout {
-    uint32_t ptrs, colsrc, cols, segs, wbits, wlist, spans, total;   // byte offsets
-};
-// data_bytes: the spans of the streams (slots x region_frames x channels f32) or the split image (rows x 160 B)
-__host__ __device__ inline LsLayout ls_layout(uint32_t slots, uint32_t max_cols, uint32_t wrap_words,
-                                              uint32_t wrap_cap, uint32_t data_bytes) {
-    LsLayout l;
-    l.ptrs = kLsMaxSlots * 64 + kLsSyncBytes + kLsMaxSlots * 96 + 64;  // PlanLds[16], sync words, state stash[16], channel 1's column peaks
-    l.colsrc = l.ptrs + kLsMaxSlots * 32;                         // (hist, in, hist_next) pointers per slot
-    l.cols = l.colsrc + 16 * 32;                                  // split: where each of the 16 columns' frames come from
-    l.segs = (l.cols + max_cols * 16 + 7) & ~7u;
-    l.wbits = l.segs + slots * kLsSegCap * 24;
-    l.wlist = l.wbits + slots * wrap_words * 4;
-    l.spans = (l.wlist + slots * wrap_cap * 4 + 15) & ~15u;
-    l.total = l.spans + data_bytes;
-    return l;
-}
-__host__ __device__ inline uint32_t ls_data_bytes(bool split, uint32_t rows, uint32_t row_bytes, uint32_t slots,
-                                                  uint32_t region_frames, uint32_t channels) {
-    return split ? rows * row_bytes : slots * region_frames * channels * 4u;
-}
 
 // mirror_call sink writing into LDS.
 struct LdsSink {
@@ -288,8 +260,8 @@ __global__ __launch_bounds__(kLsWaves * 64, kLsWaves / 2) void fir_lockstep_kern
     struct ColSrc { const float* hist; const float* in; int32_t frame0; uint32_t hist_frames, span_frames, pad; };   // 32 B
     ColSrc* colsrc = reinterpret_cast<ColSrc*>(lds + lay.colsrc);
     PlanLds* plan = reinterpret_cast<PlanLds*>(lds);
-    uint32_t* n_cols_p = reinterpret_cast<uint32_t*>(lds + kLsMaxSlots * 64);
-    FirMirrorState* stash = reinterpret_cast<FirMirrorState*>(lds + kLsMaxSlots * 64 + kLsSyncBytes);   // new states until every reader of the old ones is done
+    uint32_t* n_cols_p = reinterpret_cast<uint32_t*>(lds + kLsFrontPlans);
+    FirMirrorState* stash = reinterpret_cast<FirMirrorState*>(lds + kLsStashOff);   // new states until every reader of the old ones is done
     ColLds* cols = reinterpret_cast<ColLds*>(lds + lay.cols);
     SegLds* segs = reinterpret_cast<SegLds*>(lds + lay.segs);
     uint32_t* wbits = reinterpret_cast<uint32_t*>(lds + lay.wbits);
@@ -1112,118 +1084,14 @@ __global__ __launch_bounds__(kLsWaves * 64, kLsWaves / 2) void fir_lockstep_kern
 
 }  // namespace
 
-LockstepGeometry lockstep_geometry(uint64_t num, uint64_t den, double ratio, uint32_t taps,
-                                   uint32_t channels, uint32_t step_frames, bool allow_split) {
-    static const bool exact_knob = [] { const char* e = rsmp::knob("RSMP_LS_EXACT"); return e && atoi(e) != 0; }();
-    LockstepGeometry g;
-    g.taps = taps;
-    g.num = static_cast<uint32_t>(num);
-    g.den = static_cast<uint32_t>(den);
-    // With out_cap >= buffer_size_output a step never leaves more than taps - 1 frames buffered, and
-    // it produces at most (buffered + new - taps + 1) / ratio + 1 frames.
-    g.span_frames = taps + step_frames + 8;
-    g.max_out = static_cast<uint32_t>(std::ceil(static_cast<double>(step_frames + 8) / ratio)) + 2;
-    g.wrap_words = (g.max_out + 31) / 32;
-    auto finish = [&](bool periodic) -> bool {
-        g.periodic = periodic;
-        if (!periodic) {
-            g.r = g.a = 0;
-            g.b = 1;
-            g.row_len = g.n_tiles = 0;
-            g.guard_frames = 0;
-            g.region_frames = g.span_frames + 64;   // (the last staging piece may run 63 dwords past the span)
-            g.cols_per_stream = 1;
-            g.wrap_cap = 1;
-        }
-        const uint32_t want = periodic ? std::max(1u, 16u / g.cols_per_stream) : 4u;
-        for (uint32_t s = std::min(want, kLsMaxSlots); s >= 1; --s) {
-            const uint32_t bytes = ls_layout(s, s * g.cols_per_stream, g.wrap_words, g.wrap_cap,
-                                             ls_data_bytes(g.split, g.rows, g.row_bytes, s, g.region_frames, channels)).total;
-            // Two workgroups per CU: 80 KB each.  One dynamic LDS size serves the whole launch, so a group above
-            // that would halve the occupancy of every group: a split image that does not fit makes way for the
-            // exact-f32 layout (which drops to one stream per workgroup before it gives up on that).
-            if (g.split && s * g.cols_per_stream > 16) continue;   // one image = 16 columns (a long step of a high ratio has more: f32 layout)
-            if (bytes <= (s > 1 || g.split ? kLsLdsPerWorkgroup : kLsLdsLimit)) {
-                g.slots = s;
-                g.max_cols = s * g.cols_per_stream;
-                g.lds_bytes = bytes;
-                return true;
-            }
-        }
-        return false;
-    };
-    if (num != 0 && den != 0 && num <= (1u << 20) && den <= (1u << 20)) {
-        const uint32_t shift = static_cast<uint32_t>((15 * num + den - 1) / den);
-        g.split = allow_split && !exact_knob && channels == 2;
-        g.row_len = g.split ? (taps + shift + 31) / 32 * 32 : (taps + shift + 15) / 16 * 16;
-        uint64_t r = (96 + den - 1) / den;
-        if (r == 0) r = 1;
-        const uint64_t a = num * r, b = den * r;
-        if (a <= 8192 && b <= 65536 && g.row_len <= 16 * kLsMaxBlk) {
-            g.r = static_cast<uint32_t>(r);
-            g.a = static_cast<uint32_t>(a);
-            g.b = static_cast<uint32_t>(b);
-            g.n_tiles = (g.b + 15) / 16;
-            g.guard_frames = g.a + (g.a & 1u);
-            g.region_frames = g.guard_frames + g.span_frames + g.a + g.row_len;
-            g.region_frames += g.region_frames & 1u;
-            g.cols_per_stream = (g.max_out - 1) / g.b + 2;
-            g.wrap_cap = g.max_out / g.den + 2;
-            g.rows = static_cast<uint32_t>((static_cast<uint64_t>(g.n_tiles - 1) * 16 * g.a) / g.b) + g.row_len;
-            g.row_bytes = kLsImageRowBytes;
-            if (finish(true)) return g;
-            if (g.split) {   // without the rows' padding (transposed reads then meet on banks: 2-4x the LDS time of a unit, still far below f32 products)
-                g.row_bytes = kLsImageRowBytesPacked;
-                if (finish(true)) return g;
-            }
-            if (g.split) {   // the image does not fit: exact-f32 layout
-                g.split = false;
-                g.row_len = (taps + shift + 15) / 16 * 16;
-                if (g.row_len <= 16 * kLsMaxBlk && finish(true)) return g;
-            }
-        }
-    }
-    g.split = false;
-    if (!finish(false)) g.lds_bytes = 0;   // caller reports the failure
-    return g;
-}
-
-PeriodicGeometry lockstep_class_geometry(const LockstepGeometry& g) {
-    PeriodicGeometry p;
-    p.ok = g.periodic;
-    p.a = g.a;
-    p.b = g.b;
-    p.den = g.den;
-    p.taps = g.taps;
-    p.row_len = g.row_len;
-    p.n_tiles = g.n_tiles;
-    p.mfma = g.split ? 3 : 1;   // A-operand order of v_mfma_f32_16x16x4_f32, or the split table of fir_split.hip
-    p.planes = g.split ? 2 : 0;
-    p.inline_wraps = false;
-    return p;
-}
-
 hipError_t launch_fir_lockstep(const LockstepArgs& args, uint32_t n_groups, uint32_t max_lds_bytes,
                                hipStream_t stream) {
     if (n_groups == 0) return hipSuccess;
     int device = 0;
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess) return e;
-    static std::mutex mu;
-    static std::map<int, bool> granted;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        bool& have = granted[device];
-        if (!have) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(fir_lockstep_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLsLdsLimit);
-            if (e != hipSuccess) return e;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(fir_lockstep_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLsLdsLimit);
-            if (e != hipSuccess) return e;
-            have = true;
-        }
-    }
+    for (const void* fn : {reinterpret_cast<const void*>(fir_lockstep_kernel<false>), reinterpret_cast<const void*>(fir_lockstep_kernel<true>)})
+        if ((e = grant_dynamic_lds(device, fn, kLsLdsLimit)) != hipSuccess) return e;
     static const char* trace_path = rsmp::knob("RSMP_LS_TRACE");
     if (trace_path) {   // diagnostic: one synchronous traced step, phase clocks written to the file
         LockstepArgs a = args;

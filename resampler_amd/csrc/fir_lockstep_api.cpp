@@ -9,6 +9,7 @@
 #include <cstring>
 #include <tuple>
 
+#include "fir_kernel_launch.h"
 #include "fir_lockstep_batch.h"
 
 using rsmp::DeviceGuard;
@@ -42,39 +43,6 @@ int upload_states(rsmp_fir_lockstep* ls) {
     RSMP_HIP_CHECK(hipMemcpy(ls->d_states.get(), ls->h_states.data(), n * sizeof(FirMirrorState),
                              hipMemcpyHostToDevice));
     return RSMP_OK;
-}
-
-// One workgroup of the step kernel: `count` streams from internal index `first` on, all of geometry `geo` and class `class_index`.
-LockstepGroup make_group(const rsmp::LockstepGeometry& geo, const rsmp_fir* r0, size_t first, size_t e, const rsmp::ClassTable& ct, uint32_t class_index) {
-    LockstepGroup g;
-    std::memset(&g, 0, sizeof g);
-    g.first = static_cast<uint32_t>(first);
-    g.count = static_cast<uint32_t>(std::min<size_t>(geo.slots, e - first));
-    g.channels = static_cast<uint32_t>(r0->channels);
-    g.taps = static_cast<uint32_t>(r0->taps);
-    g.periodic = geo.periodic ? 1u : 0u;
-    g.num = geo.num;
-    g.den = geo.den ? geo.den : 1u;
-    g.a = geo.a;
-    g.b = geo.b ? geo.b : 1u;
-    g.row_len = geo.row_len;
-    g.n_tiles = geo.n_tiles;
-    g.guard_frames = geo.guard_frames;
-    g.span_frames = geo.span_frames;
-    g.region_frames = geo.region_frames;
-    g.max_out = geo.max_out;
-    g.wrap_words = geo.wrap_words;
-    g.wrap_cap = geo.wrap_cap;
-    g.max_cols = geo.max_cols;
-    g.class_coef = ct.d_coef;
-    g.class_meta = ct.d_meta;
-    g.lds_bytes = geo.lds_bytes;
-    g.slots = geo.slots;
-    g.split = geo.split ? 1u : 0u;
-    g.rows = geo.rows;
-    g.row_bytes = geo.row_bytes;
-    g.pad0 = class_index;   // (host side only: which DriftClass the group's tables belong to)
-    return g;
 }
 
 // Creation, first half: the streams sorted into drift classes, the classes cut into the step kernel's workgroups.
@@ -134,11 +102,9 @@ bool build_classes_and_groups(rsmp_fir_lockstep* ls) {
         cl.seen_drift = cl.table_drift;
         const uint32_t class_index = static_cast<uint32_t>(ls->drift.classes.size());
         ls->drift.classes.push_back(std::move(cl));
-        for (size_t first = k; first < e; first += geo.slots) {
-            ls->groups.push_back(make_group(geo, r0, first, e, ct, class_index));
-            if (geo.lds_bytes > ls->max_lds) ls->max_lds = geo.lds_bytes;
-            if (rsmp::lockstep_rec_stride(geo.wrap_cap) > ls->rec_stride) ls->rec_stride = rsmp::lockstep_rec_stride(geo.wrap_cap);
-        }
+        const rsmp::LsCutMax most = rsmp::lockstep_cut_groups(ls->groups, geo, static_cast<uint32_t>(r0->channels), k, e, ct.d_coef, ct.d_meta, class_index);
+        ls->max_lds = std::max(ls->max_lds, most.lds_bytes);
+        ls->rec_stride = std::max(ls->rec_stride, most.rec_stride);
         for (size_t i = k; i < e; ++i) {
             const rsmp_fir* r = rs[ls->order[i]];
             if (r->mirror.available() >= r->taps + 8) {
@@ -152,33 +118,6 @@ bool build_classes_and_groups(rsmp_fir_lockstep* ls) {
         k = e;
     }
     return true;
-}
-
-// Workgroup order = dispatch order: with more workgroups than CUs (two fit a CU) number k + CUs becomes the second
-// tenant of the CU that took number k.  The slow geometries first and the quick ones last pairs each slow workgroup
-// with a quick one (or leaves it alone, see below) instead of with its own kind -- a step ends with its slowest workgroup, and
-// two slow tenants slow each other (`tools/ls_trace.py`: the 20-tile and the 505-row images end at 46-52 k cycles, the
-// one-stream 48 -> 96 kHz ones at 27 k).  Cost: matrix units + rows to stage, a packed image's bank conflicts on top.
-void order_workgroups(rsmp_fir_lockstep* ls) {
-    auto cost = [](const LockstepGroup& g) {
-        const double units = static_cast<double>(g.n_tiles) * ((g.max_cols + 15) / 16);
-        return units + g.count * (g.split ? g.rows : g.region_frames) / 64.0 + (g.split && g.row_bytes == rsmp::kLsImageRowBytesPacked ? 10.0 : 0.0);
-    };
-    std::stable_sort(ls->groups.begin(), ls->groups.end(),
-                     [&](const LockstepGroup& x, const LockstepGroup& y) { return cost(x) > cost(y); });
-    // ... and the slowest of all ALONE: with n workgroups on c CUs the indices n - c .. c - 1 get no second tenant, so the
-    // order is [next slowest: first tenants][slowest: alone][quickest: second tenants] (0.0184 -> 0.0181 ms per step)
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ls->device);
-    const size_t n = ls->groups.size(), c = static_cast<size_t>(cus);
-    if (n > c && n < 2 * c) {
-        const size_t second = n - c, alone = c - second;
-        std::vector<LockstepGroup> o;
-        o.insert(o.end(), ls->groups.begin() + alone, ls->groups.begin() + alone + second);
-        o.insert(o.end(), ls->groups.begin(), ls->groups.begin() + alone);
-        o.insert(o.end(), ls->groups.begin() + alone + second, ls->groups.end());
-        ls->groups.swap(o);
-    }
 }
 
 // Creation, second half: the batch's device state.  (What a failure leaves behind goes with the batch: its members own it.)
@@ -259,7 +198,7 @@ extern "C" rsmp_fir_lockstep* rsmp_fir_lockstep_new(rsmp_fir* const* rs, size_t 
     for (size_t i = 0; i < n; ++i) ls->max_taps = std::max<size_t>(ls->max_taps, rs[i]->taps);
     rsmp::init_drift(ls.get());
     if (!build_classes_and_groups(ls.get())) return nullptr;
-    order_workgroups(ls.get());
+    rsmp::lockstep_order_groups(ls->groups, rsmp::device_cus(ls->device));
     if (!init_device_state(ls.get())) return nullptr;
     return ls.release();
 }

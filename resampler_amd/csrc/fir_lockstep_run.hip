@@ -719,7 +719,6 @@ __global__ __launch_bounds__(64 * kLsPlanPack) void fir_lockstep_chain_kernel(Ls
 // whose period is the planner's own latency, give every chunk of a round of kLsWrapWaves chunks a wave of its own and
 // settle the stream's drift -- that of the LAST call with an output at an integer position -- through LDS: 32 -> ~10 us
 // per run at 128 streams x 256 calls.)
-constexpr uint32_t kLsWrapWaves = 16;   // (at most: a run of 256 calls has four chunks, a bulk launch of 4096 calls sixty-four)
 template <bool RAGGED>
 __global__ __launch_bounds__(64 * kLsWrapWaves) void fir_lockstep_wraps_kernel(LsRunArgs a) {
     __shared__ double s_drift[kLsWrapWaves];
@@ -972,50 +971,34 @@ hipError_t launch_fir_lockstep_ragged_gather(const uint32_t* totals, const LsRun
     return hipGetLastError();
 }
 
-uint32_t lockstep_plan_pack(size_t n_streams) {
-    static const uint32_t knob = [] { const char* e = rsmp::knob("RSMP_LS_PACK"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 ? static_cast<uint32_t>(v) : 0u; }();
-    if (n_streams >= kLsPlanPackBelow) return 1u;
-    return knob ? knob : kLsPlanPack;
-}
-
-uint32_t lockstep_replay_cus(size_t n_streams, uint32_t k) {
-    if (lockstep_plan_pack(n_streams) <= 1) return 0;
-    const uint32_t chunks = (k + 63) / 64, waves = std::min<uint32_t>(kLsWrapWaves, chunks);
-    return static_cast<uint32_t>((n_streams * waves + 15) / 16);
-}
-
 hipError_t launch_fir_lockstep_plan(const LsRunArgs& args_in, hipStream_t stream, int parts, const LsCommitArgs* commit, hipEvent_t k1_done) {
     if (args_in.n_streams == 0 || args_in.k == 0) return hipSuccess;
-    static const bool pchain = [] { const char* e = rsmp::knob("RSMP_LS_PCHAIN"); return !e || atoi(e) != 0; }();
+    const LsPlanShape shape = lockstep_plan_shape(args_in.n_streams, args_in.k);
+    const bool pchain = shape.parallel_chain != 0;
     LsRunArgs args = args_in;
-    args.parallel_chain = pchain ? 1u : 0u;
+    args.parallel_chain = shape.parallel_chain;
     // (a ragged run is never planned ahead: no commit to fuse, no event for K1 to complete)
     const bool ragged = args.totals != nullptr;
     if (ragged && (commit || k1_done || parts != 3)) return hipErrorInvalidValue;
-    const uint32_t blocks_per_stream = (args.k + 255) / 256;
     if (parts & 1) {
+        const dim3 grid(shape.k1_grid);
         LsCommitArgs cm{};
         if (commit) cm = *commit;
         if (k1_done)
-            hipExtLaunchKernelGGL(fir_lockstep_predict_kernel<false>, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, nullptr, k1_done, 0, args,
-                                  blocks_per_stream, cm);
+            hipExtLaunchKernelGGL(fir_lockstep_predict_kernel<false>, grid, dim3(256), 0, stream, nullptr, k1_done, 0, args, shape.k1_blocks_per_stream, cm);
         else if (ragged)
-            hipLaunchKernelGGL(fir_lockstep_predict_kernel<true>, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, args, blocks_per_stream, cm);
+            hipLaunchKernelGGL(fir_lockstep_predict_kernel<true>, grid, dim3(256), 0, stream, args, shape.k1_blocks_per_stream, cm);
         else
-            hipLaunchKernelGGL(fir_lockstep_predict_kernel<false>, dim3(blocks_per_stream * args.n_streams), dim3(256), 0, stream, args, blocks_per_stream, cm);
+            hipLaunchKernelGGL(fir_lockstep_predict_kernel<false>, grid, dim3(256), 0, stream, args, shape.k1_blocks_per_stream, cm);
     }
     if (parts & 2) {
-        const uint32_t pack = lockstep_plan_pack(args.n_streams);
-        const dim3 chain_grid((args.n_streams + pack - 1) / pack), chain_block(64 * pack);
+        const dim3 chain_grid(shape.k2_grid), chain_block(shape.k2_block);
         if (ragged && pchain) hipLaunchKernelGGL((fir_lockstep_chain_kernel<true, true>), chain_grid, chain_block, 0, stream, args);
         else if (ragged) hipLaunchKernelGGL((fir_lockstep_chain_kernel<false, true>), chain_grid, chain_block, 0, stream, args);
         else if (pchain) hipLaunchKernelGGL((fir_lockstep_chain_kernel<true, false>), chain_grid, chain_block, 0, stream, args);
         else hipLaunchKernelGGL((fir_lockstep_chain_kernel<false, false>), chain_grid, chain_block, 0, stream, args);
-        // (the replay: a wave per chunk of 64 calls for small batches, one wave per stream otherwise)
-        const uint32_t chunks = (args.k + 63) / 64;
-        const uint32_t wwaves = pack > 1 ? std::min<uint32_t>(kLsWrapWaves, chunks) : 1u;
-        if (ragged) hipLaunchKernelGGL(fir_lockstep_wraps_kernel<true>, dim3(args.n_streams), dim3(64 * wwaves), 0, stream, args);
-        else hipLaunchKernelGGL(fir_lockstep_wraps_kernel<false>, dim3(args.n_streams), dim3(64 * wwaves), 0, stream, args);
+        if (ragged) hipLaunchKernelGGL(fir_lockstep_wraps_kernel<true>, dim3(args.n_streams), dim3(64 * shape.k3_waves), 0, stream, args);
+        else hipLaunchKernelGGL(fir_lockstep_wraps_kernel<false>, dim3(args.n_streams), dim3(64 * shape.k3_waves), 0, stream, args);
     }
     return hipGetLastError();
 }

@@ -100,12 +100,13 @@ RunPolicy run_policy(size_t n, uint32_t k, bool repeats, bool legacy_stream) {
     p.fuse_commit = kn.fuse_commit && big;
     p.early_wait = kn.early_wait && big;
     p.lazy_done = kn.lazy_done && big;
-    // (the planner's packed workgroups take lockstep_plan_cus(n) CUs -- 32 for 128 streams --, + 4 for its one-wave kernels; the
+    // (the planner's packed workgroups take lockstep_plan_shape(n, k).chain_cus CUs -- 32 for 128 streams --, + 4 for its one-wave kernels; the
     // replay behind the chain a wave per chunk: a bulk launch of 64 streams x 4096 calls has 1024 of them, 64 CUs' worth, and with
     // 20 CUs left to it every fourth launch took 0.78 instead of 0.56 ms -- profiles/r06/bulk_distinct_reserve.txt)
-    if (repeats && !big)
-        p.reserve_cus = kn.reserve >= 0 ? static_cast<uint32_t>(kn.reserve)
-                                        : std::min<uint32_t>(64u, std::max(rsmp::lockstep_plan_cus(n), rsmp::lockstep_replay_cus(n, k)) + 4u);
+    if (repeats && !big) {
+        const rsmp::LsPlanShape shape = rsmp::lockstep_plan_shape(n, k);
+        p.reserve_cus = kn.reserve >= 0 ? static_cast<uint32_t>(kn.reserve) : std::min<uint32_t>(64u, std::max(shape.chain_cus, shape.replay_cus) + 4u);
+    }
     p.items_ahead = kn.items_ahead;
     p.launch_completes_events = kn.stop_event && !legacy_stream;
     return p;

@@ -140,6 +140,28 @@ def test_c4_shape_1024_streams_six_pairs_16_steps():
         assert rms(g_out[:pg], r_out[:pr]) <= RMS_TOL
 
 
+def test_workgroups_of_a_small_c4_batch_as_recorded_before_the_rules_moved():
+    """Seven fresh streams for each of config 4's six pairs, 512 frames per step: as many workgroups as the geometry rows
+    recorded from the commit before the host rules left the kernel files predict (tests/golden/fir_lockstep.json: streams per
+    workgroup 3 / 3 / 3 / 5 / 1 / 4, so 3 + 3 + 3 + 2 + 7 + 2 = 20), every one of them split; set to exact f32 products, what the
+    rows without allow_split predict and none split; two steps of each within the tolerance."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fir_lockstep.json")) as fh:
+        rows = json.load(fh)["rows"]
+    slots = {k: [int(r.split(" | ")[1].split()[14]) for r in v] for k, v in rows.items()}   # (LockstepGeometry::slots, in pair order)
+    want = {k: sum(-(-7 // s) for s in v) for k, v in slots.items()}
+    assert slots["allow_split=1"] == [3, 3, 3, 5, 1, 4] and want["allow_split=1"] == 20
+    specs = sharding.mixed_rate_batch(42, 2, 512)
+    worst, ls, _, _ = run_lockstep(specs, steps=2, frames=512, seed=77)
+    assert (ls.workgroups(), ls.split_workgroups()) == (20, 20)
+    assert worst <= RMS_TOL, worst
+    ls.close()
+    worst, ls, _, _ = run_lockstep(specs, steps=2, frames=512, seed=78, exact=lambda i: True)
+    assert (ls.workgroups(), ls.split_workgroups()) == (want["allow_split=0"], 0)
+    assert worst <= RMS_TOL, worst
+    ls.close()
+
+
 @pytest.mark.parametrize("which", ["all-exact", "mixed"])
 def test_exact_f32_products_on_request_and_mixed_batches(which):
     # two-channel streams run on the fp16 matrix cores with split operands by default; a stream set to

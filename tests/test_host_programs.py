@@ -139,11 +139,12 @@ def test_class_table_images_as_before_the_move(tmp_path, geometry_golden):
     """fir_class_table.cpp (plain C++ with _Float16: ROCm's clang++ as a host compiler, -ffp-contract=off like the library, ASan +
     UBSan) on the real polyphase table of filter_design.cpp: coef, wrap_coef and meta of the headline geometry in two and in
     three planes, config 4's six pairs, an exact-f32 matrix-core geometry, a vector geometry with the wrap variant in the
-    table and one without, each at drift 0, +2e-9 and -2e-9 -- bit for bit what the commit before the move built."""
+    table and one without, and the lock-step step kernel's table of 44.1 -> 48 kHz in its split and in its exact layout, each at
+    drift 0, +2e-9 and -2e-9 -- bit for bit what the commit before the move built."""
     assert os.path.exists(CLANGXX), "ROCm's clang++ is needed to build tests/host/fir_class_table_dump.cpp"
     exe = str(tmp_path / "fir_class_table_dump")
     srcs = [os.path.join(ROOT, "tests", "host", "fir_class_table_dump.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in ("fir_class_table.cpp", "fir_geometry.cpp", "filter_design.cpp", "common.cpp")]
+    srcs += [os.path.join(CSRC, f) for f in ("fir_class_table.cpp", "fir_geometry.cpp", "fir_lockstep_geometry.cpp", "filter_design.cpp", "common.cpp")]
     subprocess.run([CLANGXX] + SANITIZE + srcs + ["-o", exe], check=True)
     for setting, args, n_images in (("default", [], 9), ("planes3", ["headline"], 1)):
         run = subprocess.run([exe] + args, env=_setting_env(setting), capture_output=True, timeout=300)
@@ -156,6 +157,15 @@ def test_class_table_images_as_before_the_move(tmp_path, geometry_golden):
     assert any(k.startswith("f32_matrix:mfma2:") for k in geometry_golden["class_tables"]["default"])
     assert any(k.startswith("vector_inline_wraps:mfma0:planes0:wraps1") for k in geometry_golden["class_tables"]["default"])
     assert any(k.startswith("vector_fixup_wraps:mfma0:planes0:wraps0") for k in geometry_golden["class_tables"]["default"])
+    # the step kernel's tables (lockstep_class_geometry): the split layout and the exact one, the only A-operand order with mfma = 1 --
+    # what the commit before the lock-step rules moved built (tests/golden/make_fir_lockstep_fixture.py)
+    with open(os.path.join(ROOT, "tests", "golden", "fir_lockstep.json")) as fh:
+        want = json.load(fh)["class_tables"]
+    run = subprocess.run([exe, "lockstep"], env=_setting_env("default"), capture_output=True, timeout=300)
+    _clean(run)
+    got = _table_digests(run.stdout)
+    assert len(got) == 2 * 3 * 3 and got == want
+    assert any(k.startswith("lockstep_split:mfma3:planes2:") for k in want) and any(k.startswith("lockstep_exact:mfma1:planes0:") for k in want)
 
 
 def test_deal_of_workgroups(tmp_path):
@@ -174,9 +184,9 @@ def test_deal_of_workgroups(tmp_path):
 
 
 # ---- the FFT launch rules that left the kernel files ----------------------------------------------------------------------
-def _load_fixture_maker():
+def _load_fixture_maker(name="make_fft_launch_fixture"):
     import importlib.util
-    spec = importlib.util.spec_from_file_location("make_fft_launch_fixture", os.path.join(ROOT, "tests", "golden", "make_fft_launch_fixture.py"))
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
@@ -237,3 +247,69 @@ def test_fft_launch_rules_as_before_the_move(tmp_path):
     assert wave_builds == {"chm=0", "chm=1", "chm=2", "occ=1", "occ=2", "occ=3"}
     text = json.dumps(fx["launches"])
     assert "notsupported" in text and "ok " in text
+
+
+# ---- the lock-step batch's host rules that left the kernel files ----------------------------------------------------------
+def test_lockstep_rules_as_before_the_move(tmp_path):
+    """fir_lockstep_geometry.cpp and fir_lockstep_plan.h (plain C++, g++ with ASan + UBSan, no HIP anywhere below them, a process
+    of its own per setting of the debug switches) against tests/golden/fir_lockstep.json, recorded from the commit before the
+    move (tests/golden/make_fir_lockstep_fixture.py):
+    geometry -- every field of LockstepGeometry and of its PeriodicGeometry view for the 90 ordered pairs of the ten sample
+    rates, 16 / 32 / 64 / 128 taps, 1 / 2 / 3 / 4 / 6 / 8 / 16 / 17 channels, steps of 1 / 64 / 512 / 1024 / 4096 frames, allow_split 0 / 1
+    (28 800 rows: per (taps, channels, allow_split) the count and SHA-256) and three inputs without a usable rational form (in
+    full), under the default setting and under RSMP_LS_EXACT=1; config 4's six pairs in full; every outcome of the decision
+    tree occurs, as often as it did;
+    layout -- every offset of ls_layout, the two peak offsets and the plan records' stride for those six;
+    groups -- config 4's batch of 1024 and of 128 streams cut into workgroups, and their order on 256, 64 and 32 CUs (1024
+    streams on 256 CUs: between one and two workgroups per CU, the slowest-alone rotation; 128 streams: not);
+    shape -- K1 / K2 / K3 grids and blocks, the parallel-chain flag and the CUs of chain and replay for 1 .. 1024 streams x 1 ..
+    4096 calls, by default and under RSMP_LS_PACK=1 / 2 and RSMP_LS_PCHAIN=0."""
+    maker = _load_fixture_maker("make_fir_lockstep_fixture")
+    with open(os.path.join(ROOT, "tests", "golden", "fir_lockstep.json")) as fh:
+        fx = json.load(fh)
+    assert fx["settings"] == {"geometry": maker.GEOMETRY_SETTINGS, "shape": maker.SHAPE_SETTINGS}
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fir_lockstep_dump.cpp"
+    exe = str(tmp_path / "fir_lockstep_dump")
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_lockstep_dump.cpp"), os.path.join(CSRC, "fir_lockstep_geometry.cpp"),
+                                       "-o", exe], check=True)
+
+    def rows_of(what, switches):
+        run = subprocess.run([exe, what], env=maker.setting_env(switches), capture_output=True, text=True, timeout=300)
+        _clean(run)
+        return run.stdout
+
+    for setting, switches in maker.GEOMETRY_SETTINGS.items():
+        groups, odd, c4, walk = maker.digest_geometry(rows_of("geometry", switches))
+        assert sorted(groups) == sorted(fx["geometry"][setting]) and len(groups) == 4 * 8 * 2
+        for key, got in groups.items():
+            assert got[0] == 90 * 5 and got == fx["geometry"][setting][key], (setting, key)
+        assert odd == fx["odd"][setting] and len(odd) == 3 * 2 * 2
+        if setting == "default":
+            assert c4 == fx["rows"] and [len(v) for v in c4.values()] == [6, 6]
+            # (a fixture cannot pass while a path is empty: the counts of the walk on the commit before the move)
+            outcomes = {}
+            for row in walk:
+                outcomes[maker.outcome(row)] = outcomes.get(maker.outcome(row), 0) + 1
+            assert outcomes == fx["outcomes"] == {
+                "split, 160-byte rows (slots > 1)": 780, "split, 160-byte rows (slots = 1)": 175,
+                "split, packed 128-byte rows (slots > 1)": 111, "split, packed 128-byte rows (slots = 1)": 29,
+                "split given up for exact f32 (slots > 1)": 148, "split given up for exact f32 (slots = 1)": 397,
+                "exact f32 (slots > 1)": 11668, "exact f32 (slots = 1)": 11156,
+                "reference form (slots > 1)": 1928, "reference form (slots = 1)": 968, "does not fit": 1440}
+            got = [[maker.geometry_of(r)[k] for k in ("slots", "row_bytes", "n_tiles", "lds_bytes")] for r in c4["allow_split=1"]]
+            assert got == [[3, 160, 10, 53808], [3, 160, 10, 57600], [3, 160, 20, 55136], [5, 128, 10, 73584], [1, 160, 6, 39056], [4, 160, 6, 63344]]
+            assert not any(maker.geometry_of(r)["split"] for r in c4["allow_split=0"])
+        else:   # RSMP_LS_EXACT=1: no split layout anywhere
+            assert not any(maker.geometry_of(r)["split"] for r in walk)
+    assert rows_of("layout", {}).splitlines() == fx["layout"] and len(fx["layout"]) == 6
+    got = rows_of("groups", {}).splitlines()
+    assert got == fx["groups"]
+    n_groups = {int(r.split()[1]): int(r.split(" | ")[1].split()[0]) for r in got if r.startswith("cut ")}
+    assert 256 < n_groups[1024] < 512 and n_groups[128] <= 256, n_groups
+    order = {tuple(r.split(" | ")[0].split()[1:]): r.split(" | ")[1].split() for r in got if r.startswith("order ")}
+    assert len(order) == 6 and all(len(v) == len(set(v)) == n_groups[int(k[0])] for k, v in order.items())
+    assert order[("1024", "256")] != order[("1024", "64")] and order[("128", "256")] == order[("128", "64")]   # (the rotation, and none)
+    for setting, switches in maker.SHAPE_SETTINGS.items():
+        assert rows_of("shape", switches).splitlines() == fx["shape"][setting] and len(fx["shape"][setting]) == 11 * 8, setting
+    assert len({tuple(fx["shape"][s]) for s in fx["shape"]}) == 4   # (every switch changes rows)
