@@ -101,6 +101,14 @@ extern "C" {
     fn rsmp_f32_to_pcm(input: *const f32, n_values: usize, bits: c_int, out_pcm: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_f32_to_pcm_device(d_in: *const f32, n_values: usize, bits: c_int, d_pcm: *mut std::os::raw::c_void,
                               stream: *mut std::os::raw::c_void) -> c_int;
+    // addition: the same with dither (RSMP_DITHER_*): value j takes the noise of (seed, first_index + j) before the rounding
+    fn rsmp_f32_to_pcm_dither(input: *const f32, n_values: usize, bits: c_int, dither: c_int, seed: u64, first_index: u64,
+                              out_pcm: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_f32_to_pcm_dither_device(d_in: *const f32, n_values: usize, bits: c_int, dither: c_int, seed: u64, first_index: u64,
+                                     d_pcm: *mut std::os::raw::c_void, stream: *mut std::os::raw::c_void) -> c_int;
+    // addition: the dither of a handle's PCM output (rsmp_fir_batch_resample_bulk_pcm_out_device)
+    fn rsmp_fir_set_pcm_dither(r: *mut rsmp_fir, dither: c_int, seed: u64) -> c_int;
+    fn rsmp_fir_pcm_dither(r: *const rsmp_fir, dither: *mut c_int, seed: *mut u64) -> c_int;
     // addition: WAV samples (resample/src/main.rs:128-137) converted inside the FFT kernel's first load
     fn rsmp_fft_batch_resample_bulk_pcm_device(rs: *const *mut rsmp_fft, n: usize, d_pcm: *const *const std::os::raw::c_void, bits: c_int,
                                                d_out: *const *mut f32, n_chunks: *const usize, stream: *mut std::os::raw::c_void) -> c_int;
@@ -218,10 +226,29 @@ impl ResamplerFir {
                                                            out_bits as c_int, &out_cap, &mut consumed, &mut produced, std::ptr::null_mut()))
             .map(|_| (consumed, produced))
     }
+
+    /// Addition to the reference API: the dither of the PCM that `resample_bulk_pcm_out_device` writes for this stream -- none (the
+    /// default) or TPDF with the stream's seed.  A setting: `reset` leaves it.  Value (output frame n since new / reset, channel c)
+    /// takes the noise of index n * channels + c: the bytes are `f32_to_pcm_dither_device`'s of the f32 output, `first_index` = the
+    /// frames produced before the call * channels, however the stream is cut into calls.
+    pub fn set_pcm_dither(&mut self, dither: Dither, seed: u64) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fir_set_pcm_dither(self.handle, dither as c_int, seed) })
+    }
+    /// (dither mode as RSMP_DITHER_*, seed) as `set_pcm_dither` left them.
+    pub fn pcm_dither(&self) -> (i32, u64) {
+        let (mut d, mut s): (c_int, u64) = (0, 0);
+        unsafe { rsmp_fir_pcm_dither(self.handle, &mut d, &mut s) };
+        (d as i32, s)
+    }
 }
 
+/// Dither of PCM output (RSMP_DITHER_*): none, or triangular noise of +-1 LSB added before the rounding.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(C)]
+pub enum Dither { None = 0, Tpdf = 1 }
+
 /// Addition to the reference API: f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host; the library's quantiser --
-/// round half to even of x * 2^(bits-1), saturated to the code range, NaN -> 0, no dither.
+/// round half to even of x * 2^(bits-1), saturated to the code range, NaN -> 0; without dither (`f32_to_pcm_dither` adds it).
 pub fn f32_to_pcm(input: &[f32], bits: u32) -> Result<Vec<u8>, ResampleError> {
     let mut out = vec![0u8; input.len() * (bits as usize / 8)];
     status(unsafe { rsmp_f32_to_pcm(input.as_ptr(), input.len(), bits as c_int, out.as_mut_ptr() as *mut std::os::raw::c_void) }).map(|_| out)
@@ -230,6 +257,22 @@ pub fn f32_to_pcm(input: &[f32], bits: u32) -> Result<Vec<u8>, ResampleError> {
 /// The same on device memory (`d_in` 16-byte aligned, `d_pcm` 4-byte aligned, asynchronous on the default stream).
 pub unsafe fn f32_to_pcm_device(d_in: *const f32, n_values: usize, bits: u32, d_pcm: *mut std::os::raw::c_void) -> Result<(), ResampleError> {
     status(rsmp_f32_to_pcm_device(d_in, n_values, bits as c_int, d_pcm, std::ptr::null_mut()))
+}
+
+/// `f32_to_pcm` with dither: value j of `input` has the index `first_index` + j (wrapping) and is quantised as
+/// saturate(round_half_to_even(f32(x * 2^(bits-1)) + d(seed, index))), NaN -> 0, d the counter-based triangular noise stated at
+/// rsmp_f32_to_pcm_dither (include/resampler_amd.h).  `Dither::None`: the bytes of `f32_to_pcm`.
+pub fn f32_to_pcm_dither(input: &[f32], bits: u32, dither: Dither, seed: u64, first_index: u64) -> Result<Vec<u8>, ResampleError> {
+    let mut out = vec![0u8; input.len() * (bits as usize / 8)];
+    status(unsafe {
+        rsmp_f32_to_pcm_dither(input.as_ptr(), input.len(), bits as c_int, dither as c_int, seed, first_index, out.as_mut_ptr() as *mut std::os::raw::c_void)
+    }).map(|_| out)
+}
+
+/// The same on device memory (`d_in` 16-byte aligned, `d_pcm` 4-byte aligned, asynchronous on the default stream).
+pub unsafe fn f32_to_pcm_dither_device(d_in: *const f32, n_values: usize, bits: u32, dither: Dither, seed: u64, first_index: u64,
+                                       d_pcm: *mut std::os::raw::c_void) -> Result<(), ResampleError> {
+    status(rsmp_f32_to_pcm_dither_device(d_in, n_values, bits as c_int, dither as c_int, seed, first_index, d_pcm, std::ptr::null_mut()))
 }
 
 /// impl fmt::Debug for ResamplerFir (src/resampler_fir.rs:203-211): channels, taps, phases, `..`

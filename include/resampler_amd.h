@@ -88,6 +88,9 @@ enum { RSMP_ATTENUATION_DB60 = 0, RSMP_ATTENUATION_DB90, RSMP_ATTENUATION_DB120 
  * replays the exact f64 positions, does not).  Clean audio never takes the repair path. */
 enum { RSMP_FIR_KERNEL_AUTO = 0, RSMP_FIR_KERNEL_GENERIC = 1, RSMP_FIR_KERNEL_PERIODIC = 2,
        RSMP_FIR_KERNEL_PERIODIC_VECTOR = 3, RSMP_FIR_KERNEL_PERIODIC_F32 = 4 };
+/* Dither of PCM output (no counterpart in the reference, which writes f32): none, or triangular noise of +-1 LSB added before
+ * rounding -- the rule is stated at rsmp_f32_to_pcm_dither. */
+enum { RSMP_DITHER_NONE = 0, RSMP_DITHER_TPDF = 1 };
 
 const char* rsmp_last_error(void);          /* thread-local message of the last failing call */
 int rsmp_device_count(void);                /* number of HIP devices, 0 when there is none   */
@@ -204,10 +207,24 @@ int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size_t n, const
  * entry on the same input.  No byte outside [d_out_pcm[i], d_out_pcm[i] + out_caps[i] * out_bits / 8) is written; a capacity
  * too small is RSMP_ERR_CAPACITY before anything is launched.  Planned on the host.  Two-channel streams; long launches need
  * the 128-tap rate pairs of the split kernel as PCM input does, at most one launch's worth of input per stream; anything else is
- * RSMP_ERR_INVALID_ARGUMENT before any launch -- take f32 output and convert with rsmp_f32_to_pcm_device. */
+ * RSMP_ERR_INVALID_ARGUMENT before any launch -- take f32 output and convert with rsmp_f32_to_pcm_device.
+ * Dither is a setting of the handles (rsmp_fir_set_pcm_dither below, default RSMP_DITHER_NONE). */
 int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                 const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
                                                 const size_t* out_caps, size_t* consumed, size_t* produced, void* stream);
+/* Dither of the PCM the entry above writes for this handle: RSMP_DITHER_NONE (the default) or RSMP_DITHER_TPDF with the stream's
+ * `seed`; anything else is RSMP_ERR_INVALID_ARGUMENT and changes nothing.  A setting, not state: it survives rsmp_fir_reset and
+ * rsmp_fir_seek.  With TPDF every sum is quantised where it is stored by rsmp_f32_to_pcm_dither's rule (below), output frame n of
+ * a launch and channel c with the index
+ *   i = (abs_out + n) * channels + c,
+ * abs_out = the output frames the handle has produced since it was made or last reset -- after rsmp_fir_seek, the plan's.  So
+ * the bytes are exactly rsmp_f32_to_pcm_dither_device's of the f32 entry's output with first_index = abs_out * channels: a
+ * stream's bytes do not depend on how its input is cut into launches (beyond what the f32 sums themselves do), reset starts the
+ * noise sequence again, and the repair pass, which rewrites chunks with non-finite sums, gives them the noise they had.  One mode
+ * for all the streams of a batch, as out_bits -- a mix is RSMP_ERR_INVALID_ARGUMENT before any launch, nothing written, no state
+ * changed --; the seeds are per stream.  rsmp_fir_pcm_dither reads the setting back (either pointer may be NULL). */
+int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed);
+int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* seed);
 
 /* reset() for every stream of a batch. */
 void rsmp_fir_batch_reset(rsmp_fir* const* rs, size_t n);
@@ -413,7 +430,8 @@ int rsmp_pcm_to_stereo_f32_device(const void* d_pcm, int bits, int channels, siz
 /* The way back, f32 -> little-endian integer PCM of `bits` (16, packed 24, 32), n_values * bits / 8 bytes:
  *   q = saturate(round_half_to_even(x * 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1),  NaN -> 0.
  * The product is exact (a power of two); +inf and everything above the range give the top code, -inf and everything below the
- * bottom one, -0.0 and denormals 0; +1.0 saturates to the top code.  No dither, no noise shaping.  Decoding with
+ * bottom one, -0.0 and denormals 0; +1.0 saturates to the top code.  No dither here (rsmp_f32_to_pcm_dither below), no noise
+ * shaping.  Decoding with
  * rsmp_pcm_to_stereo_f32_device and quantising again at the same width is the identity on every 16-bit and 24-bit code.  At 32
  * bits it is NOT: the reference decodes 32-bit files with the divisor -2^31 (resample/src/main.rs:131), the scale here is
  * +2^31 -- an f32 value means what it says --, so that round trip gives saturate(-f32(s)): polarity inverted, the bottom code
@@ -422,6 +440,22 @@ int rsmp_pcm_to_stereo_f32_device(const void* d_pcm, int bits, int channels, siz
  * asynchronous on `stream`; d_in 16-byte aligned, d_pcm 4-byte aligned, any n_values; writes exactly n_values * bits / 8 bytes. */
 int rsmp_f32_to_pcm(const float* in, size_t n_values, int bits, void* out_pcm);
 int rsmp_f32_to_pcm_device(const float* d_in, size_t n_values, int bits, void* d_pcm, void* stream);
+/* The same with dither.  RSMP_DITHER_NONE: the bytes of rsmp_f32_to_pcm.  RSMP_DITHER_TPDF: value j of the call has the absolute
+ * index i = first_index + j (wrapping, 64 bits) and is quantised as
+ *   q = saturate(round_half_to_even(f32(x * 2^(bits-1)) + d(seed, i))),  NaN -> 0:
+ * ONE f32 addition behind the exact product (an fma of the same operands gives the same bits); saturation, infinities and NaN
+ * as above.  The noise has no state -- it is a function of the seed and the index (arithmetic mod 2^64, splitmix64):
+ *   z = seed + ((i >> 1) + 1) * 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) * 0x94D049BB133111EB;          w = z ^ z >> 31;
+ *   h = low 32 bits of w for even i, high 32 bits for odd i;  r1 = h & 0xFFFF, r2 = h >> 16;  d = f32(r1 - r2) * 2^-16
+ * -- the difference of two uniform 16-bit numbers: triangular on (-1, 1) LSB, variance 1/6, the usual TPDF dither; the error
+ * of the result has mean zero and a variance that does not depend on the signal.  One mix serves two consecutive values, one
+ * two-channel frame.  Converting a buffer in pieces, each with first_index advanced by the values before it, gives the bytes of
+ * one call.  Unknown modes are RSMP_ERR_INVALID_ARGUMENT.  Host / device versions, pointers and alignment as above. */
+int rsmp_f32_to_pcm_dither(const float* in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
+                           void* out_pcm);
+int rsmp_f32_to_pcm_dither_device(const float* d_in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
+                                  void* d_pcm, void* stream);
 /* Measurement aid (no counterpart in the reference): a plain streaming copy of n_values floats, 16 bytes per lane --
  * the rate a kernel that reads as much as it writes can reach on this GPU; bench.py reports it next to every
  * roofline fraction.  16-byte aligned device pointers, n_values a multiple of 4, asynchronous on `stream`. */

@@ -83,7 +83,14 @@ class FirKernel(enum.IntEnum):
     PeriodicF32 = 4      # periodic kernels that keep every product in f32 (never the split-bf16 one)
 
 
+class Dither(enum.IntEnum):
+    """Dither of PCM output (RSMP_DITHER_*): none, or triangular noise of +-1 LSB added before rounding (rsmp_f32_to_pcm_dither)."""
+    NONE = 0
+    TPDF = 1
+
+
 RSMP_OK = 0
+_U64 = 0xFFFFFFFFFFFFFFFF
 _f32p = C.POINTER(C.c_float)
 _szp = C.POINTER(C.c_size_t)
 
@@ -113,6 +120,8 @@ _SIGNATURES = [
     ("rsmp_fir_state", None, [C.c_void_p, _szp, _szp, C.POINTER(C.c_double)]),
     ("rsmp_fir_set_kernel", C.c_int, [C.c_void_p, C.c_int]),
     ("rsmp_fir_set_profiling", C.c_int, [C.c_void_p, C.c_int]),
+    ("rsmp_fir_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    ("rsmp_fir_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     ("rsmp_fir_last_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rsmp_fir_mean_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float), _szp]),
     ("rsmp_fir_kernel_variant", C.c_int, [C.c_void_p]),
@@ -179,6 +188,8 @@ _SIGNATURES = [
     ("rsmp_pcm_to_stereo_f32_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("rsmp_f32_to_pcm", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     ("rsmp_f32_to_pcm_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    ("rsmp_f32_to_pcm_dither", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
+    ("rsmp_f32_to_pcm_dither_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rsmp_device_stream_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rsmp_fft_new", C.c_void_p, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     ("rsmp_fft_free", None, [C.c_void_p]),
@@ -379,6 +390,19 @@ class ResamplerFir:
     def set_profiling(self, enable: bool) -> None:
         _check(lib().rsmp_fir_set_profiling(self._h, 1 if enable else 0))
 
+    def set_pcm_dither(self, dither: int, seed: int = 0) -> None:
+        """Dither of the PCM that FirBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fir_set_pcm_dither): Dither.NONE
+        (the default) or Dither.TPDF with the stream's 64-bit seed.  A setting: reset() and seek() leave it.  Value (output frame n
+        since new / reset, channel c) takes the noise of index n * channels + c -- f32_to_pcm_device(..., dither, seed,
+        first_index = frames produced so far * channels) of the f32 output gives the same bytes."""
+        _check(lib().rsmp_fir_set_pcm_dither(self._h, int(dither), int(seed) & _U64))
+
+    def pcm_dither(self) -> Tuple[int, int]:
+        """(dither mode, seed) as set_pcm_dither left them."""
+        d, sd = C.c_int(), C.c_uint64()
+        _check(lib().rsmp_fir_pcm_dither(self._h, C.byref(d), C.byref(sd)))
+        return d.value, sd.value
+
     def last_kernel_ms(self) -> float:
         ms = C.c_float()
         _check(lib().rsmp_fir_last_kernel_ms(self._h, C.byref(ms)))
@@ -520,7 +544,7 @@ class FirBatch:
                                      stream: Optional[int] = None):
         """The bulk driver loop with the output as a WAV file stores it (rsmp_fir_batch_resample_bulk_pcm_out_device): d_out_pcms =
         uint8 tensors that receive little-endian PCM of `out_bits` (16 / 24 / 32), quantised where the kernels store their sums
-        (f32_to_pcm's rule).  d_ins = float32 tensors (in_bits = 0) or uint8 tensors of PCM of `in_bits`."""
+        (f32_to_pcm's rule; with the dither the streams were given by ResamplerFir.set_pcm_dither -- one mode for all of them).  d_ins = float32 tensors (in_bits = 0) or uint8 tensors of PCM of `in_bits`."""
         n = len(self.resamplers)
         pin, pout = (C.c_void_p * n)(), (C.c_void_p * n)()
         lens, caps = (C.c_size_t * n)(), (C.c_size_t * n)()
@@ -870,22 +894,31 @@ def pcm_to_stereo_f32_device(d_pcm, bits: int, channels: int, d_out, stream: Opt
                                                C.c_void_p(d_out.data_ptr()), C.c_void_p(stream or 0)))
 
 
-def f32_to_pcm(x, bits: int) -> bytes:
-    """f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host, no device needed (rsmp_f32_to_pcm): the library's
-    quantiser -- round half to even of x * 2^(bits-1), saturated, NaN -> 0."""
+def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0) -> bytes:
+    """f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host, no device needed (rsmp_f32_to_pcm[_dither]): the
+    library's quantiser -- round half to even of x * 2^(bits-1), saturated, NaN -> 0.  dither = Dither.TPDF: value j takes, before
+    the rounding, the triangular noise of (seed, first_index + j) -- the rule is stated at rsmp_f32_to_pcm_dither."""
     a = _np_f32(x).reshape(-1)
     out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8)
-    _check(lib().rsmp_f32_to_pcm(C.c_void_p(a.ctypes.data), a.size, bits, C.c_void_p(out.ctypes.data)))
+    if dither == 0:
+        _check(lib().rsmp_f32_to_pcm(C.c_void_p(a.ctypes.data), a.size, bits, C.c_void_p(out.ctypes.data)))
+    else:
+        _check(lib().rsmp_f32_to_pcm_dither(C.c_void_p(a.ctypes.data), a.size, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                            C.c_void_p(out.ctypes.data)))
     return out.tobytes()
 
 
-def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None) -> None:
-    """The same on HBM-resident torch tensors (rsmp_f32_to_pcm_device): d_in = float32, d_pcm = uint8 with room for
+def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None, dither: int = 0, seed: int = 0, first_index: int = 0) -> None:
+    """The same on HBM-resident torch tensors (rsmp_f32_to_pcm[_dither]_device): d_in = float32, d_pcm = uint8 with room for
     d_in.numel() * bits / 8 bytes, 4-byte aligned; exactly those bytes are written."""
     n = d_in.numel()
     if bits in (16, 24, 32):
         assert d_pcm.numel() >= n * (bits // 8)
-    _check(lib().rsmp_f32_to_pcm_device(C.c_void_p(_dev_ptr(d_in)), n, bits, C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
+    if dither == 0:
+        _check(lib().rsmp_f32_to_pcm_device(C.c_void_p(_dev_ptr(d_in)), n, bits, C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
+    else:
+        _check(lib().rsmp_f32_to_pcm_dither_device(C.c_void_p(_dev_ptr(d_in)), n, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                                   C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
 
 
 def fft_plan_sizes(input_rate_hz: int, output_rate_hz: int):

@@ -6,7 +6,7 @@
 //     (`s as f32 / (1 << (bits - 1)) as f32`) with mono duplicated to stereo, so a decoded file goes from
 //     its PCM bytes in HBM to the interleaved f32 frames the resamplers take in one pass;
 //   * the way back, f32 -> 16 / 24 / 32-bit little-endian PCM (fir_pcm_quantise, fir_kernels.h: round half to even, saturate,
-//     NaN -> 0, no dither), on the host and as a streaming pass on the device.
+//     NaN -> 0), without or with TPDF dither (fir_pcm_quantise_dither), on the host and as a streaming pass on the device.
 // Both are HBM-bound elementwise kernels: coalesced loads / stores, nothing to stage.
 #include <hip/hip_runtime.h>
 
@@ -112,6 +112,35 @@ __global__ __launch_bounds__(kThreads) void f32_to_pcm_kernel(const float* __res
     }
 }
 
+// The same lanes, loads and stores with TPDF dither: value k of the buffer has the index first + k (wrapping) and takes the noise
+// fir_pcm_dither(seed, first + k) -- each value by the definition itself, whatever the parity of `first`.
+template <int BITS>
+__global__ __launch_bounds__(kThreads) void f32_to_pcm_tpdf_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, uint64_t n, uint64_t seed,
+                                                                   uint64_t first) {
+    typedef float v4f_in __attribute__((ext_vector_type(4)));
+    const uint64_t n4 = n / 4, stride = static_cast<uint64_t>(gridDim.x) * kThreads;
+    auto code = [&](float x, uint64_t k) { return static_cast<uint32_t>(rsmp::fir_pcm_quantise_dither(x, BITS, rsmp::fir_pcm_dither(seed, first + k))); };
+    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(kThreads) + threadIdx.x; i <= n4; i += stride) {
+        if (i == n4) {   // the 0 .. 3 values behind the last whole four
+            for (uint64_t k = 4 * n4; k < n; ++k) rsmp::fir_pcm_store_code(out, BITS, k, static_cast<int32_t>(code(in[k], k)));
+            break;
+        }
+        const v4f_in x = reinterpret_cast<const v4f_in*>(in)[i];
+        const uint32_t q0 = code(x.x, 4 * i), q1 = code(x.y, 4 * i + 1), q2 = code(x.z, 4 * i + 2), q3 = code(x.w, 4 * i + 3);
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + i * (BITS / 2));
+        if constexpr (BITS == 16) {
+            o[0] = (q0 & 0xFFFFu) | (q1 << 16);
+            o[1] = (q2 & 0xFFFFu) | (q3 << 16);
+        } else if constexpr (BITS == 24) {
+            o[0] = (q0 & 0xFFFFFFu) | (q1 << 24);
+            o[1] = ((q1 >> 8) & 0xFFFFu) | (q2 << 16);
+            o[2] = ((q2 >> 16) & 0xFFu) | (q3 << 8);
+        } else {
+            o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
+        }
+    }
+}
+
 int check_device() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
@@ -187,6 +216,17 @@ extern "C" int rsmp_pcm_to_stereo_f32_device(const void* d_pcm, int bits, int ch
     return RSMP_OK;
 }
 
+// f32 -> PCM kernels' grid: a lane per four values and one for the rest
+static dim3 f32_to_pcm_grid(size_t n_values) {
+    int cus = 256;
+    int device = 0;
+    (void)hipGetDevice(&device);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    const uint64_t lanes = n_values / 4 + 1;
+    const uint64_t blocks = (lanes + kThreads - 1) / kThreads, most = static_cast<uint64_t>(cus) * 8u;   // (eight workgroups of 256 a CU walk the buffer side by side)
+    return dim3(static_cast<uint32_t>(blocks < most ? blocks : most));
+}
+
 // The definition itself, on the host (no device needed).
 extern "C" int rsmp_f32_to_pcm(const float* in, size_t n_values, int bits, void* out_pcm) {
     if ((bits != 16 && bits != 24 && bits != 32) || (n_values != 0 && (!in || !out_pcm)))
@@ -207,18 +247,47 @@ extern "C" int rsmp_f32_to_pcm_device(const float* d_in, size_t n_values, int bi
         return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_device: d_in 16-byte aligned, d_pcm 4-byte aligned");
     if (int rc = check_device()) return rc;
     if (n_values == 0) return RSMP_OK;
-    int cus = 256;
-    int device = 0;
-    (void)hipGetDevice(&device);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    const uint64_t lanes = n_values / 4 + 1;
-    const uint64_t blocks = (lanes + kThreads - 1) / kThreads, most = static_cast<uint64_t>(cus) * 8u;   // (eight workgroups of 256 a CU walk the buffer side by side)
-    const dim3 grid(static_cast<uint32_t>(blocks < most ? blocks : most));
+    const dim3 grid = f32_to_pcm_grid(n_values);
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* o = static_cast<uint8_t*>(d_pcm);
     if (bits == 16) hipLaunchKernelGGL(f32_to_pcm_kernel<16>, grid, dim3(kThreads), 0, s, d_in, o, static_cast<uint64_t>(n_values));
     else if (bits == 24) hipLaunchKernelGGL(f32_to_pcm_kernel<24>, grid, dim3(kThreads), 0, s, d_in, o, static_cast<uint64_t>(n_values));
     else hipLaunchKernelGGL(f32_to_pcm_kernel<32>, grid, dim3(kThreads), 0, s, d_in, o, static_cast<uint64_t>(n_values));
+    RSMP_HIP_CHECK(hipGetLastError());
+    return RSMP_OK;
+}
+
+// The definition with dither, on the host (no device needed).
+extern "C" int rsmp_f32_to_pcm_dither(const float* in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index, void* out_pcm) {
+    if ((bits != 16 && bits != 24 && bits != 32) || (dither != RSMP_DITHER_NONE && dither != RSMP_DITHER_TPDF) || (n_values != 0 && (!in || !out_pcm)))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_dither: 16 / 24 / 32 bits, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, non-null buffers");
+    if (dither == RSMP_DITHER_NONE) return rsmp_f32_to_pcm(in, n_values, bits, out_pcm);
+    uint8_t* o = static_cast<uint8_t*>(out_pcm);
+    const size_t bytes = static_cast<size_t>(bits) / 8;
+    for (size_t i = 0; i < n_values; ++i) {
+        const float d = rsmp::fir_pcm_dither(seed, first_index + i);
+        const uint32_t q = static_cast<uint32_t>(rsmp::fir_pcm_quantise_dither(in[i], static_cast<uint32_t>(bits), d));
+        for (size_t b = 0; b < bytes; ++b) o[i * bytes + b] = static_cast<uint8_t>(q >> (8 * b));   // little-endian
+    }
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_f32_to_pcm_dither_device(const float* d_in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
+                                             void* d_pcm, void* stream) {
+    if ((bits != 16 && bits != 24 && bits != 32) || (dither != RSMP_DITHER_NONE && dither != RSMP_DITHER_TPDF) || (n_values != 0 && (!d_in || !d_pcm)))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_dither_device: 16 / 24 / 32 bits, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, non-null buffers");
+    if (dither == RSMP_DITHER_NONE) return rsmp_f32_to_pcm_device(d_in, n_values, bits, d_pcm, stream);
+    if (reinterpret_cast<uintptr_t>(d_in) % 16 != 0 || reinterpret_cast<uintptr_t>(d_pcm) % 4 != 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_dither_device: d_in 16-byte aligned, d_pcm 4-byte aligned");
+    if (int rc = check_device()) return rc;
+    if (n_values == 0) return RSMP_OK;
+    const dim3 grid = f32_to_pcm_grid(n_values);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* o = static_cast<uint8_t*>(d_pcm);
+    const uint64_t n = n_values;
+    if (bits == 16) hipLaunchKernelGGL(f32_to_pcm_tpdf_kernel<16>, grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index);
+    else if (bits == 24) hipLaunchKernelGGL(f32_to_pcm_tpdf_kernel<24>, grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index);
+    else hipLaunchKernelGGL(f32_to_pcm_tpdf_kernel<32>, grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index);
     RSMP_HIP_CHECK(hipGetLastError());
     return RSMP_OK;
 }

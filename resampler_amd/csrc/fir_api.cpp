@@ -404,6 +404,22 @@ extern "C" int rsmp_fir_set_kernel(rsmp_fir* r, int kernel) {
     return RSMP_OK;
 }
 
+// PCM output's dither: a setting of the handle (reset and seek leave it), read when a PCM-output launch is made.
+extern "C" int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed) {
+    if (!r || (dither != RSMP_DITHER_NONE && dither != RSMP_DITHER_TPDF))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_set_pcm_dither: null handle or unknown dither mode %d", dither);
+    r->pcm_dither = dither;
+    r->pcm_dither_seed = seed;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* seed) {
+    if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_dither: null handle");
+    if (dither) *dither = r->pcm_dither;
+    if (seed) *seed = r->pcm_dither_seed;
+    return RSMP_OK;
+}
+
 extern "C" int rsmp_fir_set_profiling(rsmp_fir* r, int enable) {
     DeviceGuard guard(r->device);
     if (enable && !r->prof_start[0])
@@ -634,6 +650,9 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
 // per-frame stores, the generic kernels, the repair pass.  Input: interleaved f32 (in_bits = 0) or PCM as above.  Counts, end states
 // and buffered frames (f32) are those of rsmp_fir_batch_resample_bulk_device; the bytes are rsmp_f32_to_pcm_device's of that
 // entry's output, without the f32 ever reaching HBM (f32 written, f32 read, PCM written: two passes less).
+// Handles set to RSMP_DITHER_TPDF (rsmp_fir_set_pcm_dither; all of a batch or none: launch_jobs refuses a mix) add their noise at
+// the same sites, value (frame n of the launch, channel c) with index (abs_out + n) * channels + c -- rsmp_f32_to_pcm_dither_device's
+// bytes with the handle's seed and first_index = abs_out * channels.
 extern "C" int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                            const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
                                                            const size_t* out_caps, size_t* consumed, size_t* produced, void* stream) {

@@ -43,8 +43,9 @@ __device__ __forceinline__ float load_sample(const FirStreamDesc& d, int64_t v, 
 
 // fuse_tail: the first workgroup of every stream also copies the stream's still-buffered frames into hist_next
 // (the job of fir_tail_copy_kernel: a second launch is a fifth of a streaming call's latency).
-// OUT: the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes (fir_pcm_store).
-template <bool OUT>
+// OUT (FirOut): the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes (fir_pcm_store), with or
+// without TPDF dither (fir_out_store).
+template <int OUT>
 __device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
     const FirStreamDesc d = descs[blockIdx.y];
     const uint32_t tile = blockIdx.x;
@@ -130,10 +131,13 @@ __device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict
 }
 
 __global__ __launch_bounds__(kBlock) void fir_generic_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
-    fir_generic_body<false>(descs, fuse_tail);
+    fir_generic_body<kFirOutF32>(descs, fuse_tail);
 }
 __global__ __launch_bounds__(kBlock) void fir_generic_pcm_out_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
-    fir_generic_body<true>(descs, fuse_tail);
+    fir_generic_body<kFirOutPcm>(descs, fuse_tail);
+}
+__global__ __launch_bounds__(kBlock) void fir_generic_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
+    fir_generic_body<kFirOutPcmTpdf>(descs, fuse_tail);
 }
 
 __global__ __launch_bounds__(kBlock) void fir_tail_copy_kernel(const FirStreamDesc* __restrict__ descs) {
@@ -153,8 +157,9 @@ __global__ __launch_bounds__(kBlock) void fir_tail_copy_kernel(const FirStreamDe
 // stream's class table was built for -- the same phase rows and frac the periodic kernel pre-mixed -- and
 // outputs at an integer position take the previous frame and row 1023 where the wrap bitmap says so
 // (resampler_fir.rs:544, :562-565).
-// OUT: the marked chunks lie in a PCM buffer (FirStreamDesc::out_bits) and are rewritten as PCM.
-template <bool OUT>
+// OUT (FirOut): the marked chunks lie in a PCM buffer (FirStreamDesc::out_bits) and are rewritten as PCM -- dithered launches with
+// the noise the first pass gave them: it depends on the seed and the value's index alone.
+template <int OUT>
 __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict__ descs, uint32_t n_streams, const NfArgs& nf) {
     if (__hip_atomic_load(nf.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nf.tag) return;
     const int g = threadIdx.x & (kLanesPerFrame - 1);
@@ -226,11 +231,15 @@ __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict_
 }
 __global__ __launch_bounds__(kBlock) void fir_repair_kernel(const FirStreamDesc* __restrict__ descs,
                                                             uint32_t n_streams, NfArgs nf) {
-    fir_repair_body<false>(descs, n_streams, nf);
+    fir_repair_body<kFirOutF32>(descs, n_streams, nf);
 }
 __global__ __launch_bounds__(kBlock) void fir_repair_pcm_out_kernel(const FirStreamDesc* __restrict__ descs,
                                                                     uint32_t n_streams, NfArgs nf) {
-    fir_repair_body<true>(descs, n_streams, nf);
+    fir_repair_body<kFirOutPcm>(descs, n_streams, nf);
+}
+__global__ __launch_bounds__(kBlock) void fir_repair_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs,
+                                                                     uint32_t n_streams, NfArgs nf) {
+    fir_repair_body<kFirOutPcmTpdf>(descs, n_streams, nf);
 }
 struct RepairMulti {
     const FirStreamDesc* descs[kMaxRepairJobs];
@@ -241,7 +250,7 @@ struct RepairMulti {
     const FirStreamDesc* tail_descs;
     uint32_t n_tail, n_jobs;
 };
-template <bool OUT>
+template <int OUT>
 __device__ __forceinline__ void fir_repair_multi_body(const RepairMulti& m) {   // grid = (blocks, jobs [+ 1])
     if (blockIdx.y >= m.n_jobs) {   // the tail row: a workgroup per stream, round the row
         for (uint32_t s = blockIdx.x; s < m.n_tail; s += gridDim.x) {
@@ -258,16 +267,18 @@ __device__ __forceinline__ void fir_repair_multi_body(const RepairMulti& m) {   
     }
     fir_repair_body<OUT>(m.descs[blockIdx.y], m.n_streams[blockIdx.y], m.nf[blockIdx.y]);
 }
-__global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMulti m) { fir_repair_multi_body<false>(m); }
-__global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_out_kernel(const RepairMulti m) { fir_repair_multi_body<true>(m); }
+__global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMulti m) { fir_repair_multi_body<kFirOutF32>(m); }
+__global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_out_kernel(const RepairMulti m) { fir_repair_multi_body<kFirOutPcm>(m); }
+__global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_tpdf_kernel(const RepairMulti m) { fir_repair_multi_body<kFirOutPcmTpdf>(m); }
 
 }  // namespace
 
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done, bool* done_attached, uint32_t out_bits) {
+                             hipEvent_t done, bool* done_attached, uint32_t out_bits, uint32_t dither) {
     if (n_streams == 0 || !nf.words || nf.chunks == 0) return hipSuccess;
     const uint32_t total = n_streams * nf.chunks;
-    const auto kernel = out_bits != 0 ? fir_repair_pcm_out_kernel : fir_repair_kernel;
+    const FirOut mode = fir_out_mode(out_bits, dither);
+    const auto kernel = mode == kFirOutPcmTpdf ? fir_repair_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_repair_pcm_out_kernel : fir_repair_kernel;
     if (done && done_attached) {
         hipExtLaunchKernelGGL(kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, nullptr, done, 0,
                               d_descs, n_streams, nf);
@@ -279,9 +290,11 @@ hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, c
 }
 
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs,
-                                   uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached, uint32_t out_bits) {
+                                   uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached, uint32_t out_bits,
+                                   uint32_t dither) {
     if (done_attached) *done_attached = false;
-    const auto kernel = out_bits != 0 ? fir_repair_multi_pcm_out_kernel : fir_repair_multi_kernel;
+    const FirOut mode = fir_out_mode(out_bits, dither);
+    const auto kernel = mode == kFirOutPcmTpdf ? fir_repair_multi_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_repair_multi_pcm_out_kernel : fir_repair_multi_kernel;
     bool tail_left = tail_descs != nullptr && n_tail != 0 && max_tail_values != 0;
     for (size_t j = 0; j < n_jobs;) {
         RepairMulti m{};
@@ -317,11 +330,12 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
 }
 
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, uint32_t out_bits) {
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, uint32_t out_bits, uint32_t dither) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
     const uint32_t cz = (max_channels + kChannelsPerBlock - 1) / kChannelsPerBlock;
     const dim3 grid((max_out + kFirTile - 1) / kFirTile, n_streams, cz ? cz : 1);
-    hipLaunchKernelGGL(out_bits != 0 ? fir_generic_pcm_out_kernel : fir_generic_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u);
+    const FirOut mode = fir_out_mode(out_bits, dither);
+    hipLaunchKernelGGL(mode == kFirOutPcmTpdf ? fir_generic_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_generic_pcm_out_kernel : fir_generic_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u);
     return hipGetLastError();
 }
 

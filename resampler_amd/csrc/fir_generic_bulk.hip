@@ -94,8 +94,9 @@ struct BulkPass {
     bool live;
 };
 
-// OUT: the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes (fir_pcm_store).
-template <int CH, bool FULL, bool OUT>   // FULL: 128 taps (every lane's four chunks exist: no tests, every LDS offset an immediate)
+// OUT (FirOut): the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes, with or without TPDF
+// dither (fir_out_store).
+template <int CH, bool FULL, int OUT>   // FULL: 128 taps (every lane's four chunks exist: no tests, every LDS offset an immediate)
 __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkMeta* meta, const uint16_t* sorted, const float* win, uint32_t n0,
                                              uint32_t nt, uint32_t lane, uint32_t wave) {
     const uint32_t ch = CH ? static_cast<uint32_t>(CH) : d.channels, taps = d.taps;
@@ -108,13 +109,13 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
     const GRow coeffs = (GRow)d.coeffs;
     const GOut out = (GOut)d.out;
     auto store1 = [&](size_t i, float y) {
-        if constexpr (OUT) fir_pcm_store(d.out, d.out_bits, i, y);
+        if constexpr (OUT != kFirOutF32) fir_out_store<OUT>(d, i, y);
         else out[i] = y;
     };
     auto store2 = [&](size_t i, float y0, float y1) {   // (two channels: i even)
-        if constexpr (OUT) {
-            fir_pcm_store(d.out, d.out_bits, i, y0);
-            fir_pcm_store(d.out, d.out_bits, i + 1, y1);
+        if constexpr (OUT != kFirOutF32) {
+            fir_out_store<OUT>(d, i, y0);
+            fir_out_store<OUT>(d, i + 1, y1);
         } else {
             *(GOut2)(out + i) = v2f{y0, y1};
         }
@@ -221,7 +222,7 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
 
 // CH: 1 / 2 = every stream of the launch has that many channels; 0 = any counts (a kernel each: side by side in one kernel the three
 // bodies shared a register allocation and spilled)
-template <int CH, bool FULL, bool OUT>
+template <int CH, bool FULL, int OUT>
 __device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames, uint32_t window_cap_frames) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const FirStreamDesc d = descs[blockIdx.y];
@@ -332,13 +333,18 @@ __device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __res
 template <int CH, bool FULL>
 __global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
                                                                       uint32_t window_cap_frames) {
-    fir_generic_bulk_body<CH, FULL, false>(descs, tile_frames, window_cap_frames);
+    fir_generic_bulk_body<CH, FULL, kFirOutF32>(descs, tile_frames, window_cap_frames);
 }
 // PCM output: two-channel streams (the only ones the entry admits)
 template <bool FULL>
 __global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_pcm_out_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
                                                                               uint32_t window_cap_frames) {
-    fir_generic_bulk_body<2, FULL, true>(descs, tile_frames, window_cap_frames);
+    fir_generic_bulk_body<2, FULL, kFirOutPcm>(descs, tile_frames, window_cap_frames);
+}
+template <bool FULL>
+__global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
+                                                                               uint32_t window_cap_frames) {
+    fir_generic_bulk_body<2, FULL, kFirOutPcmTpdf>(descs, tile_frames, window_cap_frames);
 }
 
 }  // namespace
@@ -358,7 +364,7 @@ uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double 
 
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels, uint32_t uniform_taps,
-                                   uint32_t out_bits) {
+                                   uint32_t out_bits, uint32_t dither) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
     if (out_bits != 0 && uniform_channels != 2) return hipErrorNotSupported;
     const uint32_t tile = fir_generic_bulk_tile(max_channels, max_taps, max_ratio);
@@ -374,9 +380,12 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
         {reinterpret_cast<const void*>(fir_generic_bulk_kernel<2, false>), reinterpret_cast<const void*>(fir_generic_bulk_kernel<2, true>)}};
     static const void* const fns_pcm_out[2] = {reinterpret_cast<const void*>(fir_generic_bulk_pcm_out_kernel<false>),
                                                reinterpret_cast<const void*>(fir_generic_bulk_pcm_out_kernel<true>)};
-    const void* fn = out_bits != 0 ? fns_pcm_out[full ? 1 : 0] : fns[ci][full ? 1 : 0];
-    static bool granted[4][2] = {};   // (the attribute is per function and process: set once)
-    bool& have = granted[out_bits != 0 ? 3 : ci][full ? 1 : 0];
+    static const void* const fns_pcm_tpdf[2] = {reinterpret_cast<const void*>(fir_generic_bulk_pcm_tpdf_kernel<false>),
+                                                reinterpret_cast<const void*>(fir_generic_bulk_pcm_tpdf_kernel<true>)};
+    const FirOut mode = fir_out_mode(out_bits, dither);
+    const void* fn = mode == kFirOutPcmTpdf ? fns_pcm_tpdf[full ? 1 : 0] : mode == kFirOutPcm ? fns_pcm_out[full ? 1 : 0] : fns[ci][full ? 1 : 0];
+    static bool granted[5][2] = {};   // (the attribute is per function and process: set once)
+    bool& have = granted[mode == kFirOutPcmTpdf ? 4 : mode == kFirOutPcm ? 3 : ci][full ? 1 : 0];
     if (!have) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;

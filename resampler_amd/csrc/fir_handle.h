@@ -60,6 +60,10 @@ struct rsmp_fir {
     static constexpr int kProfRing = 64;
     rsmp::EventHolder prof_start[kProfRing], prof_stop[kProfRing];
     size_t prof_count = 0;
+    // PCM output (rsmp_fir_batch_resample_bulk_pcm_out_device): RSMP_DITHER_* and the stream's seed (rsmp_fir_set_pcm_dither).
+    // A setting, not state: reset and seek leave it alone; the noise counter is the mirror's abs_out.
+    int pcm_dither = RSMP_DITHER_NONE;
+    uint64_t pcm_dither_seed = 0;
 
     rsmp_fir(uint32_t i, uint32_t o, size_t t) : mirror(i, o, t) {}
 };

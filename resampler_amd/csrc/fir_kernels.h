@@ -51,6 +51,11 @@ struct FirStreamDesc {
     // bytes a sample), every sum quantised where it is stored (fir_pcm_quantise below); one width for all the streams of a
     // launch.  `hist_next` -- the frames that stay buffered -- is f32 always.
     uint32_t out_bits;
+    // PCM output only: RSMP_DITHER_NONE / RSMP_DITHER_TPDF, one mode for all the streams of a launch -- the host picks the kernels'
+    // dithered builds by it --, and the stream's own seed.  Value (frame n of the launch, channel c) takes the noise of index
+    // (abs_out + n) * channels + c (fir_pcm_dither below).  No build without PCM output reads either field, no undithered one the seed.
+    uint32_t dither;
+    uint64_t dither_seed;
 };
 
 // One sample of a stream's `in`, index `i` in values (frame * channels + channel).
@@ -68,21 +73,50 @@ __device__ __forceinline__ float fir_in_value(const FirStreamDesc& d, size_t i) 
 
 // f32 -> PCM code of `bits` (16 / 24 / 32): round_half_to_even(x * 2^(bits-1)), saturated to [-2^(bits-1), 2^(bits-1) - 1]; NaN -> 0.
 // The product is exact (a power of two; an overflow to +-inf saturates like any other value out of range), +inf is the top code
-// and -inf the bottom one, -0.0 and denormals give 0.  No dither.  The 32-bit top code 2^31 - 1 is no f32 value: the comparison
+// and -inf the bottom one, -0.0 and denormals give 0.  No dither (that is fir_pcm_quantise_dither below).  The 32-bit top code 2^31 - 1 is no f32 value: the comparison
 // saturates, not a clamp in f32.  Decoding a code with fir_pcm_value and quantising it again at the same width is the identity
 // for 16 and 24 bits.  For 32 bits it is NOT: the reference's input divisor is -2^31 (main.rs:131), the scale here is +2^31 -- an
 // f32 value means what it says on the way out --, so that round trip gives saturate(-f32(s)): polarity inverted, the bottom
 // code saturated to the top one.
-__host__ __device__ __forceinline__ int32_t fir_pcm_quantise(float x, uint32_t bits) {
-    const float v = rintf(x * (bits == 16 ? 32768.0f : bits == 24 ? 8388608.0f : 2147483648.0f));
+__host__ __device__ __forceinline__ float fir_pcm_scale(uint32_t bits) { return bits == 16 ? 32768.0f : bits == 24 ? 8388608.0f : 2147483648.0f; }
+// (v: the scaled value, already rounded to an integer, +-inf or NaN)
+__host__ __device__ __forceinline__ int32_t fir_pcm_code(float v, uint32_t bits) {
     if (!(v == v)) return 0;
     if (bits == 32) return v >= 2147483648.0f ? INT32_MAX : v <= -2147483648.0f ? INT32_MIN : static_cast<int32_t>(v);
     const float top = bits == 16 ? 32767.0f : 8388607.0f, bottom = bits == 16 ? -32768.0f : -8388608.0f;
     return static_cast<int32_t>(v > top ? top : v < bottom ? bottom : v);
 }
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise(float x, uint32_t bits) { return fir_pcm_code(rintf(x * fir_pcm_scale(bits)), bits); }
+
+// TPDF dither (RSMP_DITHER_TPDF): value `i` of a stream -- i = frame * channels + channel, counted from the stream's start or
+// reset -- is quantised as
+//   q = saturate(round_half_to_even(f32(x * 2^(bits-1)) + d(seed, i))),  NaN -> 0,
+// one f32 addition behind the exact product (an fma of the same operands gives the same bits); saturation and NaN as above.  The
+// noise has no state, it is a function of the seed and the index: splitmix64 of the counter i / 2 + 1 gives 64 bits, the low 32
+// for even i and the high 32 for odd i (one mix serves a two-channel frame); the difference of their two 16-bit halves, times
+// 2^-16, is triangular on (-1, 1) LSB with variance 1/6.  A stream's bytes therefore do not depend on how it is cut into calls.
+constexpr uint64_t kFirDitherStep = 0x9E3779B97F4A7C15ull;   // splitmix64's counter step: pair p starts from seed + (p + 1) * step
+__host__ __device__ __forceinline__ uint64_t fir_dither_mix(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__host__ __device__ __forceinline__ uint64_t fir_dither_word(uint64_t seed, uint64_t pair) {   // pair = i >> 1
+    return fir_dither_mix(seed + (pair + 1) * kFirDitherStep);
+}
+__host__ __device__ __forceinline__ float fir_dither_value(uint32_t h) {   // h: the value's 32 bits of the word
+    return static_cast<float>(static_cast<int32_t>(h & 0xFFFFu) - static_cast<int32_t>(h >> 16)) * (1.0f / 65536.0f);
+}
+__host__ __device__ __forceinline__ float fir_pcm_dither(uint64_t seed, uint64_t i) {
+    const uint64_t w = fir_dither_word(seed, i >> 1);
+    return fir_dither_value(static_cast<uint32_t>((i & 1) ? w >> 32 : w));
+}
+// The quantiser with the noise `d` of the value's index added: THE definition of dithered output, every site calls it.
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise_dither(float x, uint32_t bits, float d) {
+    return fir_pcm_code(rintf(x * fir_pcm_scale(bits) + d), bits);
+}
 // One sample of a stream's PCM `out`, index `i` in values: the lane writes the sample's own bytes and no others.
-__device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y) {
-    const int32_t q = fir_pcm_quantise(y, bits);
+__device__ __forceinline__ void fir_pcm_store_code(void* out, uint32_t bits, size_t i, int32_t q) {
     if (bits == 16) {
         static_cast<int16_t*>(out)[i] = static_cast<int16_t>(q);
     } else if (bits == 32) {
@@ -94,20 +128,29 @@ __device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i
         p[2] = static_cast<uint8_t>(q >> 16);
     }
 }
-// Value `i` of a stream's output.  OUT: the PCM-output builds of the generic kernels and of the repair pass (out_bits != 0); the
-// f32 builds do not read the field.
-template <bool OUT>
+__device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y) { fir_pcm_store_code(out, bits, i, fir_pcm_quantise(y, bits)); }
+// How a build stores its sums: f32, PCM, PCM with TPDF dither (the launchers' choice by out_bits and dither).
+enum FirOut : int { kFirOutF32 = 0, kFirOutPcm = 1, kFirOutPcmTpdf = 2 };
+__host__ __device__ constexpr FirOut fir_out_mode(uint32_t out_bits, uint32_t dither) {
+    return out_bits == 0 ? kFirOutF32 : dither == RSMP_DITHER_TPDF ? kFirOutPcmTpdf : kFirOutPcm;
+}
+// Value `i` of a stream's output in this launch.  OUT: the PCM-output builds of the generic kernels and of the repair pass (out_bits
+// != 0), with and without dither; the f32 builds do not read the fields.
+template <int OUT>
 __device__ __forceinline__ void fir_out_store(const FirStreamDesc& d, size_t i, float y) {
-    if constexpr (OUT) fir_pcm_store(d.out, d.out_bits, i, y);
+    if constexpr (OUT == kFirOutPcmTpdf)
+        fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_dither(y, d.out_bits, fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i)));
+    else if constexpr (OUT == kFirOutPcm) fir_pcm_store(d.out, d.out_bits, i, y);
     else d.out[i] = y;
 }
 
 constexpr uint32_t kFirTile = 32;   // output frames per workgroup tile (generic kernel): one pass of 32 x 8 lanes
 
 // Generic kernel: any ratio, reference-form two-row interpolation; grid = (max tiles, streams).
-// (out_bits, here and below: FirStreamDesc::out_bits of the launch's streams -- != 0 selects the builds that store PCM)
+// (out_bits / dither, here and below: FirStreamDesc::out_bits / dither of the launch's streams -- out_bits != 0 selects the builds
+// that store PCM, dither their dithered twins)
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, uint32_t out_bits = 0);
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, uint32_t out_bits = 0, uint32_t dither = 0);
 // The same arithmetic for LONG launches (fir_generic_bulk.hip): tiles of up to 4096 output frames per workgroup, their outputs sorted
 // by phase row, the tile's input window in LDS.  hipErrorNotSupported where no tile fits the LDS (fir_generic_bulk_tile == 0);
 // does not copy the tails (launch_fir_tail_copy).
@@ -116,14 +159,15 @@ uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double 
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels = 0,
                                    uint32_t uniform_taps = 0,    // (uniform_taps: 128 = every stream has 128 taps)
-                                   uint32_t out_bits = 0);       // (PCM output: two-channel streams only, hipErrorNotSupported otherwise)
+                                   uint32_t out_bits = 0,       // (PCM output: two-channel streams only, hipErrorNotSupported otherwise)
+                                   uint32_t dither = 0);
 constexpr uint32_t kFirBulkMinOut = 8192;   // launches whose longest generic stream produces fewer frames keep fir_generic_kernel
 // Re-evaluates, in the reference's two-row form, the output chunks a periodic launch marked as non-finite
 // (fir_nonfinite.h); exits at once when the launch marked nothing.
 // (done / done_attached, here and in launch_fir_tail_copy: as in launch_fir_repair_multi below -- the launch completes `done`
 // itself; *done_attached stays false when there was nothing to launch)
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done = nullptr, bool* done_attached = nullptr, uint32_t out_bits = 0);
+                             hipEvent_t done = nullptr, bool* done_attached = nullptr, uint32_t out_bits = 0, uint32_t dither = 0);
 // The same for up to eight groups of streams (each with its own marks) in one launch.
 struct RepairJob {
     const FirStreamDesc* d_descs;
@@ -137,7 +181,7 @@ constexpr uint32_t kMaxRepairJobs = 8;
 // own behind the kernel as hipEventRecord puts there; *done_attached = false: there was no such launch, record it yourself)
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs = nullptr,
                                    uint32_t n_tail = 0, uint32_t max_tail_values = 0, hipEvent_t done = nullptr, bool* done_attached = nullptr,
-                                   uint32_t out_bits = 0);
+                                   uint32_t out_bits = 0, uint32_t dither = 0);
 // Copies the still-buffered tail of [hist|in] into hist_next; grid = (blocks, streams).
 hipError_t launch_fir_tail_copy(const FirStreamDesc* d_descs, uint32_t n_streams,
                                 uint32_t max_tail_values, hipStream_t stream, hipEvent_t done = nullptr, bool* done_attached = nullptr);

@@ -59,6 +59,7 @@ struct Launch {
     std::vector<FirJob>& jobs;
     const hipStream_t stream;
     const uint32_t pcm_bits, out_bits;
+    uint32_t dither = 0;   // PCM output: the handles' dither mode (rsmp_fir_set_pcm_dither), one for the launch
     const size_t n;
     // launch order: generic jobs, then periodic jobs grouped by geometry (one launch per geometry)
     std::vector<size_t> order;
@@ -111,6 +112,13 @@ int bind_and_group(Launch& L) {
     }
     for (const Group& g : L.groups) for (size_t i : g.members) L.order.push_back(i);
     // PCM input and PCM output have one admission rule: two-channel streams; periodic groups on the split kernel's builds for them
+    if (L.out_bits != 0) {
+        L.dither = static_cast<uint32_t>(jobs[0].r->pcm_dither);
+        for (const FirJob& j : jobs)
+            if (static_cast<uint32_t>(j.r->pcm_dither) != L.dither)
+                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: one dither mode for all the streams of a batch (rsmp_fir_set_pcm_dither; "
+                                                       "the seeds may differ)");
+    }
     if (L.pcm_bits != 0 || L.out_bits != 0) {
         for (const FirJob& j : jobs)
             if (j.r->channels != 2)
@@ -262,6 +270,8 @@ int fill_descriptors(Launch& L) {
         ds.abs_consumed = r->mirror.abs_consumed();
         ds.in_bits = L.pcm_bits;
         ds.out_bits = L.out_bits;
+        ds.dither = L.dither;
+        ds.dither_seed = L.out_bits != 0 ? r->pcm_dither_seed : 0;
         if (ds.tail_frames * ch > L.max_tail_values) L.max_tail_values = ds.tail_frames * ch;
         if (!pl.periodic) {
             ds.segs = reinterpret_cast<const rsmp_fir_segment*>(L.d + pp.seg_off);
@@ -318,10 +328,10 @@ int launch_generic(Launch& L) {
         RSMP_HIP_CHECK(launch_fir_generic_bulk(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic,
                                                L.max_taps_generic, L.max_ratio_generic, L.stream,
                                                L.min_ch_generic == L.max_ch_generic ? L.max_ch_generic : 0u,
-                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.out_bits));
+                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.out_bits, L.dither));
     } else if (L.n_generic)
         RSMP_HIP_CHECK(launch_fir_generic(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic, L.stream,
-                                          L.tail_fused, L.out_bits));
+                                          L.tail_fused, L.out_bits, L.dither));
     return RSMP_OK;
 }
 
@@ -395,7 +405,8 @@ int launch_periodic_groups(Launch& L) {
             split_jobs.push_back(SplitJob{L.d_descs + first, static_cast<uint32_t>(g.members.size()), &g.geo, max_blocks, rp.nf});
         } else {
             RSMP_HIP_CHECK(launch_fir_periodic(L.d_descs + first, static_cast<uint32_t>(g.members.size()), g.geo, max_blocks,
-                                               leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.pcm_bits, L.out_bits));
+                                               leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.pcm_bits, L.out_bits,
+                                               L.dither));
         }
         first += g.members.size();
     }
@@ -462,11 +473,11 @@ int launch_followups(Launch& L) {
         std::vector<RepairJob> rj;
         for (const Repair& rp : L.repairs) rj.push_back(RepairJob{L.d_descs + rp.first, rp.count, rp.nf});
         RSMP_HIP_CHECK(launch_fir_repair_multi(rj.data(), rj.size(), L.stream, nullptr, 0, 0, repair_last ? L.done : nullptr,
-                                               &L.done_attached, L.out_bits));
+                                               &L.done_attached, L.out_bits, L.dither));
     } else {
         for (const Repair& rp : L.repairs)
             RSMP_HIP_CHECK(launch_fir_repair(L.d_descs + rp.first, rp.count, rp.nf, L.stream, repair_last ? L.done : nullptr,
-                                             &L.done_attached, L.out_bits));
+                                             &L.done_attached, L.out_bits, L.dither));
     }
     if (n > n_generic && L.max_wraps > 0)
         RSMP_HIP_CHECK(launch_fir_wrap_fixup(L.d_descs + n_generic, static_cast<uint32_t>(n - n_generic), L.max_wraps, L.stream,

@@ -43,7 +43,9 @@ int order_behind_handle(rsmp_fir* h, hipStream_t stream, const FirLaunchEvent*& 
 // `leader` owns the launch workspace.
 // pcm_bits != 0: every job's d_in is a WAV file's PCM of that width, read in place (FirStreamDesc::in_bits): two-channel
 // streams on the generic kernel (short launches) or the split kernel's PCM builds.
-// out_bits != 0: every job's d_out receives PCM of that width (FirStreamDesc::out_bits); the same streams and kernels.
+// out_bits != 0: every job's d_out receives PCM of that width (FirStreamDesc::out_bits); the same streams and kernels.  The
+// handles' dither setting (rsmp_fir_set_pcm_dither) applies: one mode for all of them -- RSMP_ERR_INVALID_ARGUMENT otherwise, before
+// anything is launched or changed --, a seed each.
 int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0);
 
 }  // namespace rsmp

@@ -163,6 +163,7 @@ struct StreamCtx {
     uint64_t abs_out, abs_consumed, wrap_k0;
     uint64_t q_first;     // abs_out / b: the period holding the launch's first output
     uint32_t sidx;        // the stream's index in the launch
+    uint64_t dither_seed; // (read by the dithered PCM-output builds alone)
 };
 
 // Through the scalar cache (constant address space): the descriptors do not change during the launch,
@@ -189,6 +190,7 @@ __device__ __forceinline__ StreamCtx load_stream(const FirStreamDesc* descs, uin
     c.wrap_k0 = d.wrap_k0;
     c.q_first = d.abs_out / b;   // (64-bit division: once per stream, not per item)
     c.sidx = s;
+    c.dither_seed = d.dither_seed;
     return c;
 }
 
@@ -478,8 +480,9 @@ __device__ __forceinline__ uint32_t consumer_index(uint32_t w) { return w < 6 ? 
 // ROUNDS: lane tasks per stager lane and item -- 2 for periods of 161 .. 320 frames (96 -> 44.1 kHz, 96 -> 48 kHz): both
 // rounds' loads are in flight together, one item ahead, like the single round's.
 // OUT: the streams' `out` is PCM (FirStreamDesc::out_bits: 16 / 24 / 32, one width per launch, read from the descriptor by
-// these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise).
-template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0, bool OUT = false>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
+// these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise) -- OUT is a FirOut; the
+// kFirOutPcmTpdf builds add TPDF dither there (fir_pcm_quantise_dither; the stream's seed from the descriptor, one 64-bit mix per frame).
+template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0, int OUT = kFirOutF32>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
 __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__ descs, const SplitArgs& g,
                                                const uint32_t wg, const uint32_t n_wgs) {   // workgroup `wg` of the `n_wgs` that share g's items
     static_assert(ROUNDS == 1 || ((WIDE == 0 || WIDE == 1) && PLANES == 2), "two rounds: two channels or channel pairs, fp16 planes");
@@ -1346,6 +1349,12 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     g_f32_ptr pend_o = nullptr;
     bool pend_ph = false;   // WIDE == 3: the pending sums are the last channel's
     bool pend = false;
+    // dithered builds: a frame's noise counter (dither_key below); nothing in the others
+    struct NoKey {
+        __device__ NoKey operator+(uint64_t) const { return NoKey{}; }
+    };
+    typedef typename std::conditional<OUT == kFirOutPcmTpdf, uint64_t, NoKey>::type dkey_t;
+    dkey_t pend_k{};
     typedef v2f __attribute__((address_space(1)))* g_f2_ptr;
     // PCM output: the launch's width (wave-uniform, in a scalar register) and the bytes of a two-channel frame
     uint32_t out_bits = 0, out_fb = 0;
@@ -1359,8 +1368,29 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     typedef uint32_t __attribute__((address_space(1)))* g_u32_ptr;
     // PCM output, one frame (y0, y1) at `o`: 4 bytes (4-byte aligned), 6 bytes (2-byte aligned) or 8 bytes (4-byte aligned: the
     // buffer's own alignment is all the entry asks for)
-    auto store_frame_pcm = [&](g_f32_ptr o, float y0, float y1) {
-        const uint32_t q0 = static_cast<uint32_t>(fir_pcm_quantise(y0, out_bits)), q1 = static_cast<uint32_t>(fir_pcm_quantise(y1, out_bits));
+    // Dithered builds: frame n of stream d's launch draws its two values' noise from the word fir_dither_mix(dither_key(d, n)) --
+    // fir_dither_word of pair abs_out + n: the values' indices are 2 (abs_out + n) and that + 1 --, the frames behind it from
+    // the key + kFirDitherStep each.  The key carries the stream's seed and counter: a pending store needs nothing else of `d`.
+    auto dither_key = [&](const StreamCtx& d, int32_t n) -> dkey_t {
+        if constexpr (OUT != kFirOutPcmTpdf) return NoKey{};
+        else return d.dither_seed + (d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n)) + 1u) * kFirDitherStep;
+    };
+    // a frame's two dithered codes (the undithered builds quantise below, in the statements they always had: their code is unchanged)
+    auto dither_frame = [&](float y0, float y1, dkey_t k, uint32_t& q0, uint32_t& q1) {
+        if constexpr (OUT == kFirOutPcmTpdf) {
+            const uint64_t w = fir_dither_mix(k);
+            q0 = static_cast<uint32_t>(fir_pcm_quantise_dither(y0, out_bits, fir_dither_value(static_cast<uint32_t>(w))));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise_dither(y1, out_bits, fir_dither_value(static_cast<uint32_t>(w >> 32))));
+        }
+    };
+    auto store_frame_pcm = [&](g_f32_ptr o, float y0, float y1, dkey_t k) {
+        uint32_t q0, q1;
+        if constexpr (OUT == kFirOutPcmTpdf) {
+            dither_frame(y0, y1, k, q0, q1);
+        } else {
+            q0 = static_cast<uint32_t>(fir_pcm_quantise(y0, out_bits));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise(y1, out_bits));
+        }
         if (out_bits == 16) {
             *(g_u32_ptr)o = (q0 & 0xFFFFu) | (q1 << 16);
         } else if (out_bits == 24) {
@@ -1374,11 +1404,16 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     };
     // PCM output, a lane's four frames x two channels at `o`: 16 bytes (4-byte aligned), 24 bytes (2-byte aligned) or 32 bytes
     // (4-byte aligned).  No store is wider than the alignment of its address, every byte is written once, none beside the 4 frames.
-    auto store_frames_pcm = [&](g_f32_ptr o, const v4f& lo, const v4f& hi) {
+    auto store_frames_pcm = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, dkey_t k) {
         const float y[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
         uint32_t q[8];
+        if constexpr (OUT == kFirOutPcmTpdf) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) q[i] = static_cast<uint32_t>(fir_pcm_quantise(y[i], out_bits));
+            for (int i = 0; i < 4; ++i) dither_frame(y[2 * i], y[2 * i + 1], k + static_cast<uint64_t>(i) * kFirDitherStep, q[2 * i], q[2 * i + 1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) q[i] = static_cast<uint32_t>(fir_pcm_quantise(y[i], out_bits));
+        }
         if (out_bits == 16) {
             typedef v4u __attribute__((address_space(1), aligned(4)))* g_u4a4_ptr;
             *(g_u4a4_ptr)o = v4u{(q[0] & 0xFFFFu) | (q[1] << 16), (q[2] & 0xFFFFu) | (q[3] << 16), (q[4] & 0xFFFFu) | (q[5] << 16), (q[6] & 0xFFFFu) | (q[7] << 16)};
@@ -1413,9 +1448,9 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         }
     };
     // a lane's four frames x two channels: 32 contiguous bytes, or (WIDE) 8 bytes in each of four frames
-    auto store_frames = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, bool ph) {
+    auto store_frames = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, bool ph, dkey_t k) {   // (k: dithered builds, the first frame's key)
         if constexpr (OUT) {
-            store_frames_pcm(o, lo, hi);
+            store_frames_pcm(o, lo, hi, k);
         } else if constexpr (WIDE) {
             if (kOdd && ph) {   // the last channel alone: one value per frame
                 o[0] = lo.x;
@@ -1444,7 +1479,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     };
     auto flush_pending = [&]() {
         if (pend) {   // wave-uniform
-            store_frames(pend_o, pend_lo, pend_hi, pend_ph);
+            store_frames(pend_o, pend_lo, pend_hi, pend_ph, pend_k);
             pend = false;
         }
     };
@@ -1612,16 +1647,17 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                 pend_hi = hi;
                 pend_o = o;
                 pend_ph = phantom(cu.cur_pair);
+                pend_k = dither_key(d, n0);
                 pend = true;
             } else if (full) {
-                store_frames(o, lo, hi, phantom(cu.cur_pair));
+                store_frames(o, lo, hi, phantom(cu.cur_pair), dither_key(d, n0));
             } else {
                 const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int32_t n = n0 + r;
                     if (j0 + r < g.b && n >= 0 && n < n_limit) {
-                        if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1]);
+                        if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1], dither_key(d, n));
                         else if (mono) o[r] = v[2 * r];
                         else if (phantom(cu.cur_pair)) o[fs * r] = v[2 * r];
                         else if constexpr (kOdd) *((g_f2u_ptr)(o + fs * r)) = v2f{v[2 * r], v[2 * r + 1]};
@@ -1648,7 +1684,12 @@ __global__ __launch_bounds__(1024) void fir_split_kernel(const FirStreamDesc* __
 // PCM output (FirStreamDesc::out_bits) from the two-channel fp16 builds of the 128-tap windows, f32 or PCM input.
 template <int NK, int ROUNDS, int BITS>
 __global__ __launch_bounds__(1024) void fir_split_pcm_out_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
-    fir_split_body<NK, 2, false, 0, ROUNDS, BITS, true>(descs, g, blockIdx.x, gridDim.x);
+    fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcm>(descs, g, blockIdx.x, gridDim.x);
+}
+// ... and with TPDF dither (FirStreamDesc::dither, dither_seed): builds of their own, so that the undithered ones stay as they were
+template <int NK, int ROUNDS, int BITS>
+__global__ __launch_bounds__(1024) void fir_split_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
+    fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcmTpdf>(descs, g, blockIdx.x, gridDim.x);
 }
 template <int NK, int PLANES, int WIDE, int ROUNDS>
 __global__ __launch_bounds__(1024) void fir_split_multi_kernel(const SplitMulti m) {
@@ -1741,8 +1782,10 @@ hipError_t items_workspace(int device, hipStream_t stream, size_t need, uint64_t
 // geometry runs on).
 namespace {
 const void* split_kernel_for(const SplitBuild& build) {
-#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B, false}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
-#define RSMP_SPLIT_OUT1(NK, R, B) {SplitBuild{NK, 2, false, 0, R, B, true}, reinterpret_cast<const void*>(fir_split_pcm_out_kernel<NK, R, B>)}
+#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B, false, false}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
+#define RSMP_SPLIT_OUT1(NK, R, B)                                                                                        \
+    {SplitBuild{NK, 2, false, 0, R, B, true, false}, reinterpret_cast<const void*>(fir_split_pcm_out_kernel<NK, R, B>)}, \
+    {SplitBuild{NK, 2, false, 0, R, B, true, true}, reinterpret_cast<const void*>(fir_split_pcm_tpdf_kernel<NK, R, B>)}
 #define RSMP_SPLIT_OUT(B) RSMP_SPLIT_OUT1(5, 1, B), RSMP_SPLIT_OUT1(5, 2, B), RSMP_SPLIT_OUT1(6, 2, B)
 #define RSMP_SPLIT_1TO5(P, D, W) RSMP_SPLIT(1, P, D, W, 1, 0), RSMP_SPLIT(2, P, D, W, 1, 0), RSMP_SPLIT(3, P, D, W, 1, 0), RSMP_SPLIT(4, P, D, W, 1, 0), RSMP_SPLIT(5, P, D, W, 1, 0)
 #define RSMP_SPLIT_PCM(B) RSMP_SPLIT(5, 2, false, 0, 1, B), RSMP_SPLIT(5, 2, false, 0, 2, B), RSMP_SPLIT(6, 2, false, 0, 2, B)
@@ -1757,7 +1800,8 @@ const void* split_kernel_for(const SplitBuild& build) {
         RSMP_SPLIT(5, 2, true, 0, 2, 0), RSMP_SPLIT(6, 2, true, 0, 2, 0), RSMP_SPLIT(6, 2, true, 1, 2, 0),
         // PCM input: the two-channel fp16 builds of the 128-tap windows
         RSMP_SPLIT_PCM(16), RSMP_SPLIT_PCM(24), RSMP_SPLIT_PCM(32),
-        // PCM output (its width read from the descriptor) from the same three builds, for f32 input and the three PCM widths
+        // PCM output (its width read from the descriptor) from the same three builds, for f32 input and the three PCM widths, each
+        // without and with TPDF dither
         RSMP_SPLIT_OUT(0), RSMP_SPLIT_OUT(16), RSMP_SPLIT_OUT(24), RSMP_SPLIT_OUT(32)};
 #undef RSMP_SPLIT_OUT
 #undef RSMP_SPLIT_OUT1
@@ -1772,10 +1816,10 @@ const void* split_kernel_for(const SplitBuild& build) {
 
 hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, const PeriodicGeometry& geo,
                             uint32_t max_blocks, uint32_t cus, bool fuse_tail, const NfArgs& nf, hipStream_t stream,
-                            uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits) {
+                            uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither) {
     static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
     const bool diag = fir_debug_knob() != 0 || wtrace_path != nullptr;
-    const SplitChoice choice = split_build_for(geo, diag, pcm_bits, out_bits);
+    const SplitChoice choice = split_build_for(geo, diag, pcm_bits, out_bits, dither);
     if (choice.error != BuildError::kNone) return choice.error == BuildError::kInvalid ? hipErrorInvalidValue : hipErrorNotSupported;
     const void* fn = split_kernel_for(choice.build);
     if (fn == nullptr) return hipErrorInvalidValue;

@@ -12,6 +12,12 @@ roofline.kernel_ms); the conversion pass of (b) is bracketed by events on the sa
 back to back (no host synchronisation between them: the GPU stays busy, as in bench.py's timed loop) and counts as the mean of their
 event pairs; every row starts with --spinup seconds of its own steps.  Median of --reps repetitions with min / max; row (a) is
 measured again at the end (a_f32_output_again) to show what the box's drift over the run amounts to.  Prints one JSON object.
+
+--dither tpdf: rows (b), (c) and (d) with TPDF dither (ResamplerFir.set_pcm_dither, stream i's seed = --seed + i; the conversion
+pass of (b) dithers with the same seeds); --dither none (the default) is the table as it was.
+--convert: instead of the table, the stand-alone conversion alone -- rsmp_f32_to_pcm_device without and with dither over
+--convert-values values, and rsmp_device_stream_copy moving the same number of bytes (the conversion reads 4 and writes bits / 8
+bytes a value, the copy reads and writes 4 bytes a float) -- each bracketed by events, median of --reps bursts, with GB/s.
 """
 from __future__ import annotations
 
@@ -32,6 +38,44 @@ def stats(v):
     return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(v.min()), 4), "max_ms": round(float(v.max()), 4)}
 
 
+def convert_rows(a, torch, ra, dev):
+    """The stand-alone conversion against a plain copy of the same bytes."""
+    n = a.convert_values
+    x = (torch.rand(n, device=dev) * 2.0 - 1.0).contiguous()
+    stream = ra.torch_stream()
+    result = {"values": n, "reps": a.reps, "burst": a.burst, "rows": {}}
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.burst):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / a.burst)
+        return times
+
+    for bits in (16, 24, 32):
+        moved = n * (4 + bits // 8)
+        out = torch.empty(n * bits // 8, dtype=torch.uint8, device=dev)
+        m = (moved // 8) & ~3      # floats of a copy that moves as many bytes (a multiple of 4 floats)
+        src, dst = torch.empty(m, device=dev), torch.empty(m, device=dev)
+        rows = {"f32_to_pcm": timed(lambda: ra.f32_to_pcm_device(x, bits, out, stream)),
+                "f32_to_pcm_tpdf": timed(lambda: ra.f32_to_pcm_device(x, bits, out, stream, dither=ra.Dither.TPDF, seed=a.seed, first_index=12345)),
+                "stream_copy_same_bytes": timed(lambda: ra.device_stream_copy(src, dst, stream))}
+        for k, t in rows.items():
+            st = stats(t)
+            st["gb_per_s"] = round(moved / (st["median_ms"] * 1e-3) / 1e9, 1)
+            result["rows"][f"{k}_{bits}"] = st
+        del out, src, dst
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=64)
@@ -40,6 +84,10 @@ def main():
     ap.add_argument("--burst", type=int, default=8)
     ap.add_argument("--spinup", type=float, default=1.0)
     ap.add_argument("--chunk", type=int, default=512)
+    ap.add_argument("--dither", choices=("none", "tpdf"), default="none")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--convert", action="store_true")
+    ap.add_argument("--convert-values", type=int, default=1 << 27)
     a = ap.parse_args()
 
     import torch
@@ -47,8 +95,13 @@ def main():
     from resampler_amd import synth
 
     dev = torch.device("cuda:0")
+    if a.convert:
+        return convert_rows(a, torch, ra, dev)
     S, N, chunk = a.streams, a.frames, a.chunk
+    dither = ra.Dither.TPDF if a.dither == "tpdf" else ra.Dither.NONE
     hs = [ra.ResamplerFir.new(2, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000, ra.Latency.Sample64, ra.Attenuation.Db90) for _ in range(S)]
+    for i, h in enumerate(hs):
+        h.set_pcm_dither(dither, a.seed + i)
     batch = ra.FirBatch(hs)
     batch.device_planner = False   # (the fused entry is planned on the host: the same planner for every row of the table)
     base = torch.from_numpy(synth.sweep(N, 2, 44100.0)).to(dev)
@@ -83,7 +136,7 @@ def main():
             times.append(t)
         return times
 
-    result = {"streams": S, "frames": N, "reps": a.reps, "rows": {}}
+    result = {"streams": S, "frames": N, "reps": a.reps, "dither": a.dither, "rows": {}}
     produced = [0]
 
     def f32_launch(e0=None, e1=None):
@@ -103,8 +156,8 @@ def main():
         def two_pass(e0, e1):
             f32_launch()
             e0.record()
-            for o, q, n in zip(d_out, d_pcm_out, produced[0]):
-                ra.f32_to_pcm_device(o[:n], bits, q, stream)
+            for i, (o, q, n) in enumerate(zip(d_out, d_pcm_out, produced[0])):
+                ra.f32_to_pcm_device(o[:n], bits, q, stream, dither=dither, seed=a.seed + i)
             e1.record()
             return True
 
