@@ -109,6 +109,14 @@ extern "C" {
     // addition: the dither of a handle's PCM output (rsmp_fir_batch_resample_bulk_pcm_out_device)
     fn rsmp_fir_set_pcm_dither(r: *mut rsmp_fir, dither: c_int, seed: u64) -> c_int;
     fn rsmp_fir_pcm_dither(r: *const rsmp_fir, dither: *mut c_int, seed: *mut u64) -> c_int;
+    // addition: statistics of the PCM written (values, clipped, NaN, peak): the converters that count, and a handle's totals
+    fn rsmp_f32_to_pcm_stats(input: *const f32, n_values: usize, bits: c_int, dither: c_int, seed: u64, first_index: u64,
+                             out_pcm: *mut std::os::raw::c_void, stats: *mut PcmStats) -> c_int;
+    fn rsmp_f32_to_pcm_stats_device(d_in: *const f32, n_values: usize, bits: c_int, dither: c_int, seed: u64, first_index: u64,
+                                    d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats, stream: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_fir_set_pcm_stats(r: *mut rsmp_fir, enable: c_int) -> c_int;
+    fn rsmp_fir_pcm_stats(r: *mut rsmp_fir, stats: *mut PcmStats) -> c_int;
+    fn rsmp_fir_pcm_stats_clear(r: *mut rsmp_fir) -> c_int;
     // addition: WAV samples (resample/src/main.rs:128-137) converted inside the FFT kernel's first load
     fn rsmp_fft_batch_resample_bulk_pcm_device(rs: *const *mut rsmp_fft, n: usize, d_pcm: *const *const std::os::raw::c_void, bits: c_int,
                                                d_out: *const *mut f32, n_chunks: *const usize, stream: *mut std::os::raw::c_void) -> c_int;
@@ -240,6 +248,41 @@ impl ResamplerFir {
         unsafe { rsmp_fir_pcm_dither(self.handle, &mut d, &mut s) };
         (d as i32, s)
     }
+
+    /// Addition to the reference API: count what `resample_bulk_pcm_out_device` stores for this stream (off by default; a setting:
+    /// `reset` leaves it).  The bytes do not change; `pcm_stats` reads the totals.
+    pub fn set_pcm_stats(&mut self, enable: bool) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fir_set_pcm_stats(self.handle, enable as c_int) })
+    }
+    /// Totals of every PCM-output launch of this handle since it was made, last `reset` or last `pcm_stats_clear`: the statistics
+    /// `f32_to_pcm_stats` gives for the f32 output.  Waits for the handle's last launch.  All zero with the setting off.
+    pub fn pcm_stats(&mut self) -> Result<PcmStats, ResampleError> {
+        let mut st = PcmStats::default();
+        status(unsafe { rsmp_fir_pcm_stats(self.handle, &mut st) }).map(|_| st)
+    }
+    /// Zeroes the totals; ordered like a launch of the handle.
+    pub fn pcm_stats_clear(&mut self) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fir_pcm_stats_clear(self.handle) })
+    }
+}
+
+/// What a PCM writer did to the values it was given (rsmp_pcm_stats, 32 bytes): values quantised, of which saturated, of which NaN
+/// (stored as 0, not clipped), and the largest |x| of the others before scaling and dither (+inf possible, 0.0 if none).
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+#[repr(C)]
+pub struct PcmStats {
+    pub values: u64,
+    pub clipped: u64,
+    pub nans: u64,
+    pub peak: f32,
+    pub reserved: u32,
+}
+
+impl PcmStats {
+    /// Two sets merge field by field: the counts add, the peak is the larger one.
+    pub fn merged(&self, o: &PcmStats) -> PcmStats {
+        PcmStats { values: self.values + o.values, clipped: self.clipped + o.clipped, nans: self.nans + o.nans, peak: self.peak.max(o.peak), reserved: 0 }
+    }
 }
 
 /// Dither of PCM output (RSMP_DITHER_*): none, or triangular noise of +-1 LSB added before the rounding.
@@ -273,6 +316,23 @@ pub fn f32_to_pcm_dither(input: &[f32], bits: u32, dither: Dither, seed: u64, fi
 pub unsafe fn f32_to_pcm_dither_device(d_in: *const f32, n_values: usize, bits: u32, dither: Dither, seed: u64, first_index: u64,
                                        d_pcm: *mut std::os::raw::c_void) -> Result<(), ResampleError> {
     status(rsmp_f32_to_pcm_dither_device(d_in, n_values, bits as c_int, dither as c_int, seed, first_index, d_pcm, std::ptr::null_mut()))
+}
+
+/// `f32_to_pcm_dither` that also says what it did (the definition of the statistics, on the host): the bytes -- those of
+/// `f32_to_pcm_dither` -- and the statistics stated at rsmp_f32_to_pcm_stats (include/resampler_amd.h).
+pub fn f32_to_pcm_stats(input: &[f32], bits: u32, dither: Dither, seed: u64, first_index: u64) -> Result<(Vec<u8>, PcmStats), ResampleError> {
+    let mut out = vec![0u8; input.len() * (bits as usize / 8)];
+    let mut st = PcmStats::default();
+    status(unsafe {
+        rsmp_f32_to_pcm_stats(input.as_ptr(), input.len(), bits as c_int, dither as c_int, seed, first_index, out.as_mut_ptr() as *mut std::os::raw::c_void, &mut st)
+    }).map(|_| (out, st))
+}
+
+/// The same on device memory; `d_pcm` may be null (measure only); the call's statistics are MERGED into `*d_stats` (device memory,
+/// 8-byte aligned, zeroed by the caller).  Asynchronous on the default stream.
+pub unsafe fn f32_to_pcm_stats_device(d_in: *const f32, n_values: usize, bits: u32, dither: Dither, seed: u64, first_index: u64,
+                                      d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats) -> Result<(), ResampleError> {
+    status(rsmp_f32_to_pcm_stats_device(d_in, n_values, bits as c_int, dither as c_int, seed, first_index, d_pcm, d_stats, std::ptr::null_mut()))
 }
 
 /// impl fmt::Debug for ResamplerFir (src/resampler_fir.rs:203-211): channels, taps, phases, `..`

@@ -100,6 +100,16 @@ uint32_t rsmp_sample_rate_hz(int sample_rate);
 
 /* ============================ ResamplerFir (src/resampler_fir.rs) =============================== */
 typedef struct rsmp_fir rsmp_fir;
+/* What a PCM writer did to the values it was given (no counterpart in the reference, which writes f32; SoX prints "clipped N
+ * samples").  32 bytes.  The rule is stated at rsmp_f32_to_pcm_stats.  Two sets merge field by field: the counts add, the peak
+ * is the larger one. */
+typedef struct rsmp_pcm_stats {
+    uint64_t values;     /* values quantised */
+    uint64_t clipped;    /* ... of which lay outside the code range and were saturated */
+    uint64_t nans;       /* ... of which were NaN and were stored as 0 (not counted as clipped) */
+    float peak;          /* largest |x| of the values that were not NaN, before scaling and dither; +inf possible; 0 if none */
+    uint32_t reserved;   /* 0 */
+} rsmp_pcm_stats;
 
 /* ResamplerFir::new (resampler_fir.rs:252-266).  NULL + rsmp_last_error() on failure. */
 rsmp_fir* rsmp_fir_new(size_t channels, int input_rate, int output_rate, int latency,
@@ -225,6 +235,22 @@ int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, c
  * changed --; the seeds are per stream.  rsmp_fir_pcm_dither reads the setting back (either pointer may be NULL). */
 int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed);
 int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* seed);
+/* Statistics of the PCM that entry writes for this handle: a setting, default 0 (off), that survives rsmp_fir_reset and
+ * rsmp_fir_seek like the dither setting.  With it on, a PCM-output launch takes builds of its kernels that count every value they
+ * store by rsmp_f32_to_pcm_stats's rule (below) -- the bytes are unchanged -- and adds the launch's counts to the handle's totals
+ * in device memory: exactly rsmp_f32_to_pcm_stats's of the f32 entry's output with the handle's dither, seed and
+ * first_index = abs_out * channels, chunks rewritten by the repair pass counted as rewritten.  One setting for all the streams of
+ * a batch, as out_bits and the dither mode: a mix is RSMP_ERR_INVALID_ARGUMENT before any launch, nothing written, no state
+ * changed.  Turning the setting on allocates the 32 bytes.
+ * rsmp_fir_pcm_stats: the totals of every PCM-output launch of the handle since it was made, last reset or last clear; waits for
+ * the handle's last launch, as rsmp_fir_last_kernel_ms does, then copies 32 bytes.  A handle with the setting off: all zero.
+ * rsmp_fir_pcm_stats_clear zeroes the totals; rsmp_fir_reset and rsmp_fir_batch_reset do the same -- a new stream starts,
+ * as the dither sequence does --, rsmp_fir_seek leaves them.  A clear is ordered like any other call of the handle, behind the
+ * launches made before it and ahead of those made after it, and enqueues nothing: the next counting launch replaces the totals
+ * instead of adding to them.  Null handle or null `stats`: RSMP_ERR_INVALID_ARGUMENT, nothing written. */
+int rsmp_fir_set_pcm_stats(rsmp_fir* r, int enable);
+int rsmp_fir_pcm_stats(rsmp_fir* r, rsmp_pcm_stats* stats);
+int rsmp_fir_pcm_stats_clear(rsmp_fir* r);
 
 /* reset() for every stream of a batch. */
 void rsmp_fir_batch_reset(rsmp_fir* const* rs, size_t n);
@@ -456,6 +482,23 @@ int rsmp_f32_to_pcm_dither(const float* in, size_t n_values, int bits, int dithe
                            void* out_pcm);
 int rsmp_f32_to_pcm_dither_device(const float* d_in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
                                   void* d_pcm, void* stream);
+/* The same, and what it did.  For a value x (before scaling), width `bits` and noise d (0 without dither) let
+ *   v = round_half_to_even(f32(x * 2^(bits-1)) + d)   -- the quantiser's own v.  Then
+ *   values   counts every value;
+ *   nans     those with x NaN (stored as 0, not clipped);
+ *   clipped  those with v not NaN and outside the code range: v > 2^(bits-1) - 1 or v < -2^(bits-1); at 32 bits, whose top code is
+ *            no f32 value, v >= 2^31 or v < -2^31.  So +-inf clip, +1.0 clips, -1.0 does not;
+ *   peak     the maximum of |x| over the values that are not NaN, an f32, before scaling and before dither (+inf possible; 0.0
+ *            when there is no such value).
+ * No field depends on the order of evaluation.  The bytes written are rsmp_f32_to_pcm_dither[_device]'s with the same arguments;
+ * out_pcm / d_pcm may be NULL: measure only.  Host version (needs no device: the definition): *stats is OVERWRITTEN.  Device
+ * version (asynchronous on `stream`): the call's statistics are MERGED into *d_stats -- device memory, 8-byte aligned, zeroed by the
+ * caller --, so a buffer converted in pieces, each with first_index advanced, accumulates the statistics of one call.  Unknown
+ * `bits` or `dither`, null `stats`: RSMP_ERR_INVALID_ARGUMENT, nothing written. */
+int rsmp_f32_to_pcm_stats(const float* in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
+                          void* out_pcm, rsmp_pcm_stats* stats);
+int rsmp_f32_to_pcm_stats_device(const float* d_in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
+                                 void* d_pcm, rsmp_pcm_stats* d_stats, void* stream);
 /* Measurement aid (no counterpart in the reference): a plain streaming copy of n_values floats, 16 bytes per lane --
  * the rate a kernel that reads as much as it writes can reach on this GPU; bench.py reports it next to every
  * roofline fraction.  16-byte aligned device pointers, n_values a multiple of 4, asynchronous on `stream`. */

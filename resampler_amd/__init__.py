@@ -89,6 +89,30 @@ class Dither(enum.IntEnum):
     TPDF = 1
 
 
+class PcmStats(C.Structure):
+    """What a PCM writer did to the values it was given (rsmp_pcm_stats, 32 bytes): how many it quantised, how many of them lay
+    outside the code range and were saturated, how many were NaN (stored as 0, not clipped), and the largest |x| of the others
+    before scaling and dither (+inf possible, 0.0 when there is none).  The rule is stated at rsmp_f32_to_pcm_stats."""
+    _fields_ = [("values", C.c_uint64), ("clipped", C.c_uint64), ("nans", C.c_uint64), ("peak", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_tuple(self) -> Tuple[int, int, int, float]:
+        return int(self.values), int(self.clipped), int(self.nans), float(self.peak)
+
+    def merged(self, other: "PcmStats") -> "PcmStats":
+        """Two sets merge field by field: the counts add, the peak is the larger one."""
+        return PcmStats(self.values + other.values, self.clipped + other.clipped, self.nans + other.nans, max(self.peak, other.peak), 0)
+
+    @classmethod
+    def from_tensor(cls, t) -> "PcmStats":
+        """The 32 bytes of a device accumulator (f32_to_pcm_stats_device's d_stats: any torch tensor of 32 bytes); synchronises."""
+        raw = t.detach().cpu().contiguous().view(-1).numpy().tobytes()
+        assert len(raw) == C.sizeof(cls), len(raw)
+        return cls.from_buffer_copy(raw)
+
+    def __repr__(self) -> str:
+        return "PcmStats(values=%d, clipped=%d, nans=%d, peak=%r)" % self.as_tuple()
+
+
 RSMP_OK = 0
 _U64 = 0xFFFFFFFFFFFFFFFF
 _f32p = C.POINTER(C.c_float)
@@ -122,6 +146,9 @@ _SIGNATURES = [
     ("rsmp_fir_set_profiling", C.c_int, [C.c_void_p, C.c_int]),
     ("rsmp_fir_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("rsmp_fir_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("rsmp_fir_set_pcm_stats", C.c_int, [C.c_void_p, C.c_int]),
+    ("rsmp_fir_pcm_stats", C.c_int, [C.c_void_p, C.POINTER(PcmStats)]),
+    ("rsmp_fir_pcm_stats_clear", C.c_int, [C.c_void_p]),
     ("rsmp_fir_last_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rsmp_fir_mean_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float), _szp]),
     ("rsmp_fir_kernel_variant", C.c_int, [C.c_void_p]),
@@ -190,6 +217,8 @@ _SIGNATURES = [
     ("rsmp_f32_to_pcm_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     ("rsmp_f32_to_pcm_dither", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("rsmp_f32_to_pcm_dither_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("rsmp_f32_to_pcm_stats", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(PcmStats)]),
+    ("rsmp_f32_to_pcm_stats_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rsmp_device_stream_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rsmp_fft_new", C.c_void_p, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     ("rsmp_fft_free", None, [C.c_void_p]),
@@ -402,6 +431,24 @@ class ResamplerFir:
         d, sd = C.c_int(), C.c_uint64()
         _check(lib().rsmp_fir_pcm_dither(self._h, C.byref(d), C.byref(sd)))
         return d.value, sd.value
+
+    def set_pcm_stats(self, enable: bool) -> None:
+        """Statistics of the PCM that FirBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fir_set_pcm_stats): off by
+        default; a setting, reset() and seek() leave it.  With it on the launches count every value they store -- the bytes do not
+        change -- and pcm_stats() reads the totals.  One setting for all the streams of a batch."""
+        _check(lib().rsmp_fir_set_pcm_stats(self._h, 1 if enable else 0))
+
+    def pcm_stats(self) -> PcmStats:
+        """Totals of every PCM-output launch of this handle since it was made, last reset() or last pcm_stats_clear() (rsmp_fir_pcm_stats:
+        waits for the handle's last launch): f32_to_pcm_stats' of the f32 output with the handle's dither, seed and first_index =
+        frames produced before * channels.  All zero with the setting off."""
+        st = PcmStats()
+        _check(lib().rsmp_fir_pcm_stats(self._h, C.byref(st)))
+        return st
+
+    def pcm_stats_clear(self) -> None:
+        """Zeroes the totals (rsmp_fir_pcm_stats_clear): ordered like a launch of the handle, enqueues nothing."""
+        _check(lib().rsmp_fir_pcm_stats_clear(self._h))
 
     def last_kernel_ms(self) -> float:
         ms = C.c_float()
@@ -919,6 +966,32 @@ def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None, dith
     else:
         _check(lib().rsmp_f32_to_pcm_dither_device(C.c_void_p(_dev_ptr(d_in)), n, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
                                                    C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
+
+
+def f32_to_pcm_stats(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, want_pcm: bool = True):
+    """f32_to_pcm that also says what it did (rsmp_f32_to_pcm_stats, host, no device needed: the definition of the statistics):
+    returns (bytes, PcmStats) -- the bytes are f32_to_pcm's with the same arguments; (None, PcmStats) with want_pcm = False
+    (out_pcm = NULL: measure only)."""
+    a = _np_f32(x).reshape(-1)
+    out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8) if want_pcm else None
+    st = PcmStats()
+    _check(lib().rsmp_f32_to_pcm_stats(C.c_void_p(a.ctypes.data), a.size, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                       C.c_void_p(out.ctypes.data) if want_pcm else None, C.byref(st)))
+    return (out.tobytes() if want_pcm else None), st
+
+
+def f32_to_pcm_stats_device(d_in, bits: int, d_pcm, d_stats, stream: Optional[int] = None, dither: int = 0, seed: int = 0,
+                            first_index: int = 0) -> None:
+    """The same on HBM-resident torch tensors (rsmp_f32_to_pcm_stats_device): d_pcm as f32_to_pcm_device's, or None to measure only;
+    d_stats = a tensor of 32 bytes, 8-byte aligned, that the caller zeroed -- the call's statistics are MERGED into it, so a buffer
+    converted in pieces accumulates one result (PcmStats.from_tensor reads it)."""
+    n = d_in.numel()
+    if d_pcm is not None and bits in (16, 24, 32):
+        assert d_pcm.numel() >= n * (bits // 8)
+    assert d_stats.numel() * d_stats.element_size() >= C.sizeof(PcmStats)
+    _check(lib().rsmp_f32_to_pcm_stats_device(C.c_void_p(_dev_ptr(d_in)), n, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                              C.c_void_p(d_pcm.data_ptr()) if d_pcm is not None else None, C.c_void_p(d_stats.data_ptr()),
+                                              C.c_void_p(stream or 0)))
 
 
 def fft_plan_sizes(input_rate_hz: int, output_rate_hz: int):

@@ -10,6 +10,8 @@
 // Both are HBM-bound elementwise kernels: coalesced loads / stores, nothing to stage.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include <cmath>
 #include <cstdint>
 
@@ -138,6 +140,64 @@ __global__ __launch_bounds__(kThreads) void f32_to_pcm_tpdf_kernel(const float* 
         } else {
             o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
         }
+    }
+}
+
+// The same lanes, loads and stores, counted (fir_pcm_stat: the rule of rsmp_f32_to_pcm_stats), without or with TPDF dither; `out`
+// may be null: measure only.  A lane keeps its own sums; they are added up inside the wave, then inside the workgroup, and the
+// workgroup's first lane merges them into *stats with at most four atomics.
+template <int BITS, bool TPDF>
+__global__ __launch_bounds__(kThreads) void f32_to_pcm_stats_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, uint64_t n, uint64_t seed,
+                                                                    uint64_t first, rsmp_pcm_stats* __restrict__ stats) {
+    typedef float v4f_in __attribute__((ext_vector_type(4)));
+    const uint64_t n4 = n / 4, stride = static_cast<uint64_t>(gridDim.x) * kThreads;
+    rsmp::FirPcmStat mine{0, 0, 0, 0};
+    auto code = [&](float x, uint64_t k) {
+        const float d = TPDF ? rsmp::fir_pcm_dither(seed, first + k) : 0.0f;
+        return static_cast<uint32_t>(rsmp::fir_pcm_quantise_stat(x, BITS, d, mine));
+    };
+    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(kThreads) + threadIdx.x; i <= n4; i += stride) {
+        if (i == n4) {   // the 0 .. 3 values behind the last whole four
+            for (uint64_t k = 4 * n4; k < n; ++k) {
+                const int32_t q = static_cast<int32_t>(code(in[k], k));
+                if (out) rsmp::fir_pcm_store_code(out, BITS, k, q);
+            }
+            break;
+        }
+        const v4f_in x = reinterpret_cast<const v4f_in*>(in)[i];
+        const uint32_t q0 = code(x.x, 4 * i), q1 = code(x.y, 4 * i + 1), q2 = code(x.z, 4 * i + 2), q3 = code(x.w, 4 * i + 3);
+        if (!out) continue;
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + i * (BITS / 2));
+        if constexpr (BITS == 16) {
+            o[0] = (q0 & 0xFFFFu) | (q1 << 16);
+            o[1] = (q2 & 0xFFFFu) | (q3 << 16);
+        } else if constexpr (BITS == 24) {
+            o[0] = (q0 & 0xFFFFFFu) | (q1 << 24);
+            o[1] = ((q1 >> 8) & 0xFFFFu) | (q2 << 16);
+            o[2] = ((q2 >> 16) & 0xFFu) | (q3 << 8);
+        } else {
+            o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
+        }
+    }
+    // (a lane's counts stay far below 2^32: the grid has a lane per four values up to 8 workgroups a CU, and walks on from there)
+    __shared__ rsmp::FirPcmStat waves[kThreads / 64];
+    const rsmp::FirPcmStat w = rsmp::fir_stat_wave_sum(mine);
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long values = 0, clipped = 0, nans = 0;
+        uint32_t peak = 0;
+        for (int k = 0; k < kThreads / 64; ++k) {
+            values += waves[k].values;
+            clipped += waves[k].clipped;
+            nans += waves[k].nans;
+            peak = waves[k].peak > peak ? waves[k].peak : peak;
+        }
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit atomics on the counts");
+        if (values) (void)atomicAdd(reinterpret_cast<unsigned long long*>(&stats->values), values);
+        if (clipped) (void)atomicAdd(reinterpret_cast<unsigned long long*>(&stats->clipped), clipped);
+        if (nans) (void)atomicAdd(reinterpret_cast<unsigned long long*>(&stats->nans), nans);
+        if (peak) (void)atomicMax(reinterpret_cast<uint32_t*>(&stats->peak), peak);   // (the bit pattern of |x| orders non-negative floats and +inf)
     }
 }
 
@@ -288,6 +348,58 @@ extern "C" int rsmp_f32_to_pcm_dither_device(const float* d_in, size_t n_values,
     if (bits == 16) hipLaunchKernelGGL(f32_to_pcm_tpdf_kernel<16>, grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index);
     else if (bits == 24) hipLaunchKernelGGL(f32_to_pcm_tpdf_kernel<24>, grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index);
     else hipLaunchKernelGGL(f32_to_pcm_tpdf_kernel<32>, grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index);
+    RSMP_HIP_CHECK(hipGetLastError());
+    return RSMP_OK;
+}
+
+// The definition of the statistics, on the host (no device needed): what rsmp_f32_to_pcm_dither writes, and what it did.
+extern "C" int rsmp_f32_to_pcm_stats(const float* in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index, void* out_pcm,
+                                     rsmp_pcm_stats* stats) {
+    if ((bits != 16 && bits != 24 && bits != 32) || (dither != RSMP_DITHER_NONE && dither != RSMP_DITHER_TPDF) || !stats || (n_values != 0 && !in))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_stats: 16 / 24 / 32 bits, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, non-null input and statistics");
+    uint8_t* o = static_cast<uint8_t*>(out_pcm);
+    const size_t bytes = static_cast<size_t>(bits) / 8;
+    rsmp_pcm_stats t{};
+    uint32_t peak = 0;
+    for (size_t i = 0; i < n_values; ++i) {
+        rsmp::FirPcmStat one{0, 0, 0, peak};
+        const float d = dither == RSMP_DITHER_TPDF ? rsmp::fir_pcm_dither(seed, first_index + i) : 0.0f;
+        const uint32_t q = static_cast<uint32_t>(rsmp::fir_pcm_quantise_stat(in[i], static_cast<uint32_t>(bits), d, one));
+        t.values += one.values;
+        t.clipped += one.clipped;
+        t.nans += one.nans;
+        peak = one.peak;
+        if (o)
+            for (size_t b = 0; b < bytes; ++b) o[i * bytes + b] = static_cast<uint8_t>(q >> (8 * b));   // little-endian
+    }
+    std::memcpy(&t.peak, &peak, sizeof peak);
+    *stats = t;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_f32_to_pcm_stats_device(const float* d_in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
+                                            void* d_pcm, rsmp_pcm_stats* d_stats, void* stream) {
+    if ((bits != 16 && bits != 24 && bits != 32) || (dither != RSMP_DITHER_NONE && dither != RSMP_DITHER_TPDF) || !d_stats || (n_values != 0 && !d_in))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_stats_device: 16 / 24 / 32 bits, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, non-null input and statistics");
+    if (reinterpret_cast<uintptr_t>(d_in) % 16 != 0 || reinterpret_cast<uintptr_t>(d_pcm) % 4 != 0 || reinterpret_cast<uintptr_t>(d_stats) % 8 != 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_stats_device: d_in 16-byte aligned, d_pcm 4-byte aligned, d_stats 8-byte aligned");
+    if (int rc = check_device()) return rc;
+    if (n_values == 0) return RSMP_OK;
+    const dim3 grid = f32_to_pcm_grid(n_values);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* o = static_cast<uint8_t*>(d_pcm);
+    const uint64_t n = n_values;
+#define RSMP_STATS_LAUNCH(BITS, TPDF) hipLaunchKernelGGL((f32_to_pcm_stats_kernel<BITS, TPDF>), grid, dim3(kThreads), 0, s, d_in, o, n, seed, first_index, d_stats)
+    if (dither == RSMP_DITHER_TPDF) {
+        if (bits == 16) RSMP_STATS_LAUNCH(16, true);
+        else if (bits == 24) RSMP_STATS_LAUNCH(24, true);
+        else RSMP_STATS_LAUNCH(32, true);
+    } else {
+        if (bits == 16) RSMP_STATS_LAUNCH(16, false);
+        else if (bits == 24) RSMP_STATS_LAUNCH(24, false);
+        else RSMP_STATS_LAUNCH(32, false);
+    }
+#undef RSMP_STATS_LAUNCH
     RSMP_HIP_CHECK(hipGetLastError());
     return RSMP_OK;
 }

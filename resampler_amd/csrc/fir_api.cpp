@@ -391,10 +391,14 @@ extern "C" int rsmp_fir_seek(rsmp_fir* r, const rsmp_fir_plan* p, const float* h
 extern "C" void rsmp_fir_reset(rsmp_fir* r) {
     // resampler_fir.rs:638-642: only the three scalars; stale frames are unreachable.
     r->mirror.reset();
+    r->pcm_stats_cleared = true;   // (a new stream: its PCM statistics start again -- a flag, nothing is enqueued)
 }
 
 extern "C" void rsmp_fir_batch_reset(rsmp_fir* const* rs, size_t n) {
-    for (size_t i = 0; i < n; ++i) rs[i]->mirror.reset();
+    for (size_t i = 0; i < n; ++i) {
+        rs[i]->mirror.reset();
+        rs[i]->pcm_stats_cleared = true;
+    }
 }
 
 extern "C" int rsmp_fir_set_kernel(rsmp_fir* r, int kernel) {
@@ -417,6 +421,36 @@ extern "C" int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* see
     if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_dither: null handle");
     if (dither) *dither = r->pcm_dither;
     if (seed) *seed = r->pcm_dither_seed;
+    return RSMP_OK;
+}
+
+// PCM output's statistics: a setting of the handle like the dither; the totals live in device memory (fir_handle.h).
+extern "C" int rsmp_fir_set_pcm_stats(rsmp_fir* r, int enable) {
+    if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_set_pcm_stats: null handle");
+    if (enable && !r->d_pcm_stats.get()) {
+        DeviceGuard guard(r->device);
+        RSMP_HIP_CHECK(r->d_pcm_stats.reserve(sizeof(rsmp_pcm_stats)));
+        r->pcm_stats_cleared = true;   // (the first counting launch writes the totals: no memset)
+    }
+    r->pcm_stats = enable != 0;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fir_pcm_stats(rsmp_fir* r, rsmp_pcm_stats* stats) {
+    if (!r || !stats) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_stats: null argument");
+    rsmp_pcm_stats t{};
+    if (r->pcm_stats && !r->pcm_stats_cleared && r->d_pcm_stats.get()) {
+        DeviceGuard guard(r->device);
+        if (r->last_launch) RSMP_HIP_CHECK(hipEventSynchronize(r->last_launch->ev));
+        RSMP_HIP_CHECK(hipMemcpy(&t, r->d_pcm_stats.get(), sizeof t, hipMemcpyDeviceToHost));
+    }
+    *stats = t;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fir_pcm_stats_clear(rsmp_fir* r) {
+    if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_stats_clear: null handle");
+    r->pcm_stats_cleared = true;
     return RSMP_OK;
 }
 
@@ -653,6 +687,8 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
 // Handles set to RSMP_DITHER_TPDF (rsmp_fir_set_pcm_dither; all of a batch or none: launch_jobs refuses a mix) add their noise at
 // the same sites, value (frame n of the launch, channel c) with index (abs_out + n) * channels + c -- rsmp_f32_to_pcm_dither_device's
 // bytes with the handle's seed and first_index = abs_out * channels.
+// Handles set to count (rsmp_fir_set_pcm_stats; all of a batch or none) take the kernels' counting builds: the same bytes, and
+// rsmp_f32_to_pcm_stats's statistics of them in the handles' totals.
 extern "C" int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                            const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
                                                            const size_t* out_caps, size_t* consumed, size_t* produced, void* stream) {

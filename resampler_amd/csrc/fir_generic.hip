@@ -45,8 +45,9 @@ __device__ __forceinline__ float load_sample(const FirStreamDesc& d, int64_t v, 
 // (the job of fir_tail_copy_kernel: a second launch is a fifth of a streaming call's latency).
 // OUT (FirOut): the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes (fir_pcm_store), with or
 // without TPDF dither (fir_out_store).
+// kFirOutPcmStats: every stored value is also counted into its chunk's entry of st.table (a tile of kFirTile frames lies in one chunk).
 template <int OUT>
-__device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
+__device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail, const FirStatArgs& st = FirStatArgs{}) {
     const FirStreamDesc d = descs[blockIdx.y];
     const uint32_t tile = blockIdx.x;
     const uint32_t tile_first = tile * kFirTile;
@@ -61,6 +62,7 @@ __device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict
     }
     if (tile_first >= d.n_out) return;
 
+    FirPcmStat stat{0, 0, 0, 0};   // (counting builds: what this lane stored)
     const int g = threadIdx.x & (kLanesPerFrame - 1);
     const int slot = threadIdx.x / kLanesPerFrame;
     const uint32_t taps = d.taps;
@@ -125,8 +127,18 @@ __device__ __forceinline__ void fir_generic_body(const FirStreamDesc* __restrict
             // per-lane lerp, then horizontal sum (avx.rs:41-58)
             const float part = a1 * one_minus_frac + a2 * frac;
             const float y = group_sum8(part);
-            if (live && g == 0) fir_out_store<OUT>(d, static_cast<size_t>(n) * channels + c, y);
+            if constexpr (OUT == kFirOutPcmStats) {
+                if (live && g == 0) fir_out_store_stat(d, static_cast<size_t>(n) * channels + c, y, stat);
+            } else {
+                if (live && g == 0) fir_out_store<OUT>(d, static_cast<size_t>(n) * channels + c, y);
+            }
         }
+    }
+    if constexpr (OUT == kFirOutPcmStats) {   // (every lane of the workgroup arrives here)
+        static_assert((1u << kNfChunkShift) % kFirTile == 0, "a tile lies in one chunk");
+        const FirPcmStat w = fir_stat_wave_sum(stat);
+        if ((threadIdx.x & 63) == 0)
+            fir_stat_atomic_merge(st.table + (static_cast<size_t>(blockIdx.y) * st.chunks + (tile_first >> kNfChunkShift)) * 4, w);
     }
 }
 
@@ -138,6 +150,9 @@ __global__ __launch_bounds__(kBlock) void fir_generic_pcm_out_kernel(const FirSt
 }
 __global__ __launch_bounds__(kBlock) void fir_generic_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail) {
     fir_generic_body<kFirOutPcmTpdf>(descs, fuse_tail);
+}
+__global__ __launch_bounds__(kBlock) void fir_generic_pcm_stats_kernel(const FirStreamDesc* __restrict__ descs, uint32_t fuse_tail, FirStatArgs st) {
+    fir_generic_body<kFirOutPcmStats>(descs, fuse_tail, st);
 }
 
 __global__ __launch_bounds__(kBlock) void fir_tail_copy_kernel(const FirStreamDesc* __restrict__ descs) {
@@ -159,8 +174,11 @@ __global__ __launch_bounds__(kBlock) void fir_tail_copy_kernel(const FirStreamDe
 // (resampler_fir.rs:544, :562-565).
 // OUT (FirOut): the marked chunks lie in a PCM buffer (FirStreamDesc::out_bits) and are rewritten as PCM -- dithered launches with
 // the noise the first pass gave them: it depends on the seed and the value's index alone.
+// kFirOutPcmStats: what the first pass counted for a marked chunk is void -- the chunk's workgroup (each marked chunk has exactly
+// one) counts the values it stores and overwrites the chunk's entry of st.table.
 template <int OUT>
-__device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict__ descs, uint32_t n_streams, const NfArgs& nf) {
+__device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict__ descs, uint32_t n_streams, const NfArgs& nf,
+                                                const FirStatArgs& st = FirStatArgs{}) {
     if (__hip_atomic_load(nf.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nf.tag) return;
     const int g = threadIdx.x & (kLanesPerFrame - 1);
     const uint32_t slot = threadIdx.x / kLanesPerFrame;
@@ -173,6 +191,7 @@ __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict_
         const uint32_t n_begin = chunk << kNfChunkShift;
         const uint32_t n_end = n_begin + (1u << kNfChunkShift) < d.n_out ? n_begin + (1u << kNfChunkShift) : d.n_out;
         const uint32_t taps = d.taps, channels = d.channels;
+        FirPcmStat stat{0, 0, 0, 0};   // (counting builds: what this lane stored of the chunk)
         for (uint32_t base = n_begin; base < n_end; base += kFramesPerPass) {
             const uint32_t n = base + slot;
             const bool live = n < n_end;
@@ -222,7 +241,24 @@ __device__ __forceinline__ void fir_repair_body(const FirStreamDesc* __restrict_
                 }
                 const float part = a1 * one_minus_frac + a2 * frac;
                 const float y = group_sum8(part);
-                if (live && g == 0) fir_out_store<OUT>(d, static_cast<size_t>(n) * channels + c, y);
+                if constexpr (OUT == kFirOutPcmStats) {
+                    if (live && g == 0) fir_out_store_stat(d, static_cast<size_t>(n) * channels + c, y, stat);
+                } else {
+                    if (live && g == 0) fir_out_store<OUT>(d, static_cast<size_t>(n) * channels + c, y);
+                }
+            }
+        }
+        if constexpr (OUT == kFirOutPcmStats) {
+            __shared__ FirPcmStat wave_stats[kBlock / 64];
+            const FirPcmStat w = fir_stat_wave_sum(stat);
+            __syncthreads();   // (the previous chunk's sums have been read)
+            if ((threadIdx.x & 63) == 0) wave_stats[threadIdx.x >> 6] = w;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                FirPcmStat t = wave_stats[0];
+                for (int k = 1; k < kBlock / 64; ++k) fir_pcm_stat_merge(t, wave_stats[k]);
+                uint32_t* e = st.table + (static_cast<size_t>(s) * st.chunks + chunk) * 4;   // a plain store: the entry is this workgroup's alone
+                e[0] = t.values; e[1] = t.clipped; e[2] = t.nans; e[3] = t.peak;
             }
         }
         __syncthreads();
@@ -241,6 +277,10 @@ __global__ __launch_bounds__(kBlock) void fir_repair_pcm_tpdf_kernel(const FirSt
                                                                      uint32_t n_streams, NfArgs nf) {
     fir_repair_body<kFirOutPcmTpdf>(descs, n_streams, nf);
 }
+__global__ __launch_bounds__(kBlock) void fir_repair_pcm_stats_kernel(const FirStreamDesc* __restrict__ descs,
+                                                                      uint32_t n_streams, NfArgs nf, FirStatArgs st) {
+    fir_repair_body<kFirOutPcmStats>(descs, n_streams, nf, st);
+}
 struct RepairMulti {
     const FirStreamDesc* descs[kMaxRepairJobs];
     uint32_t n_streams[kMaxRepairJobs];
@@ -250,8 +290,12 @@ struct RepairMulti {
     const FirStreamDesc* tail_descs;
     uint32_t n_tail, n_jobs;
 };
+struct RepairStatTables {   // counting builds: job j's part of the launch's table (the jobs share its `chunks`)
+    uint32_t* table[kMaxRepairJobs];
+    uint32_t chunks;
+};
 template <int OUT>
-__device__ __forceinline__ void fir_repair_multi_body(const RepairMulti& m) {   // grid = (blocks, jobs [+ 1])
+__device__ __forceinline__ void fir_repair_multi_body(const RepairMulti& m, const RepairStatTables* st = nullptr) {   // grid = (blocks, jobs [+ 1])
     if (blockIdx.y >= m.n_jobs) {   // the tail row: a workgroup per stream, round the row
         for (uint32_t s = blockIdx.x; s < m.n_tail; s += gridDim.x) {
             const FirStreamDesc d = m.tail_descs[s];
@@ -265,18 +309,82 @@ __device__ __forceinline__ void fir_repair_multi_body(const RepairMulti& m) {   
         }
         return;
     }
-    fir_repair_body<OUT>(m.descs[blockIdx.y], m.n_streams[blockIdx.y], m.nf[blockIdx.y]);
+    if constexpr (OUT == kFirOutPcmStats)
+        fir_repair_body<OUT>(m.descs[blockIdx.y], m.n_streams[blockIdx.y], m.nf[blockIdx.y], FirStatArgs{st->table[blockIdx.y], st->chunks});
+    else
+        fir_repair_body<OUT>(m.descs[blockIdx.y], m.n_streams[blockIdx.y], m.nf[blockIdx.y]);
 }
 __global__ __launch_bounds__(kBlock) void fir_repair_multi_kernel(const RepairMulti m) { fir_repair_multi_body<kFirOutF32>(m); }
 __global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_out_kernel(const RepairMulti m) { fir_repair_multi_body<kFirOutPcm>(m); }
 __global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_tpdf_kernel(const RepairMulti m) { fir_repair_multi_body<kFirOutPcmTpdf>(m); }
+__global__ __launch_bounds__(kBlock) void fir_repair_multi_pcm_stats_kernel(const RepairMulti m, const RepairStatTables st) {
+    fir_repair_multi_body<kFirOutPcmStats>(m, &st);
+}
+
+// Behind a counting launch's repair pass: workgroup s sums stream s's chunk entries and merges them into the stream's totals
+// (targets[s].acc, the handle's 32 bytes of device memory) -- or, where the handle's totals were cleared since its last launch
+// (targets[s].overwrite), replaces them: a clear is ordered on the stream like any launch, and costs none of its own.
+__global__ __launch_bounds__(kBlock) void fir_pcm_stats_fold_kernel(const uint32_t* __restrict__ table, uint32_t chunks,
+                                                                    const FirStatTarget* __restrict__ targets) {
+    __shared__ unsigned long long sums[kBlock / 64][3];
+    __shared__ uint32_t peaks[kBlock / 64];
+    const uint32_t* e = table + static_cast<size_t>(blockIdx.x) * chunks * 4;
+    unsigned long long v = 0, c = 0, n = 0;
+    uint32_t p = 0;
+    for (uint32_t k = threadIdx.x; k < chunks; k += kBlock) {
+        v += e[4 * k];
+        c += e[4 * k + 1];
+        n += e[4 * k + 2];
+        p = e[4 * k + 3] > p ? e[4 * k + 3] : p;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        v += __shfl_xor(v, m, 64);
+        c += __shfl_xor(c, m, 64);
+        n += __shfl_xor(n, m, 64);
+        const uint32_t q = __shfl_xor(p, m, 64);
+        p = q > p ? q : p;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sums[threadIdx.x >> 6][0] = v;
+        sums[threadIdx.x >> 6][1] = c;
+        sums[threadIdx.x >> 6][2] = n;
+        peaks[threadIdx.x >> 6] = p;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kBlock / 64; ++k) {
+            v += sums[k][0];
+            c += sums[k][1];
+            n += sums[k][2];
+            p = peaks[k] > p ? peaks[k] : p;
+        }
+        const FirStatTarget t = targets[blockIdx.x];
+        uint32_t* peak = reinterpret_cast<uint32_t*>(&t.acc->peak);
+        if (!t.overwrite) {   // (the handle's launches are ordered: nobody else writes its totals meanwhile)
+            v += t.acc->values;
+            c += t.acc->clipped;
+            n += t.acc->nans;
+            p = *peak > p ? *peak : p;
+        }
+        t.acc->values = v;
+        t.acc->clipped = c;
+        t.acc->nans = n;
+        *peak = p;
+        t.acc->reserved = 0;
+    }
+}
 
 }  // namespace
 
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done, bool* done_attached, uint32_t out_bits, uint32_t dither) {
+                             hipEvent_t done, bool* done_attached, uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
     if (n_streams == 0 || !nf.words || nf.chunks == 0) return hipSuccess;
     const uint32_t total = n_streams * nf.chunks;
+    if (st && st->table && out_bits != 0) {   // the counting build (never the last launch: the fold follows)
+        hipLaunchKernelGGL(fir_repair_pcm_stats_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf, *st);
+        return hipGetLastError();
+    }
     const FirOut mode = fir_out_mode(out_bits, dither);
     const auto kernel = mode == kFirOutPcmTpdf ? fir_repair_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_repair_pcm_out_kernel : fir_repair_kernel;
     if (done && done_attached) {
@@ -291,19 +399,22 @@ hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, c
 
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs,
                                    uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached, uint32_t out_bits,
-                                   uint32_t dither) {
+                                   uint32_t dither, const FirStatArgs* st) {
     if (done_attached) *done_attached = false;
+    const bool counting = st && st->table && out_bits != 0;   // RepairJob::stat_first places each job in the launch's table
     const FirOut mode = fir_out_mode(out_bits, dither);
     const auto kernel = mode == kFirOutPcmTpdf ? fir_repair_multi_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_repair_multi_pcm_out_kernel : fir_repair_multi_kernel;
     bool tail_left = tail_descs != nullptr && n_tail != 0 && max_tail_values != 0;
     for (size_t j = 0; j < n_jobs;) {
         RepairMulti m{};
+        RepairStatTables tables{};
         uint32_t n = 0, max_total = 0;
         for (; j < n_jobs && n < kMaxRepairJobs; ++j) {
             if (jobs[j].n_streams == 0 || !jobs[j].nf.words || jobs[j].nf.chunks == 0) continue;
             m.descs[n] = jobs[j].d_descs;
             m.n_streams[n] = jobs[j].n_streams;
             m.nf[n] = jobs[j].nf;
+            if (counting) tables.table[n] = st->table + static_cast<size_t>(jobs[j].stat_first) * st->chunks * 4;
             max_total = std::max(max_total, jobs[j].n_streams * jobs[j].nf.chunks);
             ++n;
         }
@@ -317,6 +428,12 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
             max_total = std::max(max_total, n_tail);
         }
         const dim3 grid(max_total < 512 ? max_total : 512, n + (with_tail ? 1u : 0u));
+        if (counting) {
+            tables.chunks = st->chunks;
+            hipLaunchKernelGGL(fir_repair_multi_pcm_stats_kernel, grid, dim3(kBlock), 0, stream, m, tables);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+            continue;
+        }
         if (done && done_attached && j >= n_jobs && !tail_left) {   // (the last launch of the lot: it completes `done` itself)
             hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, nullptr, done, 0, m);
             *done_attached = true;
@@ -330,12 +447,31 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
 }
 
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, uint32_t out_bits, uint32_t dither) {
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, uint32_t out_bits, uint32_t dither,
+                              const FirStatArgs* st) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
     const uint32_t cz = (max_channels + kChannelsPerBlock - 1) / kChannelsPerBlock;
     const dim3 grid((max_out + kFirTile - 1) / kFirTile, n_streams, cz ? cz : 1);
+    if (st && st->table && out_bits != 0) {
+        hipLaunchKernelGGL(fir_generic_pcm_stats_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u, *st);
+        return hipGetLastError();
+    }
     const FirOut mode = fir_out_mode(out_bits, dither);
     hipLaunchKernelGGL(mode == kFirOutPcmTpdf ? fir_generic_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_generic_pcm_out_kernel : fir_generic_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_fir_pcm_stats_fold(const FirStatArgs& st, uint32_t n_streams, const FirStatTarget* d_targets, hipStream_t stream,
+                                     hipEvent_t done, bool* done_attached) {
+    if (n_streams == 0 || !st.table) return hipSuccess;
+    if (done && done_attached) {
+        hipExtLaunchKernelGGL(fir_pcm_stats_fold_kernel, dim3(n_streams), dim3(kBlock), 0, stream, nullptr, done, 0,
+                              static_cast<const uint32_t*>(st.table), st.chunks, d_targets);
+        *done_attached = true;
+    } else {
+        hipLaunchKernelGGL(fir_pcm_stats_fold_kernel, dim3(n_streams), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(st.table), st.chunks,
+                           d_targets);
+    }
     return hipGetLastError();
 }
 

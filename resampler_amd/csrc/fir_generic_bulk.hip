@@ -96,9 +96,12 @@ struct BulkPass {
 
 // OUT (FirOut): the streams' `out` is PCM (FirStreamDesc::out_bits), each value quantised into its own bytes, with or without TPDF
 // dither (fir_out_store).
+// kFirOutPcmStats: every stored value is also counted, into `tile_stats` (LDS): four words per chunk of the tile, the first being
+// the chunk of frame n0 -- outputs leave in phase order, so neighbouring lanes' frames lie in any of the tile's chunks.
 template <int CH, bool FULL, int OUT>   // FULL: 128 taps (every lane's four chunks exist: no tests, every LDS offset an immediate)
 __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkMeta* meta, const uint16_t* sorted, const float* win, uint32_t n0,
-                                             uint32_t nt, uint32_t lane, uint32_t wave) {
+                                             uint32_t nt, uint32_t lane, uint32_t wave, uint32_t* tile_stats = nullptr) {
+    static_assert(OUT != kFirOutPcmStats || CH == 2, "counted PCM output: the entry admits two-channel streams only");
     const uint32_t ch = CH ? static_cast<uint32_t>(CH) : d.channels, taps = d.taps;
     const uint32_t g = lane & 7u, slot = lane >> 3;
     const uint32_t per_wave = ((nt + 15u) / 16u + 7u) & ~7u;   // (a multiple of eight: a wave's passes are whole)
@@ -108,12 +111,21 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
     const uint32_t chunks = FULL ? 32u : taps / 4;   // float4 chunks per row (4 .. 32); lane g owns g, g + 8, g + 16, g + 24
     const GRow coeffs = (GRow)d.coeffs;
     const GOut out = (GOut)d.out;
-    auto store1 = [&](size_t i, float y) {
-        if constexpr (OUT != kFirOutF32) fir_out_store<OUT>(d, i, y);
+    auto store1 = [&](size_t i, float y) {   // (i = frame * ch + channel)
+        if constexpr (OUT == kFirOutPcmStats) {
+            FirPcmStat f{0, 0, 0, 0};
+            fir_out_store_stat(d, i, y, f);
+            fir_stat_atomic_merge(tile_stats + ((static_cast<uint32_t>(i / ch) >> kNfChunkShift) - (n0 >> kNfChunkShift)) * 4, f);
+        } else if constexpr (OUT != kFirOutF32) fir_out_store<OUT>(d, i, y);
         else out[i] = y;
     };
     auto store2 = [&](size_t i, float y0, float y1) {   // (two channels: i even)
-        if constexpr (OUT != kFirOutF32) {
+        if constexpr (OUT == kFirOutPcmStats) {
+            FirPcmStat f{0, 0, 0, 0};
+            fir_out_store_stat(d, i, y0, f);
+            fir_out_store_stat(d, i + 1, y1, f);
+            fir_stat_atomic_merge(tile_stats + ((static_cast<uint32_t>(i >> 1) >> kNfChunkShift) - (n0 >> kNfChunkShift)) * 4, f);
+        } else if constexpr (OUT != kFirOutF32) {
             fir_out_store<OUT>(d, i, y0);
             fir_out_store<OUT>(d, i + 1, y1);
         } else {
@@ -223,7 +235,8 @@ __device__ __forceinline__ void bulk_outputs(const FirStreamDesc& d, const BulkM
 // CH: 1 / 2 = every stream of the launch has that many channels; 0 = any counts (a kernel each: side by side in one kernel the three
 // bodies shared a register allocation and spilled)
 template <int CH, bool FULL, int OUT>
-__device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames, uint32_t window_cap_frames) {
+__device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames, uint32_t window_cap_frames,
+                                                      const FirStatArgs& st = FirStatArgs{}) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const FirStreamDesc d = descs[blockIdx.y];
     const uint32_t n0 = blockIdx.x * tile_frames;
@@ -328,7 +341,24 @@ __device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __res
     __syncthreads();
 
     // ---- D: the outputs in phase order, a contiguous stretch of the list per wave, eight lanes per output frame
-    bulk_outputs<CH, FULL, OUT>(d, meta, sorted, win, n0, nt, lane, wave);
+    if constexpr (OUT == kFirOutPcmStats) {
+        // the tile's statistics in the LDS the scatter's cursors had (`counts`, free now): an entry per chunk the tile touches -- at
+        // most kBulkTileMax / 1024 + 1 --, merged into the stream's row of the launch's table once the tile is done
+        constexpr uint32_t kTileChunks = (kBulkTileMax >> kNfChunkShift) + 1;
+        static_assert(4 * kTileChunks <= kRows, "the tile's statistics fit the cursors' space");
+        if (tid < 4 * kTileChunks) counts[tid] = 0;
+        __syncthreads();
+        bulk_outputs<CH, FULL, OUT>(d, meta, sorted, win, n0, nt, lane, wave, counts);
+        __syncthreads();
+        const uint32_t c0 = n0 >> kNfChunkShift, n_chunks = ((n0 + nt - 1) >> kNfChunkShift) - c0 + 1;
+        if (tid < 4 * n_chunks && counts[tid] != 0) {
+            uint32_t* e = st.table + (static_cast<size_t>(blockIdx.y) * st.chunks + c0) * 4 + tid;
+            if ((tid & 3u) == 3u) (void)atomicMax(e, counts[tid]);
+            else (void)atomicAdd(e, counts[tid]);
+        }
+    } else {
+        bulk_outputs<CH, FULL, OUT>(d, meta, sorted, win, n0, nt, lane, wave);
+    }
 }
 template <int CH, bool FULL>
 __global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
@@ -345,6 +375,11 @@ template <bool FULL>
 __global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
                                                                                uint32_t window_cap_frames) {
     fir_generic_bulk_body<2, FULL, kFirOutPcmTpdf>(descs, tile_frames, window_cap_frames);
+}
+template <bool FULL>
+__global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_pcm_stats_kernel(const FirStreamDesc* __restrict__ descs, uint32_t tile_frames,
+                                                                                uint32_t window_cap_frames, FirStatArgs st) {
+    fir_generic_bulk_body<2, FULL, kFirOutPcmStats>(descs, tile_frames, window_cap_frames, st);
 }
 
 }  // namespace
@@ -364,7 +399,7 @@ uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double 
 
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels, uint32_t uniform_taps,
-                                   uint32_t out_bits, uint32_t dither) {
+                                   uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
     if (out_bits != 0 && uniform_channels != 2) return hipErrorNotSupported;
     const uint32_t tile = fir_generic_bulk_tile(max_channels, max_taps, max_ratio);
@@ -382,10 +417,13 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
                                                reinterpret_cast<const void*>(fir_generic_bulk_pcm_out_kernel<true>)};
     static const void* const fns_pcm_tpdf[2] = {reinterpret_cast<const void*>(fir_generic_bulk_pcm_tpdf_kernel<false>),
                                                 reinterpret_cast<const void*>(fir_generic_bulk_pcm_tpdf_kernel<true>)};
-    const FirOut mode = fir_out_mode(out_bits, dither);
-    const void* fn = mode == kFirOutPcmTpdf ? fns_pcm_tpdf[full ? 1 : 0] : mode == kFirOutPcm ? fns_pcm_out[full ? 1 : 0] : fns[ci][full ? 1 : 0];
-    static bool granted[5][2] = {};   // (the attribute is per function and process: set once)
-    bool& have = granted[mode == kFirOutPcmTpdf ? 4 : mode == kFirOutPcm ? 3 : ci][full ? 1 : 0];
+    static const void* const fns_pcm_stats[2] = {reinterpret_cast<const void*>(fir_generic_bulk_pcm_stats_kernel<false>),
+                                                 reinterpret_cast<const void*>(fir_generic_bulk_pcm_stats_kernel<true>)};
+    const FirOut mode = fir_out_mode(out_bits, dither, st != nullptr && st->table != nullptr);
+    const void* fn = mode == kFirOutPcmStats ? fns_pcm_stats[full ? 1 : 0]
+                     : mode == kFirOutPcmTpdf ? fns_pcm_tpdf[full ? 1 : 0] : mode == kFirOutPcm ? fns_pcm_out[full ? 1 : 0] : fns[ci][full ? 1 : 0];
+    static bool granted[6][2] = {};   // (the attribute is per function and process: set once)
+    bool& have = granted[mode == kFirOutPcmStats ? 5 : mode == kFirOutPcmTpdf ? 4 : mode == kFirOutPcm ? 3 : ci][full ? 1 : 0];
     if (!have) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -393,7 +431,8 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
     }
     const dim3 grid((max_out + tile - 1) / tile, n_streams);
     uint32_t tile_arg = tile, cap_arg = cap;
-    void* kargs[3] = {&d_descs, &tile_arg, &cap_arg};
+    FirStatArgs st_arg = mode == kFirOutPcmStats ? *st : FirStatArgs{nullptr, 0};
+    void* kargs[4] = {&d_descs, &tile_arg, &cap_arg, &st_arg};   // (the counting builds alone take the fourth)
     if (hipError_t e = hipLaunchKernel(fn, grid, dim3(kBulkBlock), kargs, lds, stream); e != hipSuccess) return e;
     return hipGetLastError();
 }

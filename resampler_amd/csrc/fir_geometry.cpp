@@ -293,14 +293,15 @@ void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_ou
 // for any other geometry (the caller converts with rsmp_pcm_to_stereo_f32_device first).
 // PCM output (FirStreamDesc::out_bits): the same three windows, from f32 or PCM input, as builds of their own that read the
 // width from the descriptor; kNotSupported for any other geometry (the caller converts with rsmp_f32_to_pcm_device afterwards).
-// dither != 0 (FirStreamDesc::dither): their twins that add TPDF dither.
-SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither) {
+// dither != 0 (FirStreamDesc::dither): their twins that add TPDF dither.  stats: their twins that count what they store, with or
+// without dither (one build for both: a uniform branch).
+SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither, bool stats) {
     const bool one_channel = geo.cg == 1, odd_count = geo.cg == 3;
     const bool wide = geo.lp > 1 || one_channel;
     const bool two_rounds = geo.rounds == 2;
     const int nk = static_cast<int>(geo.row_len / 32);
     const bool diag_long = two_rounds && diag && (nk == 6 || (nk == 5 && !wide));
-    SplitBuild b{nk, 2, false, 0, two_rounds ? 2 : 1, 0, false, false};
+    SplitBuild b{nk, 2, false, 0, two_rounds ? 2 : 1, 0, false, false, false};
     if (two_rounds) {
         b.wide = wide ? 1 : 0;
         b.diag = diag_long;
@@ -318,7 +319,8 @@ SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm
         if (wide || one_channel || odd_count || geo.planes != 2 || diag || !window_ok || (pcm_bits != 0 && !width_ok(pcm_bits)) ||
             (out_bits != 0 && !width_ok(out_bits)))
             return {b, BuildError::kNotSupported};
-        b = SplitBuild{nk, 2, false, 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, out_bits != 0 && dither != 0};
+        const bool counted = out_bits != 0 && stats;
+        b = SplitBuild{nk, 2, false, 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, out_bits != 0 && dither != 0 && !counted, counted};
     }
     return {b, BuildError::kNone};
 }

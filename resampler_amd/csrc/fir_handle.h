@@ -64,6 +64,14 @@ struct rsmp_fir {
     // A setting, not state: reset and seek leave it alone; the noise counter is the mirror's abs_out.
     int pcm_dither = RSMP_DITHER_NONE;
     uint64_t pcm_dither_seed = 0;
+    // ... and its statistics (rsmp_fir_set_pcm_stats): the setting -- reset and seek leave it -- and the handle's totals, one
+    // rsmp_pcm_stats in device memory that the fold kernel behind every counting launch merges into.  pcm_stats_cleared: the totals
+    // are zero whatever the memory holds (a new handle, reset, rsmp_fir_pcm_stats_clear): the next counting launch replaces them.
+    // Nothing is enqueued by a clear, and a handle with the setting off has neither buffer.
+    bool pcm_stats = false;
+    bool pcm_stats_cleared = true;
+    rsmp::DeviceBuffer d_pcm_stats;
+    rsmp::DeviceBuffer d_stat_table;   // a counting launch's per-chunk table (FirStatArgs, fir_kernels.h; leader only)
 
     rsmp_fir(uint32_t i, uint32_t o, size_t t) : mirror(i, o, t) {}
 };

@@ -115,6 +115,82 @@ __host__ __device__ __forceinline__ float fir_pcm_dither(uint64_t seed, uint64_t
 __host__ __device__ __forceinline__ int32_t fir_pcm_quantise_dither(float x, uint32_t bits, float d) {
     return fir_pcm_code(rintf(x * fir_pcm_scale(bits) + d), bits);
 }
+// What the quantiser did to the values it was given (rsmp_pcm_stats, include/resampler_amd.h): THE definition, every site that
+// counts calls fir_pcm_stat.  x: the value before scaling; v: the quantiser's own rounded value, rintf(x * 2^(bits-1) + d).
+//   values  every value;   nans  x is NaN (stored as 0, not clipped);
+//   clipped v is not NaN and outside the code range: v > 2^(bits-1) - 1 or v < -2^(bits-1) -- at 32 bits, whose top code is no
+//           f32 value, v >= 2^31 or v < -2^31.  +-inf clip, +1.0 clips, -1.0 does not;
+//   peak    the largest |x| among the values that are not NaN, as its bit pattern (which orders non-negative floats and +inf as
+//           unsigned integers): before scaling, before dither; 0 when there is none.
+// Two sets merge field by field (sums, max), so no field depends on the order of evaluation.  The counters of a launch's table
+// are 32 bits (a 1024-frame chunk holds 2048 values), the public totals 64.
+struct FirPcmStat {
+    uint32_t values, clipped, nans, peak;
+};
+__host__ __device__ __forceinline__ void fir_pcm_stat(float x, float v, uint32_t bits, FirPcmStat& s) {
+    ++s.values;
+    if (!(x == x)) {
+        ++s.nans;
+        return;
+    }
+    if (v == v) {
+        if (bits == 32) s.clipped += (v >= 2147483648.0f || v < -2147483648.0f) ? 1u : 0u;
+        else s.clipped += (v > (bits == 16 ? 32767.0f : 8388607.0f) || v < (bits == 16 ? -32768.0f : -8388608.0f)) ? 1u : 0u;
+    }
+    union { float f; uint32_t u; } a;
+    a.f = x;
+    const uint32_t m = a.u & 0x7FFFFFFFu;   // |x|
+    if (m > s.peak) s.peak = m;
+}
+__host__ __device__ __forceinline__ void fir_pcm_stat_merge(FirPcmStat& s, const FirPcmStat& o) {
+    s.values += o.values;
+    s.clipped += o.clipped;
+    s.nans += o.nans;
+    if (o.peak > s.peak) s.peak = o.peak;
+}
+// fir_pcm_quantise_dither that also says what it did (d = 0: fir_pcm_quantise's code -- x * scale + 0 rounds as x * scale does).
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise_stat(float x, uint32_t bits, float d, FirPcmStat& s) {
+    const float v = rintf(x * fir_pcm_scale(bits) + d);
+    fir_pcm_stat(x, v, bits, s);
+    return fir_pcm_code(v, bits);
+}
+// Where a counting launch keeps its statistics: four words {values, clipped, nans, peak bits} per stream and 1024-output-frame
+// chunk (kNfChunkShift: the repair pass's chunks), entry (stream * chunks + chunk); zeroed before the launch's main kernels.  The
+// first pass merges every value it stores into its frame's chunk with atomics; the repair pass, which rewrites marked chunks whole,
+// OVERWRITES their entries; fir_pcm_stats_fold behind it sums a stream's entries into the handle's totals.
+struct FirStatArgs {
+    uint32_t* table;
+    uint32_t chunks;   // entries per stream
+};
+// Where fir_pcm_stats_fold puts stream s's sums: the handle's totals in device memory, merged -- or replaced, where the handle was
+// cleared (rsmp_fir_pcm_stats_clear, reset) since its last counting launch.
+struct FirStatTarget {
+    rsmp_pcm_stats* acc;
+    uint32_t overwrite, reserved;
+};
+// One wave's share of an entry: `s` summed over the wave's lanes (all 64 active), then one lane's atomics -- none for a zero.
+__device__ __forceinline__ FirPcmStat fir_stat_wave_sum(FirPcmStat s) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        s.values += __shfl_xor(s.values, m, 64);
+        const uint32_t p = __shfl_xor(s.peak, m, 64);
+        s.peak = p > s.peak ? p : s.peak;
+    }
+    if (__any(s.clipped | s.nans)) {   // (rare: clean audio has neither)
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            s.clipped += __shfl_xor(s.clipped, m, 64);
+            s.nans += __shfl_xor(s.nans, m, 64);
+        }
+    }
+    return s;
+}
+__device__ __forceinline__ void fir_stat_atomic_merge(uint32_t* entry, const FirPcmStat& s) {
+    if (s.values) (void)atomicAdd(entry, s.values);
+    if (s.clipped) (void)atomicAdd(entry + 1, s.clipped);
+    if (s.nans) (void)atomicAdd(entry + 2, s.nans);
+    if (s.peak) (void)atomicMax(entry + 3, s.peak);
+}
 // One sample of a stream's PCM `out`, index `i` in values: the lane writes the sample's own bytes and no others.
 __device__ __forceinline__ void fir_pcm_store_code(void* out, uint32_t bits, size_t i, int32_t q) {
     if (bits == 16) {
@@ -129,10 +205,16 @@ __device__ __forceinline__ void fir_pcm_store_code(void* out, uint32_t bits, siz
     }
 }
 __device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y) { fir_pcm_store_code(out, bits, i, fir_pcm_quantise(y, bits)); }
-// How a build stores its sums: f32, PCM, PCM with TPDF dither (the launchers' choice by out_bits and dither).
-enum FirOut : int { kFirOutF32 = 0, kFirOutPcm = 1, kFirOutPcmTpdf = 2 };
-__host__ __device__ constexpr FirOut fir_out_mode(uint32_t out_bits, uint32_t dither) {
-    return out_bits == 0 ? kFirOutF32 : dither == RSMP_DITHER_TPDF ? kFirOutPcmTpdf : kFirOutPcm;
+// How a build stores its sums: f32, PCM, PCM with TPDF dither (the launchers' choice by out_bits and dither) -- and PCM that is
+// counted as it is stored (rsmp_fir_set_pcm_stats): builds of their own, with the dither a uniform branch on FirStreamDesc::dither.
+enum FirOut : int { kFirOutF32 = 0, kFirOutPcm = 1, kFirOutPcmTpdf = 2, kFirOutPcmStats = 3 };
+__host__ __device__ constexpr FirOut fir_out_mode(uint32_t out_bits, uint32_t dither, bool stats = false) {
+    return out_bits == 0 ? kFirOutF32 : stats ? kFirOutPcmStats : dither == RSMP_DITHER_TPDF ? kFirOutPcmTpdf : kFirOutPcm;
+}
+// A counting build's store of value `i` (as fir_out_store below): the bytes of the plain / dithered builds, and `s` says what was done.
+__device__ __forceinline__ void fir_out_store_stat(const FirStreamDesc& d, size_t i, float y, FirPcmStat& s) {
+    const float noise = d.dither == RSMP_DITHER_TPDF ? fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i) : 0.0f;
+    fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_stat(y, d.out_bits, noise, s));
 }
 // Value `i` of a stream's output in this launch.  OUT: the PCM-output builds of the generic kernels and of the repair pass (out_bits
 // != 0), with and without dither; the f32 builds do not read the fields.
@@ -150,7 +232,8 @@ constexpr uint32_t kFirTile = 32;   // output frames per workgroup tile (generic
 // (out_bits / dither, here and below: FirStreamDesc::out_bits / dither of the launch's streams -- out_bits != 0 selects the builds
 // that store PCM, dither their dithered twins)
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, uint32_t out_bits = 0, uint32_t dither = 0);
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, uint32_t out_bits = 0, uint32_t dither = 0,
+                              const FirStatArgs* st = nullptr);   // (st with a table, here and below: the counting builds; stream s's entries are st->table's s-th row)
 // The same arithmetic for LONG launches (fir_generic_bulk.hip): tiles of up to 4096 output frames per workgroup, their outputs sorted
 // by phase row, the tile's input window in LDS.  hipErrorNotSupported where no tile fits the LDS (fir_generic_bulk_tile == 0);
 // does not copy the tails (launch_fir_tail_copy).
@@ -160,19 +243,21 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels = 0,
                                    uint32_t uniform_taps = 0,    // (uniform_taps: 128 = every stream has 128 taps)
                                    uint32_t out_bits = 0,       // (PCM output: two-channel streams only, hipErrorNotSupported otherwise)
-                                   uint32_t dither = 0);
+                                   uint32_t dither = 0, const FirStatArgs* st = nullptr);
 constexpr uint32_t kFirBulkMinOut = 8192;   // launches whose longest generic stream produces fewer frames keep fir_generic_kernel
 // Re-evaluates, in the reference's two-row form, the output chunks a periodic launch marked as non-finite
 // (fir_nonfinite.h); exits at once when the launch marked nothing.
 // (done / done_attached, here and in launch_fir_tail_copy: as in launch_fir_repair_multi below -- the launch completes `done`
 // itself; *done_attached stays false when there was nothing to launch)
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done = nullptr, bool* done_attached = nullptr, uint32_t out_bits = 0, uint32_t dither = 0);
+                             hipEvent_t done = nullptr, bool* done_attached = nullptr, uint32_t out_bits = 0, uint32_t dither = 0,
+                             const FirStatArgs* st = nullptr);   // (counting: never completes `done` -- the fold follows)
 // The same for up to eight groups of streams (each with its own marks) in one launch.
 struct RepairJob {
     const FirStreamDesc* d_descs;
     uint32_t n_streams;
     NfArgs nf;
+    uint32_t stat_first = 0;   // counting launches: the row of the launch's statistics table that holds the job's first stream
 };
 constexpr uint32_t kMaxRepairJobs = 8;
 // (tail_descs: the launch also copies the tails of these n_tail streams -- what launch_fir_tail_copy does -- in one more row
@@ -181,7 +266,11 @@ constexpr uint32_t kMaxRepairJobs = 8;
 // own behind the kernel as hipEventRecord puts there; *done_attached = false: there was no such launch, record it yourself)
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs = nullptr,
                                    uint32_t n_tail = 0, uint32_t max_tail_values = 0, hipEvent_t done = nullptr, bool* done_attached = nullptr,
-                                   uint32_t out_bits = 0, uint32_t dither = 0);
+                                   uint32_t out_bits = 0, uint32_t dither = 0, const FirStatArgs* st = nullptr);
+// Behind a counting launch and its repair pass: a workgroup per stream sums the stream's row of st.table into d_targets[s]
+// (device memory).  (done / done_attached: as above)
+hipError_t launch_fir_pcm_stats_fold(const FirStatArgs& st, uint32_t n_streams, const FirStatTarget* d_targets, hipStream_t stream,
+                                     hipEvent_t done = nullptr, bool* done_attached = nullptr);
 // Copies the still-buffered tail of [hist|in] into hist_next; grid = (blocks, streams).
 hipError_t launch_fir_tail_copy(const FirStreamDesc* d_descs, uint32_t n_streams,
                                 uint32_t max_tail_values, hipStream_t stream, hipEvent_t done = nullptr, bool* done_attached = nullptr);

@@ -60,6 +60,17 @@ struct Launch {
     const hipStream_t stream;
     const uint32_t pcm_bits, out_bits;
     uint32_t dither = 0;   // PCM output: the handles' dither mode (rsmp_fir_set_pcm_dither), one for the launch
+    // PCM output: the handles count what they store (rsmp_fir_set_pcm_stats), all of them or none.  st: the launch's table in the
+    // leader's d_stat_table, a row of st.chunks entries per stream in launch order; targets_off: the FirStatTarget of every stream,
+    // in the workspace behind the plans' arrays.
+    bool stats = false;
+    FirStatArgs st{nullptr, 0};
+    size_t targets_off = 0;
+    const FirStatArgs* stat_rows(size_t first, FirStatArgs& rows) const {   // (the table from stream `first` of the launch on; nullptr: not counting)
+        if (!stats) return nullptr;
+        rows = FirStatArgs{st.table + first * st.chunks * 4, st.chunks};
+        return &rows;
+    }
     const size_t n;
     // launch order: generic jobs, then periodic jobs grouped by geometry (one launch per geometry)
     std::vector<size_t> order;
@@ -119,6 +130,12 @@ int bind_and_group(Launch& L) {
                 return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: one dither mode for all the streams of a batch (rsmp_fir_set_pcm_dither; "
                                                        "the seeds may differ)");
     }
+    if (L.out_bits != 0) {
+        L.stats = jobs[0].r->pcm_stats;
+        for (const FirJob& j : jobs)
+            if (j.r->pcm_stats != L.stats)
+                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: statistics for all the streams of a batch or for none (rsmp_fir_set_pcm_stats)");
+    }
     if (L.pcm_bits != 0 || L.out_bits != 0) {
         for (const FirJob& j : jobs)
             if (j.r->channels != 2)
@@ -162,6 +179,10 @@ void lay_out_workspace(Launch& L) {
                                      : pl.wraps.size();
             bytes = align_up(bytes + words * sizeof(uint32_t), 256);
         }
+    }
+    if (L.stats) {
+        L.targets_off = bytes;
+        bytes = align_up(bytes + L.n * sizeof(FirStatTarget), 256);
     }
     L.bytes = bytes;
 }
@@ -288,7 +309,28 @@ int fill_descriptors(Launch& L) {
             return rc;
         }
         pp.written = true;
+        if (L.stats) reinterpret_cast<FirStatTarget*>(L.h + L.targets_off)[slot] = FirStatTarget{r->d_pcm_stats.as<rsmp_pcm_stats>(), r->pcm_stats_cleared ? 1u : 0u, 0u};
     }
+    return RSMP_OK;
+}
+
+// A counting launch's table: a row of chunks per stream, zero before the main kernels (on the launch stream).
+int reserve_stat_table(Launch& L) {
+    if (!L.stats) return RSMP_OK;
+    rsmp_fir* leader = L.leader;
+    uint32_t max_out = 0;
+    for (const FirJob& j : L.jobs)
+        if (j.plan->produced_frames > max_out) max_out = static_cast<uint32_t>(j.plan->produced_frames);
+    L.st.chunks = (max_out >> kNfChunkShift) + 1;
+    const size_t bytes = L.n * L.st.chunks * 4 * sizeof(uint32_t);
+    if (bytes > leader->d_stat_table.capacity()) {
+        // (as reserve_mark_regions grows d_nf: the leader's earlier launches on ANOTHER stream are ahead of this one already --
+        // order_streams made L.stream wait for the handle's launch event --, so L.stream's end is the end of all of them)
+        RSMP_HIP_CHECK(hipStreamSynchronize(L.stream));
+        RSMP_HIP_CHECK(leader->d_stat_table.reserve(bytes));
+    }
+    L.st.table = leader->d_stat_table.as<uint32_t>();
+    RSMP_HIP_CHECK(hipMemsetAsync(L.st.table, 0, bytes, L.stream));
     return RSMP_OK;
 }
 
@@ -323,15 +365,17 @@ int launch_generic(Launch& L) {
     static const bool bulk_on = [] { const char* e = knob("RSMP_FIR_GENERIC_BULK"); return !e || atoi(e) != 0; }();
     const bool generic_bulk = bulk_on && L.n_generic != 0 && L.max_out_generic >= kFirBulkMinOut &&
                               fir_generic_bulk_tile(L.max_ch_generic, L.max_taps_generic, L.max_ratio_generic) != 0;
+    FirStatArgs rows;
+    const FirStatArgs* st = L.stat_rows(0, rows);   // (the generic streams are the launch's first)
     if (generic_bulk) {
         L.tail_fused = false;
         RSMP_HIP_CHECK(launch_fir_generic_bulk(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic,
                                                L.max_taps_generic, L.max_ratio_generic, L.stream,
                                                L.min_ch_generic == L.max_ch_generic ? L.max_ch_generic : 0u,
-                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.out_bits, L.dither));
+                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.out_bits, L.dither, st));
     } else if (L.n_generic)
         RSMP_HIP_CHECK(launch_fir_generic(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic, L.stream,
-                                          L.tail_fused, L.out_bits, L.dither));
+                                          L.tail_fused, L.out_bits, L.dither, st));
     return RSMP_OK;
 }
 
@@ -399,6 +443,7 @@ int launch_periodic_groups(Launch& L) {
         if (++leader->nf_tag == 0) leader->nf_tag = 1;
         rp.nf.tag = leader->nf_tag;
         const uint64_t key = items_key(L, g, max_blocks);
+        FirStatArgs rows;
         if (L.groups.size() > 1 && g.geo.mfma == 3 && L.pcm_bits == 0 && L.out_bits == 0) {
             // several rate pairs in one batch: those of the split kernel share launches (launch_fir_split_multi: one item
             // table launch, one kernel launch per kernel build among them), as in rsmp_fir_lockstep_run
@@ -406,7 +451,7 @@ int launch_periodic_groups(Launch& L) {
         } else {
             RSMP_HIP_CHECK(launch_fir_periodic(L.d_descs + first, static_cast<uint32_t>(g.members.size()), g.geo, max_blocks,
                                                leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.pcm_bits, L.out_bits,
-                                               L.dither));
+                                               L.dither, L.stat_rows(first, rows)));
         }
         first += g.members.size();
     }
@@ -417,6 +462,7 @@ int launch_periodic_groups(Launch& L) {
 // The main kernels: generic or generic-bulk, then the periodic groups; timed as one where the leader is profiling.
 int launch_main_kernels(Launch& L) {
     rsmp_fir* leader = L.leader;
+    if (int rc = reserve_stat_table(L)) return rc;
     if (leader->profiling)
         RSMP_HIP_CHECK(event_record(leader->prof_start[leader->prof_count % rsmp_fir::kProfRing], L.stream));
     if (int rc = launch_generic(L)) return rc;
@@ -467,18 +513,24 @@ int launch_followups(Launch& L) {
     // common.h), it is recorded behind them.
     if (int rc = launch_event(leader)) return rc;
     const bool wrap_last = n > n_generic && L.max_wraps > 0 && L.tail_fused;
-    const bool repair_last = L.tail_fused && !wrap_last;
+    // (a counting launch: the fold behind the repair pass takes the repair pass's place as the last launch)
+    const bool fold_last = L.stats && L.tail_fused && !wrap_last;
+    const bool repair_last = L.tail_fused && !wrap_last && !L.stats;
     L.done = L.stream != reinterpret_cast<hipStream_t>(RSMP_STREAM_LEGACY) ? leader->launch_ev->ev : nullptr;
     if (L.repairs.size() > 1) {
         std::vector<RepairJob> rj;
-        for (const Repair& rp : L.repairs) rj.push_back(RepairJob{L.d_descs + rp.first, rp.count, rp.nf});
+        for (const Repair& rp : L.repairs) rj.push_back(RepairJob{L.d_descs + rp.first, rp.count, rp.nf, static_cast<uint32_t>(rp.first)});
         RSMP_HIP_CHECK(launch_fir_repair_multi(rj.data(), rj.size(), L.stream, nullptr, 0, 0, repair_last ? L.done : nullptr,
-                                               &L.done_attached, L.out_bits, L.dither));
+                                               &L.done_attached, L.out_bits, L.dither, L.stats ? &L.st : nullptr));
     } else {
+        FirStatArgs rows;
         for (const Repair& rp : L.repairs)
             RSMP_HIP_CHECK(launch_fir_repair(L.d_descs + rp.first, rp.count, rp.nf, L.stream, repair_last ? L.done : nullptr,
-                                             &L.done_attached, L.out_bits, L.dither));
+                                             &L.done_attached, L.out_bits, L.dither, L.stat_rows(rp.first, rows)));
     }
+    if (L.stats)
+        RSMP_HIP_CHECK(launch_fir_pcm_stats_fold(L.st, static_cast<uint32_t>(n), reinterpret_cast<const FirStatTarget*>(L.d + L.targets_off),
+                                                 L.stream, fold_last ? L.done : nullptr, &L.done_attached));
     if (n > n_generic && L.max_wraps > 0)
         RSMP_HIP_CHECK(launch_fir_wrap_fixup(L.d_descs + n_generic, static_cast<uint32_t>(n - n_generic), L.max_wraps, L.stream,
                                              wrap_last ? L.done : nullptr, &L.done_attached));
@@ -498,6 +550,7 @@ void commit(Launch& L) {
         j.r->last_periodic = j.plan->periodic;
         j.r->mirror = j.plan->planned;
         j.r->cur ^= 1;
+        if (L.stats) j.r->pcm_stats_cleared = false;   // (the fold has written the handle's totals)
         if (j.r->last_launch != L.leader->launch_ev) j.r->last_launch = L.leader->launch_ev;   // (no reference count traffic per launch)
     }
 }

@@ -81,9 +81,10 @@ struct SplitBuild {
     int bits;         // PCM input of that width (0: f32)
     bool pcm_out;     // PCM output (its width is the descriptor's, read at run time)
     bool dither;      // ... with TPDF dither (the seeds are the descriptors')
+    bool stats;       // ... counted as it is stored (SplitArgs::stat); these builds read the dither mode from the descriptor (dither = false)
     bool operator==(const SplitBuild& o) const {
         return nk == o.nk && planes == o.planes && diag == o.diag && wide == o.wide && rounds == o.rounds && bits == o.bits &&
-               pcm_out == o.pcm_out && dither == o.dither;
+               pcm_out == o.pcm_out && dither == o.dither && stats == o.stats;
     }
 };
 enum class BuildError { kNone, kInvalid, kNotSupported };   // the launchers' hipErrorInvalidValue / hipErrorNotSupported
@@ -92,8 +93,9 @@ struct SplitChoice {
     BuildError error;
 };
 // diag: RSMP_FIR_DEBUG or RSMP_FIR_WTRACE is set; pcm_bits / out_bits / dither: FirStreamDesc::in_bits / out_bits / dither of the
-// launch's streams.
-SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits = 0, uint32_t dither = 0);
+// launch's streams; stats: the PCM output is counted (rsmp_fir_set_pcm_stats).
+SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits = 0, uint32_t dither = 0,
+                            bool stats = false);
 // Slot of launch_fir_periodic's kernel table for a geometry of the vector or f32 matrix-core kernels, or -1 (no such
 // build).  mfma_dbg: RSMP_FIR_MFMA_DBG (0 .. 3); mfma_ring: mfma_ring_knob().
 constexpr int kPeriodicSlots = 20;

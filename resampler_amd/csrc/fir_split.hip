@@ -76,6 +76,7 @@ struct SplitArgs {
     const uint32_t* items;           // the launch's item table (split_items_kernel): kItemWords words per item
     unsigned long long* wtrace;   // RSMP_FIR_WTRACE: kWtraceSlots timestamped events per wave
     NfArgs nf;                    // non-finite sums are marked here (fir_nonfinite.h)
+    FirStatArgs stat;             // the counting PCM-output builds (kFirOutPcmStats) merge what they store here; no other build reads it
 };
 
 constexpr uint32_t kWtraceSlots = 16;
@@ -163,7 +164,7 @@ struct StreamCtx {
     uint64_t abs_out, abs_consumed, wrap_k0;
     uint64_t q_first;     // abs_out / b: the period holding the launch's first output
     uint32_t sidx;        // the stream's index in the launch
-    uint64_t dither_seed; // (read by the dithered PCM-output builds alone)
+    uint64_t dither_seed; // (read by the dithered and the counting PCM-output builds alone)
 };
 
 // Through the scalar cache (constant address space): the descriptors do not change during the launch,
@@ -482,6 +483,8 @@ __device__ __forceinline__ uint32_t consumer_index(uint32_t w) { return w < 6 ? 
 // OUT: the streams' `out` is PCM (FirStreamDesc::out_bits: 16 / 24 / 32, one width per launch, read from the descriptor by
 // these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise) -- OUT is a FirOut; the
 // kFirOutPcmTpdf builds add TPDF dither there (fir_pcm_quantise_dither; the stream's seed from the descriptor, one 64-bit mix per frame).
+// The kFirOutPcmStats builds also count every value they store into its chunk's entry of g.stat (fir_pcm_stat), where the wave
+// decides what it stores -- a deferred store is counted once, there --; they serve both dither modes (a wave-uniform branch).
 template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0, int OUT = kFirOutF32>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
 __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__ descs, const SplitArgs& g,
                                                const uint32_t wg, const uint32_t n_wgs) {   // workgroup `wg` of the `n_wgs` that share g's items
@@ -1353,7 +1356,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     struct NoKey {
         __device__ NoKey operator+(uint64_t) const { return NoKey{}; }
     };
-    typedef typename std::conditional<OUT == kFirOutPcmTpdf, uint64_t, NoKey>::type dkey_t;
+    constexpr bool kKeyed = OUT == kFirOutPcmTpdf || OUT == kFirOutPcmStats;
+    typedef typename std::conditional<kKeyed, uint64_t, NoKey>::type dkey_t;
     dkey_t pend_k{};
     typedef v2f __attribute__((address_space(1)))* g_f2_ptr;
     // PCM output: the launch's width (wave-uniform, in a scalar register) and the bytes of a two-channel frame
@@ -1362,6 +1366,11 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
         out_bits = __builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[0].out_bits));
         out_fb = out_bits >> 2;
+    }
+    bool dith = false;   // counting builds: the launch's dither mode (wave-uniform, as the width)
+    if constexpr (OUT == kFirOutPcmStats) {
+        typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
+        dith = __builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[0].dither)) == RSMP_DITHER_TPDF;
     }
     typedef uint8_t __attribute__((address_space(1)))* g_u8_ptr;
     typedef uint16_t __attribute__((address_space(1)))* g_u16_ptr;
@@ -1372,7 +1381,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     // fir_dither_word of pair abs_out + n: the values' indices are 2 (abs_out + n) and that + 1 --, the frames behind it from
     // the key + kFirDitherStep each.  The key carries the stream's seed and counter: a pending store needs nothing else of `d`.
     auto dither_key = [&](const StreamCtx& d, int32_t n) -> dkey_t {
-        if constexpr (OUT != kFirOutPcmTpdf) return NoKey{};
+        if constexpr (!kKeyed) return NoKey{};
         else return d.dither_seed + (d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n)) + 1u) * kFirDitherStep;
     };
     // a frame's two dithered codes (the undithered builds quantise below, in the statements they always had: their code is unchanged)
@@ -1381,11 +1390,64 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
             const uint64_t w = fir_dither_mix(k);
             q0 = static_cast<uint32_t>(fir_pcm_quantise_dither(y0, out_bits, fir_dither_value(static_cast<uint32_t>(w))));
             q1 = static_cast<uint32_t>(fir_pcm_quantise_dither(y1, out_bits, fir_dither_value(static_cast<uint32_t>(w >> 32))));
+        } else if constexpr (OUT == kFirOutPcmStats) {
+            float d0 = 0.0f, d1 = 0.0f;   // (no dither: x * scale + 0 rounds to fir_pcm_quantise's code)
+            if (dith) {
+                const uint64_t w = fir_dither_mix(k);
+                d0 = fir_dither_value(static_cast<uint32_t>(w));
+                d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
+            }
+            q0 = static_cast<uint32_t>(fir_pcm_quantise_dither(y0, out_bits, d0));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise_dither(y1, out_bits, d1));
+        }
+    };
+    // Counting builds: the frames n0 + r this lane is about to store (or to defer) -- all four where `full`, else those inside the
+    // period and the launch -- merged into their chunks' entries of stream d's row.  Called by the whole wave.  A wave's lanes are
+    // sixteen periods of four classes each: its frames lie in a few chunks (one to three at 44.1 -> 48 kHz), a lane's four frames in
+    // one or, across a chunk boundary, two.  Per chunk present in the wave: a sum over the wave of the frames that lie in it, and one
+    // lane's atomics.
+    auto count_frames = [&](const StreamCtx& d, int32_t n0, int32_t n_limit, uint32_t j0, bool full, const v4f& lo, const v4f& hi) {
+        if constexpr (OUT == kFirOutPcmStats) {
+            const float y[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            FirPcmStat fr[4];
+            int32_t c_next = -1, c_last = -1;   // the lane's chunks still to merge: c_next first, then c_last if it is another
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int32_t n = n0 + r;
+                fr[r] = FirPcmStat{0, 0, 0, 0};
+                if (full || (j0 + r < g.b && n >= 0 && n < n_limit)) {
+                    float d0 = 0.0f, d1 = 0.0f;
+                    if (dith) {
+                        const uint64_t w = fir_dither_mix(dither_key(d, n));
+                        d0 = fir_dither_value(static_cast<uint32_t>(w));
+                        d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
+                    }
+                    (void)fir_pcm_quantise_stat(y[2 * r], out_bits, d0, fr[r]);
+                    (void)fir_pcm_quantise_stat(y[2 * r + 1], out_bits, d1, fr[r]);
+                    c_last = n >> kNfChunkShift;
+                    if (c_next < 0) c_next = c_last;
+                }
+            }
+            uint32_t* row = g.stat.table + static_cast<size_t>(d.sidx) * g.stat.chunks * 4;
+            for (unsigned long long m = __ballot(c_next >= 0); m != 0; m = __ballot(c_next >= 0)) {   // (wave-uniform)
+                const int first = __ffsll(m) - 1;
+                const int32_t c = __shfl(c_next, first, 64);
+                FirPcmStat part{0, 0, 0, 0};
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (c_next == c && fr[r].values != 0 && ((n0 + r) >> kNfChunkShift) == c) fir_pcm_stat_merge(part, fr[r]);   // (a lane merges a chunk when it is AT it: once)
+                const FirPcmStat w = fir_stat_wave_sum(part);
+                if (static_cast<int>(lane) == first) fir_stat_atomic_merge(row + static_cast<size_t>(c) * 4, w);
+                if (c_next == c) {   // this lane's frames of chunk c are in: on to its other chunk, if it has one
+                    c_next = c_last != c ? c_last : -1;
+                    c_last = c_next;
+                }
+            }
         }
     };
     auto store_frame_pcm = [&](g_f32_ptr o, float y0, float y1, dkey_t k) {
         uint32_t q0, q1;
-        if constexpr (OUT == kFirOutPcmTpdf) {
+        if constexpr (kKeyed) {
             dither_frame(y0, y1, k, q0, q1);
         } else {
             q0 = static_cast<uint32_t>(fir_pcm_quantise(y0, out_bits));
@@ -1407,7 +1469,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     auto store_frames_pcm = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, dkey_t k) {
         const float y[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
         uint32_t q[8];
-        if constexpr (OUT == kFirOutPcmTpdf) {
+        if constexpr (kKeyed) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) dither_frame(y[2 * i], y[2 * i + 1], k + static_cast<uint64_t>(i) * kFirDitherStep, q[2 * i], q[2 * i + 1]);
         } else {
@@ -1624,6 +1686,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         const v4f hi = v4f{acc0.z, acc1.z, acc0.w, acc1.w};
         if (!(dbg & 16)) {
             const bool full = j0 + 4 <= g.b && n0 >= 0 && n0 + 4 <= n_limit;
+            count_frames(d, n0, n_limit, j0, full, lo, hi);
             bool combined = false;
             if constexpr (WIDE) {
                 // the odd pair of a block whose even pair is pending: four channels of a frame side by side, 16-byte stores
@@ -1691,6 +1754,11 @@ template <int NK, int ROUNDS, int BITS>
 __global__ __launch_bounds__(1024) void fir_split_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
     fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcmTpdf>(descs, g, blockIdx.x, gridDim.x);
 }
+// ... and counted as it is stored (SplitArgs::stat), with or without dither
+template <int NK, int ROUNDS, int BITS>
+__global__ __launch_bounds__(1024) void fir_split_pcm_stats_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
+    fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcmStats>(descs, g, blockIdx.x, gridDim.x);
+}
 template <int NK, int PLANES, int WIDE, int ROUNDS>
 __global__ __launch_bounds__(1024) void fir_split_multi_kernel(const SplitMulti m) {
     uint32_t begin;
@@ -1750,7 +1818,7 @@ SplitArgs make_split_args(const PeriodicGeometry& geo, uint32_t n_streams, uint3
                      groups, per_group, quads, qpairs, wide ? 1u : 0u,
                      // (b = r den with r > 1: a super period of an exact ratio.  WIDE builds only: the two-channel tile-group
                      // kernel got SLOWER without the fetches -- 2 ch 48 -> 96 kHz 0.59 -> 0.66 ms)
-                     wide && geo.b != geo.den ? 1u : 0u, nullptr, nullptr, nf};
+                     wide && geo.b != geo.den ? 1u : 0u, nullptr, nullptr, nf, FirStatArgs{nullptr, 0}};
 }
 // The item-table workspace of (device, stream), at least `need` bytes.  `key` / `items`: see launch_fir_split; *have_table =
 // the workspace already holds the table with that key.
@@ -1782,10 +1850,11 @@ hipError_t items_workspace(int device, hipStream_t stream, size_t need, uint64_t
 // geometry runs on).
 namespace {
 const void* split_kernel_for(const SplitBuild& build) {
-#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B, false, false}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
+#define RSMP_SPLIT(NK, P, D, W, R, B) {SplitBuild{NK, P, D, W, R, B, false, false, false}, reinterpret_cast<const void*>(fir_split_kernel<NK, P, D, W, R, B>)}
 #define RSMP_SPLIT_OUT1(NK, R, B)                                                                                        \
-    {SplitBuild{NK, 2, false, 0, R, B, true, false}, reinterpret_cast<const void*>(fir_split_pcm_out_kernel<NK, R, B>)}, \
-    {SplitBuild{NK, 2, false, 0, R, B, true, true}, reinterpret_cast<const void*>(fir_split_pcm_tpdf_kernel<NK, R, B>)}
+    {SplitBuild{NK, 2, false, 0, R, B, true, false, false}, reinterpret_cast<const void*>(fir_split_pcm_out_kernel<NK, R, B>)},  \
+    {SplitBuild{NK, 2, false, 0, R, B, true, true, false}, reinterpret_cast<const void*>(fir_split_pcm_tpdf_kernel<NK, R, B>)},  \
+    {SplitBuild{NK, 2, false, 0, R, B, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_stats_kernel<NK, R, B>)}
 #define RSMP_SPLIT_OUT(B) RSMP_SPLIT_OUT1(5, 1, B), RSMP_SPLIT_OUT1(5, 2, B), RSMP_SPLIT_OUT1(6, 2, B)
 #define RSMP_SPLIT_1TO5(P, D, W) RSMP_SPLIT(1, P, D, W, 1, 0), RSMP_SPLIT(2, P, D, W, 1, 0), RSMP_SPLIT(3, P, D, W, 1, 0), RSMP_SPLIT(4, P, D, W, 1, 0), RSMP_SPLIT(5, P, D, W, 1, 0)
 #define RSMP_SPLIT_PCM(B) RSMP_SPLIT(5, 2, false, 0, 1, B), RSMP_SPLIT(5, 2, false, 0, 2, B), RSMP_SPLIT(6, 2, false, 0, 2, B)
@@ -1801,7 +1870,7 @@ const void* split_kernel_for(const SplitBuild& build) {
         // PCM input: the two-channel fp16 builds of the 128-tap windows
         RSMP_SPLIT_PCM(16), RSMP_SPLIT_PCM(24), RSMP_SPLIT_PCM(32),
         // PCM output (its width read from the descriptor) from the same three builds, for f32 input and the three PCM widths, each
-        // without and with TPDF dither
+        // without and with TPDF dither, and counted (either dither mode)
         RSMP_SPLIT_OUT(0), RSMP_SPLIT_OUT(16), RSMP_SPLIT_OUT(24), RSMP_SPLIT_OUT(32)};
 #undef RSMP_SPLIT_OUT
 #undef RSMP_SPLIT_OUT1
@@ -1816,10 +1885,11 @@ const void* split_kernel_for(const SplitBuild& build) {
 
 hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, const PeriodicGeometry& geo,
                             uint32_t max_blocks, uint32_t cus, bool fuse_tail, const NfArgs& nf, hipStream_t stream,
-                            uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither) {
+                            uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
     static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
     const bool diag = fir_debug_knob() != 0 || wtrace_path != nullptr;
-    const SplitChoice choice = split_build_for(geo, diag, pcm_bits, out_bits, dither);
+    const bool counted = st != nullptr && st->table != nullptr && out_bits != 0;
+    const SplitChoice choice = split_build_for(geo, diag, pcm_bits, out_bits, dither, counted);
     if (choice.error != BuildError::kNone) return choice.error == BuildError::kInvalid ? hipErrorInvalidValue : hipErrorNotSupported;
     const void* fn = split_kernel_for(choice.build);
     if (fn == nullptr) return hipErrorInvalidValue;
@@ -1828,6 +1898,7 @@ hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, co
     if (e != hipSuccess) return e;
     if ((e = grant_dynamic_lds(device, fn, kLdsLimit)) != hipSuccess) return e;
     SplitArgs args = make_split_args(geo, n_streams, max_blocks, fuse_tail, nf);
+    if (counted) args.stat = *st;
     const dim3 grid(args.total_items < cus ? args.total_items : cus);
     static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
     if (verbose)

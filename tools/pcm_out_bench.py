@@ -15,6 +15,12 @@ measured again at the end (a_f32_output_again) to show what the box's drift over
 
 --dither tpdf: rows (b), (c) and (d) with TPDF dither (ResamplerFir.set_pcm_dither, stream i's seed = --seed + i; the conversion
 pass of (b) dithers with the same seeds); --dither none (the default) is the table as it was.
+--stats: behind the table, what counting costs (ResamplerFir.set_pcm_stats).  Per width, from f32 and from PCM input, with the
+--dither mode: the fused launch with the setting off and on, and the two-pass route a caller would take without it -- the f32
+launch, then rsmp_f32_to_pcm_stats_device over every stream's output into a 32-byte accumulator per stream.  These rows are WHOLE
+steps, bracketed by events on the stream (the zeroing of the launch's table, the main kernels, the repair pass and the fold that
+follow them; for the two-pass route the conversions): the handle's profiling events cover the main kernels alone, which is not
+all that the setting adds.  The rows of the table above run with the setting off.
 --convert: instead of the table, the stand-alone conversion alone -- rsmp_f32_to_pcm_device without and with dither over
 --convert-values values, and rsmp_device_stream_copy moving the same number of bytes (the conversion reads 4 and writes bits / 8
 bytes a value, the copy reads and writes 4 bytes a float) -- each bracketed by events, median of --reps bursts, with GB/s.
@@ -86,6 +92,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=512)
     ap.add_argument("--dither", choices=("none", "tpdf"), default="none")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--stats", action="store_true")
     ap.add_argument("--convert", action="store_true")
     ap.add_argument("--convert-values", type=int, default=1 << 27)
     a = ap.parse_args()
@@ -131,7 +138,9 @@ def main():
             torch.cuda.synchronize()
             t, n = hs[0].mean_kernel_ms()
             assert n == a.burst
-            if extra:
+            if extra == "whole":   # (the step bracketed itself with its event pair: that is its time)
+                t = sum(e0.elapsed_time(e1) for e0, e1 in ev) / a.burst
+            elif extra:
                 t += sum(e0.elapsed_time(e1) for e0, e1 in ev) / a.burst
             times.append(t)
         return times
@@ -175,6 +184,41 @@ def main():
         result["rows"][f"d_fused_{bits}_from_pcm_{bits}"] = stats(t_d)
         result["rows"][f"gain_b_minus_c_{bits}_ms"] = round(float(np.median(t_b) - np.median(t_c)), 4)
         result["rows"][f"c_minus_a_{bits}_ms"] = round(float(np.median(t_c) - np.median(t_a)), 4)
+        if a.stats:
+            d_acc = torch.zeros(S, 4, dtype=torch.int64, device=dev)   # a 32-byte accumulator per stream
+
+            def whole(step):
+                def bracketed(e0, e1):
+                    e0.record()
+                    step(None, None)
+                    e1.record()
+                    return "whole"
+                return bracketed
+
+            def two_pass_stats(e0, e1):
+                d_acc.zero_()   # (the caller zeroes its accumulators: part of the route)
+                f32_launch()
+                for i, (o, q, n) in enumerate(zip(d_out, d_pcm_out, produced[0])):
+                    ra.f32_to_pcm_stats_device(o[:n], bits, q, d_acc[i], stream, dither=dither, seed=a.seed + i)
+
+            on_f32 = None
+            for name, step in (("f32", fused_f32), (f"pcm_{bits}", fused_pcm)):
+                t_off = run(whole(step))
+                for h in hs:
+                    h.set_pcm_stats(True)
+                t_on = run(whole(step))
+                clipped = sum(h.pcm_stats().clipped for h in hs)
+                for h in hs:
+                    h.set_pcm_stats(False)
+                on_f32 = t_on if on_f32 is None else on_f32
+                result["rows"][f"e_step_fused_{bits}_from_{name}_stats_off"] = stats(t_off)
+                result["rows"][f"f_step_fused_{bits}_from_{name}_stats_on"] = stats(t_on)
+                result["rows"][f"f_minus_e_{bits}_from_{name}_ms"] = round(float(np.median(t_on) - np.median(t_off)), 4)
+                result["rows"][f"clipped_last_step_{bits}_from_{name}"] = int(clipped)
+            t_g = run(whole(two_pass_stats))
+            result["rows"][f"g_step_f32_output_then_f32_to_pcm_stats_{bits}"] = stats(t_g)
+            result["rows"][f"gain_g_minus_f_{bits}_from_f32_ms"] = round(float(np.median(t_g) - np.median(on_f32)), 4)
+            del d_acc
         del d_pcm_out, d_pcm_in
     result["rows"]["a_f32_output_again"] = stats(run(f32_launch))
     hs[0].set_profiling(False)
