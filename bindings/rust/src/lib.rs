@@ -224,6 +224,9 @@ impl ResamplerFir {
     /// Addition to the reference API: the same loop with the output as a WAV file stores it -- `d_out_pcm` (device memory, 4-byte
     /// aligned, room for `out_cap` samples) receives little-endian PCM of `out_bits` (16 / 24 / 32), quantised where the kernels
     /// store their sums (`f32_to_pcm`'s rule).  `d_in`: interleaved f32 (`in_bits` = 0) or PCM of `in_bits`, `n_values` values.
+    /// Streams of two channels, or -- f32 input only -- of an even count of 4 .. 16 channels; long launches need one of the split
+    /// kernel's 128-tap rate pairs.  One channel, odd counts, more than 16 channels and PCM input of other than two channels are
+    /// an error before anything is launched or written: take f32 output and convert with `rsmp_f32_to_pcm_device`.
     /// Returns (consumed, produced) in samples.
     pub unsafe fn resample_bulk_pcm_out_device(&mut self, d_in: *const std::os::raw::c_void, in_bits: u32, n_values: usize, chunk_len: usize,
                                                d_out_pcm: *mut std::os::raw::c_void, out_bits: u32, out_cap: usize)

@@ -215,9 +215,14 @@ int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size_t n, const
  * interleaved f32 (in_bits = 0) or PCM of in_bits (16 / 24 / 32) as in rsmp_fir_batch_resample_bulk_pcm_device; in_lens in
  * values / samples.  Counts, end states, the buffered frames (f32 always) and the ordering on `stream` are those of the f32
  * entry on the same input.  No byte outside [d_out_pcm[i], d_out_pcm[i] + out_caps[i] * out_bits / 8) is written; a capacity
- * too small is RSMP_ERR_CAPACITY before anything is launched.  Planned on the host.  Two-channel streams; long launches need
- * the 128-tap rate pairs of the split kernel as PCM input does, at most one launch's worth of input per stream; anything else is
- * RSMP_ERR_INVALID_ARGUMENT before any launch -- take f32 output and convert with rsmp_f32_to_pcm_device.
+ * too small is RSMP_ERR_CAPACITY before anything is launched.  Planned on the host.  Streams of two channels (f32 or PCM input)
+ * or, from f32 input, of an even count of 4 .. 16 channels -- a 5.1, 7.1 or 8-channel file; the contract is the same with the
+ * stream's own `channels`, and one batch may mix the counts.  Long launches need the 128-tap rate pairs of the split kernel as PCM
+ * input does, at most one launch's worth of input per stream; a launch of fewer than 16384 output frames, and a rate pair without
+ * a short period at any length, is served by the generic kernels -- for more than two channels the latency kernel.  Still refused: one channel, odd counts, more than 16 channels, and
+ * PCM input of other than two channels (rsmp_pcm_to_stereo_f32_device reads stereo files: pass f32).  These and anything else
+ * are RSMP_ERR_INVALID_ARGUMENT before any launch, with nothing written and no state changed -- take f32 output and convert with
+ * rsmp_f32_to_pcm_device.
  * Dither is a setting of the handles (rsmp_fir_set_pcm_dither below, default RSMP_DITHER_NONE). */
 int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                 const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,

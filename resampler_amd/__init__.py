@@ -591,7 +591,12 @@ class FirBatch:
                                      stream: Optional[int] = None):
         """The bulk driver loop with the output as a WAV file stores it (rsmp_fir_batch_resample_bulk_pcm_out_device): d_out_pcms =
         uint8 tensors that receive little-endian PCM of `out_bits` (16 / 24 / 32), quantised where the kernels store their sums
-        (f32_to_pcm's rule; with the dither the streams were given by ResamplerFir.set_pcm_dither -- one mode for all of them).  d_ins = float32 tensors (in_bits = 0) or uint8 tensors of PCM of `in_bits`."""
+        (f32_to_pcm's rule; with the dither the streams were given by ResamplerFir.set_pcm_dither -- one mode for all of them).  d_ins = float32 tensors (in_bits = 0) or uint8 tensors of PCM of `in_bits`.
+        Streams of two channels, or -- float32 input only -- of an even count of 4 .. 16 channels (5.1, 7.1 ...; a batch may mix the
+        counts); long launches need one of the split kernel's 128-tap rate pairs (44.1 <-> 48, 96 -> 44.1 / 48 kHz ...); launches under
+        16384 output frames, and rate pairs without a short period, take the generic kernels at any length.  One channel,
+        odd counts, more than 16 channels and PCM input of other than two channels raise ResampleError before anything is launched,
+        written or changed: take float32 output and f32_to_pcm_device."""
         n = len(self.resamplers)
         pin, pout = (C.c_void_p * n)(), (C.c_void_p * n)()
         lens, caps = (C.c_size_t * n)(), (C.c_size_t * n)()

@@ -689,6 +689,9 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
 // bytes with the handle's seed and first_index = abs_out * channels.
 // Handles set to count (rsmp_fir_set_pcm_stats; all of a batch or none) take the kernels' counting builds: the same bytes, and
 // rsmp_f32_to_pcm_stats's statistics of them in the handles' totals.
+// Streams: two channels (f32 or PCM input), or -- f32 input -- an even count of 4 .. 16 channels, written by the split kernel's
+// channel-pair builds a frame of a pair at a time (the same contract with `channels` for 2; launch_jobs holds the periodic groups
+// to the three 128-tap windows; streams it plans generic go to the latency kernel at any length).  One channel, odd counts, more than 16 and PCM input of other than two channels are refused here.
 extern "C" int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                            const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
                                                            const size_t* out_caps, size_t* consumed, size_t* produced, void* stream) {
@@ -700,13 +703,18 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, 
     std::vector<const float*> in(n);
     std::vector<float*> out(n);
     for (size_t i = 0; i < n; ++i) {
-        if (!rs[i] || rs[i]->channels != 2)
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: two-channel streams only "
-                                                         "(any other count: f32 output and rsmp_f32_to_pcm_device)");
+        if (!rs[i]) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: null stream");
+        const size_t ch = rs[i]->channels;
+        if (in_bits != 0 && ch != 2)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: PCM input: two-channel streams only "
+                                                         "(rsmp_pcm_to_stereo_f32_device converts a stereo file; pass any other count as f32)");
+        if (ch % 2 != 0 || ch > 16)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: two-channel streams only or, from f32 input, "
+                                                         "an even count up to 16; one channel, odd counts, more than 16: f32 output and rsmp_f32_to_pcm_device");
         if ((in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) || reinterpret_cast<uintptr_t>(d_out_pcm[i]) % 4 != 0)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input and output must be 4-byte aligned");
         // (one launch: a stream offered more than a launch's worth of input goes through the f32 entry point, which cuts it)
-        if (chunk_len % 2 == 0 && in_lens[i] % 2 == 0 && in_lens[i] > rsmp::launch_input_values(rs[i]->mirror.ratio(), 2, chunk_len))
+        if (chunk_len % ch == 0 && in_lens[i] % ch == 0 && in_lens[i] > rsmp::launch_input_values(rs[i]->mirror.ratio(), ch, chunk_len))
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: more than one launch's worth of input (46 M outputs)");
         in[i] = static_cast<const float*>(d_in[i]);
         out[i] = static_cast<float*>(d_out_pcm[i]);

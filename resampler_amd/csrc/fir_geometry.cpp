@@ -292,7 +292,8 @@ void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_ou
 // (44.1 <-> 48 kHz) or two, 192 taps in two rounds (96 -> 44.1 kHz) -- exist for the three widths; kNotSupported
 // for any other geometry (the caller converts with rsmp_pcm_to_stereo_f32_device first).
 // PCM output (FirStreamDesc::out_bits): the same three windows, from f32 or PCM input, as builds of their own that read the
-// width from the descriptor; kNotSupported for any other geometry (the caller converts with rsmp_f32_to_pcm_device afterwards).
+// width from the descriptor -- and, from f32 input, the channel-pair builds of those windows (an even count of 4 .. 16 channels);
+// kNotSupported for any other geometry (the caller converts with rsmp_f32_to_pcm_device afterwards).
 // dither != 0 (FirStreamDesc::dither): their twins that add TPDF dither.  stats: their twins that count what they store, with or
 // without dither (one build for both: a uniform branch).
 SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither, bool stats) {
@@ -316,11 +317,13 @@ SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm
     if (pcm_bits != 0 || out_bits != 0) {
         const bool window_ok = nk == 5 || (two_rounds && nk == 6);
         const auto width_ok = [](uint32_t w) { return w == 16 || w == 24 || w == 32; };
-        if (wide || one_channel || odd_count || geo.planes != 2 || diag || !window_ok || (pcm_bits != 0 && !width_ok(pcm_bits)) ||
+        // (channel pairs -- an even count of 4 .. 16 channels -- write PCM from f32 input; they do not read it)
+        const bool pairs_out = wide && geo.cg == 2 && pcm_bits == 0 && out_bits != 0;
+        if ((wide && !pairs_out) || one_channel || odd_count || geo.planes != 2 || diag || !window_ok || (pcm_bits != 0 && !width_ok(pcm_bits)) ||
             (out_bits != 0 && !width_ok(out_bits)))
             return {b, BuildError::kNotSupported};
         const bool counted = out_bits != 0 && stats;
-        b = SplitBuild{nk, 2, false, 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, out_bits != 0 && dither != 0 && !counted, counted};
+        b = SplitBuild{nk, 2, false, pairs_out ? 1 : 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, out_bits != 0 && dither != 0 && !counted, counted};
     }
     return {b, BuildError::kNone};
 }

@@ -122,7 +122,8 @@ int bind_and_group(Launch& L) {
         if (!found) L.groups.push_back(Group{j.r->periodic.geo, {i}});
     }
     for (const Group& g : L.groups) for (size_t i : g.members) L.order.push_back(i);
-    // PCM input and PCM output have one admission rule: two-channel streams; periodic groups on the split kernel's builds for them
+    // PCM input: two-channel streams, periodic groups on the split kernel's builds for them.  PCM output: the same, or -- from f32
+    // input -- an even count of 4 .. 16 channels on the channel-pair builds of the same three windows (split_build_for).
     if (L.out_bits != 0) {
         L.dither = static_cast<uint32_t>(jobs[0].r->pcm_dither);
         for (const FirJob& j : jobs)
@@ -137,22 +138,29 @@ int bind_and_group(Launch& L) {
                 return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: statistics for all the streams of a batch or for none (rsmp_fir_set_pcm_stats)");
     }
     if (L.pcm_bits != 0 || L.out_bits != 0) {
-        for (const FirJob& j : jobs)
-            if (j.r->channels != 2)
-                return fail(RSMP_ERR_INVALID_ARGUMENT, L.pcm_bits != 0 ? "PCM input: two-channel streams only"
-                                                                       : "PCM output: two-channel streams only (convert with rsmp_f32_to_pcm_device afterwards)");
+        for (const FirJob& j : jobs) {
+            const size_t ch = j.r->channels;
+            if (L.pcm_bits != 0 && ch != 2)
+                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input: two-channel streams only (rsmp_pcm_to_stereo_f32_device converts a stereo file; "
+                                                       "pass any other count as f32)");
+            if (ch % 2 != 0 || ch > 16)
+                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: two-channel streams only or, from f32 input, an even count up to 16; "
+                                                       "one channel, odd counts, more than 16: f32 output and rsmp_f32_to_pcm_device");
+        }
         for (const Group& g : L.groups) {
             const uint32_t nk = g.geo.row_len / 32;
-            const bool ok = g.geo.mfma == 3 && g.geo.planes == 2 && g.geo.lp == 1 && g.geo.cg == 2 &&
-                            ((g.geo.rounds == 1 && nk == 5) || (g.geo.rounds == 2 && (nk == 5 || nk == 6)));
+            const bool window_ok = (g.geo.rounds == 1 && nk == 5) || (g.geo.rounds == 2 && (nk == 5 || nk == 6));
+            const bool stereo = g.geo.lp == 1 && g.geo.cg == 2;
+            const bool pairs_out = L.pcm_bits == 0 && g.geo.lp > 1 && g.geo.cg == 2;   // (PCM output alone: 4, 6, 8 .. 16 channels)
+            const bool ok = g.geo.mfma == 3 && g.geo.planes == 2 && (stereo || pairs_out) && window_ok;
             if (!ok && L.pcm_bits != 0)
                 return fail(RSMP_ERR_INVALID_ARGUMENT,
                             "PCM input is read in place by the two-channel split kernel of the 128-tap rate pairs only "
                             "(44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): convert with rsmp_pcm_to_stereo_f32_device first");
             if (!ok)
                 return fail(RSMP_ERR_INVALID_ARGUMENT,
-                            "PCM output is written in place by the two-channel split kernel of the 128-tap rate pairs only "
-                            "(44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): take f32 output and convert with rsmp_f32_to_pcm_device");
+                            "PCM output is written in place by the split kernel of the 128-tap rate pairs only, for two channels or "
+                            "an even count up to 16 (44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): take f32 output and convert with rsmp_f32_to_pcm_device");
         }
     }
     return RSMP_OK;
@@ -364,7 +372,11 @@ int launch_generic(Launch& L) {
     // keep the one-launch latency path.  (RSMP_FIR_GENERIC_BULK=0, debug: the latency kernel for everything.)
     static const bool bulk_on = [] { const char* e = knob("RSMP_FIR_GENERIC_BULK"); return !e || atoi(e) != 0; }();
     const bool generic_bulk = bulk_on && L.n_generic != 0 && L.max_out_generic >= kFirBulkMinOut &&
-                              fir_generic_bulk_tile(L.max_ch_generic, L.max_taps_generic, L.max_ratio_generic) != 0;
+                              fir_generic_bulk_tile(L.max_ch_generic, L.max_taps_generic, L.max_ratio_generic) != 0 &&
+                              // (PCM output: the tiled kernel's builds are two-channel; a generic stream of more channels -- a launch
+                              // too short to be worth the periodic kernels, a rate pair without a short period -- keeps the batch's
+                              // generic streams on the latency kernel, which stores by value index for any count, at any length)
+                              (L.out_bits == 0 || (L.min_ch_generic == 2 && L.max_ch_generic == 2));
     FirStatArgs rows;
     const FirStatArgs* st = L.stat_rows(0, rows);   // (the generic streams are the launch's first)
     if (generic_bulk) {

@@ -489,7 +489,7 @@ template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0,
 __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__ descs, const SplitArgs& g,
                                                const uint32_t wg, const uint32_t n_wgs) {   // workgroup `wg` of the `n_wgs` that share g's items
     static_assert(ROUNDS == 1 || ((WIDE == 0 || WIDE == 1) && PLANES == 2), "two rounds: two channels or channel pairs, fp16 planes");
-    static_assert(!OUT || (WIDE == 0 && PLANES == 2 && !DIAG), "PCM output: the two-channel fp16 build");
+    static_assert(!OUT || ((WIDE == 0 || (WIDE == 1 && BITS == 0)) && PLANES == 2 && !DIAG), "PCM output: the two-channel fp16 build, or channel pairs from f32 input");
     constexpr uint32_t kRowBytes = row_bytes(PLANES);
     const uint32_t fs = WIDE ? g.cstride : 2u;   // floats per frame
     const uint32_t fsb = fs * 4u;                // bytes per frame
@@ -1362,10 +1362,14 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     typedef v2f __attribute__((address_space(1)))* g_f2_ptr;
     // PCM output: the launch's width (wave-uniform, in a scalar register) and the bytes of a two-channel frame
     uint32_t out_bits = 0, out_fb = 0;
+    // ... channel pairs (OUT && WIDE): a pair of a frame is out_fb bytes -- the unit of a store --, the same pair of the next frame
+    // lies out_stride bytes on (a byte count: no arithmetic on `fs`, which counts floats); key_pair: the current item's pair
+    uint32_t out_stride = 0, key_pair = 0;
     if constexpr (OUT) {
         typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
         out_bits = __builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[0].out_bits));
         out_fb = out_bits >> 2;
+        if constexpr (WIDE) out_stride = out_fb * g.pairs;
     }
     bool dith = false;   // counting builds: the launch's dither mode (wave-uniform, as the width)
     if constexpr (OUT == kFirOutPcmStats) {
@@ -1382,6 +1386,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     // the key + kFirDitherStep each.  The key carries the stream's seed and counter: a pending store needs nothing else of `d`.
     auto dither_key = [&](const StreamCtx& d, int32_t n) -> dkey_t {
         if constexpr (!kKeyed) return NoKey{};
+        // channel pairs: values (abs_out + n) * channels + 2 pair and + 1 -- an even index, word (abs_out + n) * pairs + pair
+        else if constexpr (WIDE) return d.dither_seed + ((d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n))) * g.pairs + key_pair + 1u) * kFirDitherStep;
         else return d.dither_seed + (d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n)) + 1u) * kFirDitherStep;
     };
     // a frame's two dithered codes (the undithered builds quantise below, in the statements they always had: their code is unchanged)
@@ -1511,7 +1517,15 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     };
     // a lane's four frames x two channels: 32 contiguous bytes, or (WIDE) 8 bytes in each of four frames
     auto store_frames = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, bool ph, dkey_t k) {   // (k: dithered builds, the first frame's key)
-        if constexpr (OUT) {
+        if constexpr (OUT && WIDE) {
+            // a frame of the pair is the unit: 4 bytes (4-byte aligned: the channel count is even), 6 bytes (2-byte aligned) or
+            // 8 bytes (4-byte aligned), one frame stride apart; from one frame to the next the key moves on by the frame's pairs
+            const uint64_t kstep = static_cast<uint64_t>(g.pairs) * kFirDitherStep;
+            store_frame_pcm(o, lo.x, lo.y, k);
+            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + out_stride), lo.z, lo.w, k + kstep);
+            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + 2 * out_stride), hi.x, hi.y, k + 2 * kstep);
+            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + 3 * out_stride), hi.z, hi.w, k + 3 * kstep);
+        } else if constexpr (OUT) {
             store_frames_pcm(o, lo, hi, k);
         } else if constexpr (WIDE) {
             if (kOdd && ph) {   // the last channel alone: one value per frame
@@ -1632,7 +1646,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[s][0], y1, acc1, 0, 0, 0);
             }
             // (WIDE: an even pair's sums wait for the odd pair of their block -- the next item -- and leave as 16-byte stores)
-            if (s == 0 && !(dbg & 131072) && (!WIDE || (cu.cur_pair & 1u) == 0)) {
+            // (PCM output: every pair leaves on its own, inside the next item's stream whichever pair that is)
+            if (s == 0 && !(dbg & 131072) && (!WIDE || OUT || (cu.cur_pair & 1u) == 0)) {
                 __builtin_amdgcn_sched_barrier(0);
                 flush_pending();
                 __builtin_amdgcn_sched_barrier(0);
@@ -1661,7 +1676,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
             acc0 *= __uint_as_float((e_used - 27u) << 23);    // 2^(E-141): channel 0's scale undone; 2^-13: the taps'
             acc1 *= __uint_as_float((e_used1 - 27u) << 23);   // ... channel 1's
         }
-        if (!WIDE || (cu.cur_pair & 1u) == 0) flush_pending();   // (no MFMA loop ran, or the experiment switch above)
+        if (!WIDE || OUT || (cu.cur_pair & 1u) == 0) flush_pending();   // (no MFMA loop ran, or the experiment switch above)
         // class 0 may take the wrap variant the producers left with the image (tile 0, D row 0)
         if (Tt == 0) {
             const v4f w = *reinterpret_cast<const v4f*>(lds + kCtrlBytes + slot * 256 + pl * 16);
@@ -1680,7 +1695,10 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         // in the reference's form by the repair launch
         nf_mark(g.nf, item_bad || nf_is_bad(mono || phantom(cu.cur_pair) ? (acc0.x + acc0.y) + (acc0.z + acc0.w) : nf_sum8(acc0, acc1)), d.sidx, n0, 4, n_limit);
         g_f32_ptr o;
-        if constexpr (OUT) o = (g_f32_ptr)((g_u8_ptr)d.out + static_cast<int64_t>(n0) * out_fb);   // (a byte address: out_fb bytes a frame)
+        if constexpr (OUT && WIDE) {   // (a byte address: frame n0 of the stream, the item's pair in it)
+            key_pair = cu.cur_pair;
+            o = (g_f32_ptr)((g_u8_ptr)d.out + static_cast<int64_t>(n0) * out_stride + cu.cur_pair * out_fb);
+        } else if constexpr (OUT) o = (g_f32_ptr)((g_u8_ptr)d.out + static_cast<int64_t>(n0) * out_fb);   // (a byte address: out_fb bytes a frame)
         else o = (g_f32_ptr)d.out + static_cast<int64_t>(n0) * fs + (WIDE ? 2 * cu.cur_pair : 0u);
         const v4f lo = v4f{acc0.x, acc1.x, acc0.y, acc1.y};
         const v4f hi = v4f{acc0.z, acc1.z, acc0.w, acc1.w};
@@ -1688,7 +1706,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
             const bool full = j0 + 4 <= g.b && n0 >= 0 && n0 + 4 <= n_limit;
             count_frames(d, n0, n_limit, j0, full, lo, hi);
             bool combined = false;
-            if constexpr (WIDE) {
+            if constexpr (WIDE && !OUT) {   // (PCM output: pairs are not merged, and nothing is pending here -- flushed above, before every item's stores)
                 // the odd pair of a block whose even pair is pending: four channels of a frame side by side, 16-byte stores
                 if ((cu.cur_pair & 1u) && pend && pend_o + 2 == o && __all(full) && !phantom(cu.cur_pair)) {
                     typedef v4f __attribute__((address_space(1), aligned(4)))* g_f4a4_ptr;
@@ -1720,7 +1738,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                 for (int r = 0; r < 4; ++r) {
                     const int32_t n = n0 + r;
                     if (j0 + r < g.b && n >= 0 && n < n_limit) {
-                        if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1], dither_key(d, n));
+                        if constexpr (OUT && WIDE) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_stride), v[2 * r], v[2 * r + 1], dither_key(d, n));
+                        else if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1], dither_key(d, n));
                         else if (mono) o[r] = v[2 * r];
                         else if (phantom(cu.cur_pair)) o[fs * r] = v[2 * r];
                         else if constexpr (kOdd) *((g_f2u_ptr)(o + fs * r)) = v2f{v[2 * r], v[2 * r + 1]};
@@ -1758,6 +1777,12 @@ __global__ __launch_bounds__(1024) void fir_split_pcm_tpdf_kernel(const FirStrea
 template <int NK, int ROUNDS, int BITS>
 __global__ __launch_bounds__(1024) void fir_split_pcm_stats_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
     fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcmStats>(descs, g, blockIdx.x, gridDim.x);
+}
+// PCM output from the channel-pair builds (streams of 4, 6, 8 .. 16 channels, f32 input): OUT = kFirOutPcm, kFirOutPcmTpdf or
+// kFirOutPcmStats as above; builds of their own again
+template <int NK, int ROUNDS, int OUT>
+__global__ __launch_bounds__(1024) void fir_split_pcm_wide_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
+    fir_split_body<NK, 2, false, 1, ROUNDS, 0, OUT>(descs, g, blockIdx.x, gridDim.x);
 }
 template <int NK, int PLANES, int WIDE, int ROUNDS>
 __global__ __launch_bounds__(1024) void fir_split_multi_kernel(const SplitMulti m) {
@@ -1856,6 +1881,10 @@ const void* split_kernel_for(const SplitBuild& build) {
     {SplitBuild{NK, 2, false, 0, R, B, true, true, false}, reinterpret_cast<const void*>(fir_split_pcm_tpdf_kernel<NK, R, B>)},  \
     {SplitBuild{NK, 2, false, 0, R, B, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_stats_kernel<NK, R, B>)}
 #define RSMP_SPLIT_OUT(B) RSMP_SPLIT_OUT1(5, 1, B), RSMP_SPLIT_OUT1(5, 2, B), RSMP_SPLIT_OUT1(6, 2, B)
+#define RSMP_SPLIT_OUT_WIDE(NK, R)                                                                                                          \
+    {SplitBuild{NK, 2, false, 1, R, 0, true, false, false}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcm>)},      \
+    {SplitBuild{NK, 2, false, 1, R, 0, true, true, false}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcmTpdf>)},   \
+    {SplitBuild{NK, 2, false, 1, R, 0, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcmStats>)}
 #define RSMP_SPLIT_1TO5(P, D, W) RSMP_SPLIT(1, P, D, W, 1, 0), RSMP_SPLIT(2, P, D, W, 1, 0), RSMP_SPLIT(3, P, D, W, 1, 0), RSMP_SPLIT(4, P, D, W, 1, 0), RSMP_SPLIT(5, P, D, W, 1, 0)
 #define RSMP_SPLIT_PCM(B) RSMP_SPLIT(5, 2, false, 0, 1, B), RSMP_SPLIT(5, 2, false, 0, 2, B), RSMP_SPLIT(6, 2, false, 0, 2, B)
     static const struct { SplitBuild build; const void* fn; } table[] = {
@@ -1871,7 +1900,10 @@ const void* split_kernel_for(const SplitBuild& build) {
         RSMP_SPLIT_PCM(16), RSMP_SPLIT_PCM(24), RSMP_SPLIT_PCM(32),
         // PCM output (its width read from the descriptor) from the same three builds, for f32 input and the three PCM widths, each
         // without and with TPDF dither, and counted (either dither mode)
-        RSMP_SPLIT_OUT(0), RSMP_SPLIT_OUT(16), RSMP_SPLIT_OUT(24), RSMP_SPLIT_OUT(32)};
+        RSMP_SPLIT_OUT(0), RSMP_SPLIT_OUT(16), RSMP_SPLIT_OUT(24), RSMP_SPLIT_OUT(32),
+        // ... and from the channel-pair builds of the same three windows (f32 input)
+        RSMP_SPLIT_OUT_WIDE(5, 1), RSMP_SPLIT_OUT_WIDE(5, 2), RSMP_SPLIT_OUT_WIDE(6, 2)};
+#undef RSMP_SPLIT_OUT_WIDE
 #undef RSMP_SPLIT_OUT
 #undef RSMP_SPLIT_OUT1
 #undef RSMP_SPLIT_PCM

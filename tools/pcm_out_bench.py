@@ -21,6 +21,12 @@ launch, then rsmp_f32_to_pcm_stats_device over every stream's output into a 32-b
 steps, bracketed by events on the stream (the zeroing of the launch's table, the main kernels, the repair pass and the fold that
 follow them; for the two-pass route the conversions): the handle's profiling events cover the main kernels alone, which is not
 all that the setting adds.  The rows of the table above run with the setting off.
+--channels C (default 2): streams of C channels, an even count up to 16 -- the split kernel's channel-pair builds.  They take f32
+input alone: row (d) and the PCM-input rows of --stats are left out.  (128 channel-streams as the README's channel row has them:
+--channels 8 --streams 16.)
+--rounds R (default 1): rows (b) and (c) are measured R times in alternation, b c b c ..., --reps repetitions each, in the one
+process; the rows are then over all their repetitions and carry every round's median (round_medians_ms), so that the two-pass
+route's own spread from round to round stands beside the gain.
 --convert: instead of the table, the stand-alone conversion alone -- rsmp_f32_to_pcm_device without and with dither over
 --convert-values values, and rsmp_device_stream_copy moving the same number of bytes (the conversion reads 4 and writes bits / 8
 bytes a value, the copy reads and writes 4 bytes a float) -- each bracketed by events, median of --reps bursts, with GB/s.
@@ -93,6 +99,8 @@ def main():
     ap.add_argument("--dither", choices=("none", "tpdf"), default="none")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--channels", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--convert", action="store_true")
     ap.add_argument("--convert-values", type=int, default=1 << 27)
     a = ap.parse_args()
@@ -104,17 +112,18 @@ def main():
     dev = torch.device("cuda:0")
     if a.convert:
         return convert_rows(a, torch, ra, dev)
-    S, N, chunk = a.streams, a.frames, a.chunk
+    S, N, chunk, C = a.streams, a.frames, a.chunk, a.channels
+    assert a.rounds >= 1
     dither = ra.Dither.TPDF if a.dither == "tpdf" else ra.Dither.NONE
-    hs = [ra.ResamplerFir.new(2, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000, ra.Latency.Sample64, ra.Attenuation.Db90) for _ in range(S)]
+    hs = [ra.ResamplerFir.new(C, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000, ra.Latency.Sample64, ra.Attenuation.Db90) for _ in range(S)]
     for i, h in enumerate(hs):
         h.set_pcm_dither(dither, a.seed + i)
     batch = ra.FirBatch(hs)
     batch.device_planner = False   # (the fused entry is planned on the host: the same planner for every row of the table)
-    base = torch.from_numpy(synth.sweep(N, 2, 44100.0)).to(dev)
+    base = torch.from_numpy(synth.sweep(N, C, 44100.0)).to(dev)
     gains = torch.linspace(0.5, 1.0, S, device=dev)
     d_f32 = [(base * gains[i]).contiguous() for i in range(S)]
-    cap = max(h.bulk_output_bound(2 * N, chunk) for h in hs)
+    cap = max(h.bulk_output_bound(C * N, chunk) for h in hs)
     d_out = [torch.empty(cap, device=dev) for _ in range(S)]
     batch.bind(d_f32, d_out)
     stream = ra.torch_stream()
@@ -146,6 +155,8 @@ def main():
         return times
 
     result = {"streams": S, "frames": N, "reps": a.reps, "dither": a.dither, "rows": {}}
+    if C != 2 or a.rounds != 1:
+        result.update(channels=C, rounds=a.rounds)
     produced = [0]
 
     def f32_launch(e0=None, e1=None):
@@ -158,7 +169,7 @@ def main():
     for bits in (16, 24):
         nb = bits // 8
         d_pcm_out = [torch.empty(cap * nb, dtype=torch.uint8, device=dev) for _ in range(S)]
-        d_pcm_in = [torch.empty(2 * N * nb, dtype=torch.uint8, device=dev) for _ in range(S)]
+        d_pcm_in = [torch.empty(2 * N * nb, dtype=torch.uint8, device=dev) for _ in range(S if C == 2 else 0)]
         for x, p in zip(d_f32, d_pcm_in):
             ra.f32_to_pcm_device(x, bits, p, stream)
 
@@ -178,10 +189,19 @@ def main():
             batch.resample_bulk_pcm_out_device(d_pcm_in, bits, d_pcm_out, bits, chunk, stream)
             return False
 
-        t_b, t_c, t_d = run(two_pass), run(fused_f32), run(fused_pcm)
+        t_b, t_c, med_b, med_c = [], [], [], []
+        for _ in range(a.rounds):
+            for step, times, medians in ((two_pass, t_b, med_b), (fused_f32, t_c, med_c)):
+                t = run(step)
+                times += t
+                medians.append(round(float(np.median(t)), 4))
         result["rows"][f"b_f32_output_then_f32_to_pcm_{bits}"] = stats(t_b)
         result["rows"][f"c_fused_{bits}_from_f32"] = stats(t_c)
-        result["rows"][f"d_fused_{bits}_from_pcm_{bits}"] = stats(t_d)
+        if a.rounds > 1:
+            result["rows"][f"b_f32_output_then_f32_to_pcm_{bits}"]["round_medians_ms"] = med_b
+            result["rows"][f"c_fused_{bits}_from_f32"]["round_medians_ms"] = med_c
+        if C == 2:
+            result["rows"][f"d_fused_{bits}_from_pcm_{bits}"] = stats(run(fused_pcm))
         result["rows"][f"gain_b_minus_c_{bits}_ms"] = round(float(np.median(t_b) - np.median(t_c)), 4)
         result["rows"][f"c_minus_a_{bits}_ms"] = round(float(np.median(t_c) - np.median(t_a)), 4)
         if a.stats:
@@ -202,7 +222,7 @@ def main():
                     ra.f32_to_pcm_stats_device(o[:n], bits, q, d_acc[i], stream, dither=dither, seed=a.seed + i)
 
             on_f32 = None
-            for name, step in (("f32", fused_f32), (f"pcm_{bits}", fused_pcm)):
+            for name, step in (("f32", fused_f32), (f"pcm_{bits}", fused_pcm))[:2 if C == 2 else 1]:
                 t_off = run(whole(step))
                 for h in hs:
                     h.set_pcm_stats(True)
