@@ -120,6 +120,12 @@ extern "C" {
     // addition: WAV samples (resample/src/main.rs:128-137) converted inside the FFT kernel's first load
     fn rsmp_fft_batch_resample_bulk_pcm_device(rs: *const *mut rsmp_fft, n: usize, d_pcm: *const *const std::os::raw::c_void, bits: c_int,
                                                d_out: *const *mut f32, n_chunks: *const usize, stream: *mut std::os::raw::c_void) -> c_int;
+    // addition: the FFT engine's output as a WAV file stores it -- PCM of out_bits (16 / 24 / 32) from the pair kernel's store
+    fn rsmp_fft_batch_resample_bulk_pcm_out_device(rs: *const *mut rsmp_fft, n: usize, d_in: *const *const std::os::raw::c_void, in_bits: c_int,
+                                                   d_out_pcm: *const *mut std::os::raw::c_void, out_bits: c_int, n_chunks: *const usize,
+                                                   stream: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_fft_set_pcm_dither(r: *mut rsmp_fft, dither: c_int, seed: u64) -> c_int;
+    fn rsmp_fft_pcm_dither(r: *const rsmp_fft, dither: *mut c_int, seed: *mut u64) -> c_int;
     // additions to the reference API: a fixed set of streams stepped together on device-resident state
     fn rsmp_fir_lockstep_new(rs: *const *mut rsmp_fir, n: usize, max_step_frames: usize) -> *mut rsmp_fir_lockstep;
     fn rsmp_fir_lockstep_free(ls: *mut rsmp_fir_lockstep);
@@ -378,6 +384,31 @@ impl ResamplerFft {
     pub unsafe fn resample_bulk_pcm_device(&mut self, d_pcm: *const std::os::raw::c_void, bits: u32, d_out: *mut f32, n_chunks: usize) -> Result<(), ResampleError> {
         let (h, p, o) = ([self.handle], [d_pcm], [d_out]);
         status(rsmp_fft_batch_resample_bulk_pcm_device(h.as_ptr(), 1, p.as_ptr(), bits as c_int, o.as_ptr(), &n_chunks, std::ptr::null_mut()))
+    }
+    /// Addition to the reference API: `n_chunks` chunks with the output as a WAV file stores it -- `d_out_pcm` (4-byte aligned)
+    /// receives exactly n_chunks * chunk_size_output * out_bits / 8 bytes of little-endian PCM of `out_bits` (16 / 24 / 32, 24-bit
+    /// packed), quantised where the kernel stores its frames: the bytes of `rsmp_f32_to_pcm_device` of the f32 output.  `d_in` is
+    /// interleaved f32 (`in_bits` = 0) or PCM of `in_bits`.  Two-channel streams of the pair kernel's rate pairs, at least 4 chunks;
+    /// anything else is an error before anything is launched, written or changed: take f32 output and convert.
+    /// # Safety
+    /// Device pointers with room for the sizes above.
+    pub unsafe fn resample_bulk_pcm_out_device(&mut self, d_in: *const std::os::raw::c_void, in_bits: u32, d_out_pcm: *mut std::os::raw::c_void,
+                                               out_bits: u32, n_chunks: usize) -> Result<(), ResampleError> {
+        let (h, p, o) = ([self.handle], [d_in], [d_out_pcm]);
+        status(rsmp_fft_batch_resample_bulk_pcm_out_device(h.as_ptr(), 1, p.as_ptr(), in_bits as c_int, o.as_ptr(), out_bits as c_int, &n_chunks,
+                                                           std::ptr::null_mut()))
+    }
+    /// Addition to the reference API: the dither of the PCM that `resample_bulk_pcm_out_device` writes for this stream -- none (the
+    /// default) or TPDF with the stream's seed.  Value (output frame n since the handle was made, through any entry, channel c)
+    /// takes the noise of index n * channels + c.  ResamplerFft has no reset: the sequence never starts again.
+    pub fn set_pcm_dither(&mut self, dither: Dither, seed: u64) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fft_set_pcm_dither(self.handle, dither as c_int, seed) })
+    }
+    /// (dither mode as RSMP_DITHER_*, seed) as `set_pcm_dither` left them.
+    pub fn pcm_dither(&self) -> (i32, u64) {
+        let (mut d, mut s): (c_int, u64) = (0, 0);
+        unsafe { rsmp_fft_pcm_dither(self.handle, &mut d, &mut s) };
+        (d as i32, s)
     }
     pub fn resample(&mut self, input: &[f32], output: &mut [f32]) -> Result<(), ResampleError> {
         status(unsafe {

@@ -547,6 +547,35 @@ int rsmp_fft_batch_resample_bulk_device(rsmp_fft* const* rs, size_t n, const flo
  * 8 / 4 / 16 bytes for 16 / 24 / 32 bits. */
 int rsmp_fft_batch_resample_bulk_pcm_device(rsmp_fft* const* rs, size_t n, const void* const* d_pcm, int bits,
                                             float* const* d_out, const size_t* n_chunks, void* stream);
+/* The other half of a file-to-file pipeline: the output as a WAV file stores it, written by the kernel's own store.  d_in[i] is
+ * interleaved f32 (in_bits = 0) or PCM of in_bits (16 / 24 / 32), aligned as for rsmp_fft_batch_resample_bulk_pcm_device.
+ * d_out_pcm[i], 4-byte aligned, receives exactly n_chunks[i] * chunk_size_output * out_bits / 8 bytes of little-endian PCM of
+ * `out_bits` (16 / 24 / 32; 24-bit packed at 3 bytes a sample); no byte outside that range is written.  Every value the f32
+ * entry would have stored is quantised where the kernel stores it (the rule: rsmp_f32_to_pcm above -- round half to even,
+ * saturate, NaN -> 0), so for a handle in the same state, the same n_chunks and the same batch the bytes are exactly
+ * rsmp_f32_to_pcm_device's of rsmp_fft_batch_resample_bulk_device's output, and the f32 never reaches HBM.  The overlap
+ * state stays f32 and ends bit-equal to the f32 entry's.
+ * Served: what the two-channel pair kernel serves -- two-channel streams of one of its 19 rate pairs (44.1 <-> 48 kHz,
+ * 48 <-> 96 kHz ...), at least 4 chunks in the batch's longest stream, the default library (not libresampler_amd_fftexact.so).
+ * Everything else -- other channel counts, other rate pairs, fewer than 4 chunks, the exact build, out_bits not 16 / 24 / 32,
+ * null arguments, misalignment, a mix of dither modes -- is RSMP_ERR_INVALID_ARGUMENT before any launch: nothing is written, no
+ * state and no counter changes; take f32 output and convert with rsmp_f32_to_pcm_device.
+ * Dither is a setting of the handles (rsmp_fft_set_pcm_dither below, default RSMP_DITHER_NONE).  No statistics
+ * (rsmp_pcm_stats) from this store. */
+int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, size_t n, const void* const* d_in, int in_bits,
+                                                void* const* d_out_pcm, int out_bits, const size_t* n_chunks, void* stream);
+/* Dither of the PCM the entry above writes for this handle: RSMP_DITHER_NONE (the default) or RSMP_DITHER_TPDF with the stream's
+ * `seed`; anything else is RSMP_ERR_INVALID_ARGUMENT and changes nothing.  With TPDF every value is quantised where it is stored
+ * by rsmp_f32_to_pcm_dither's rule, output frame n of a launch and channel c with the index
+ *   i = (abs_out + n) * channels + c,
+ * abs_out = the output frames the handle has produced since it was made, through ANY entry (every call that advances the
+ * overlap state advances it).  So the bytes are exactly rsmp_f32_to_pcm_dither_device's of the f32 entry's output with
+ * first_index = abs_out * channels, and a stream's bytes do not depend on how it is cut into launches.  ResamplerFft has no
+ * reset: the noise sequence of a handle never starts again.  One mode for all the streams of a batch -- a mix is
+ * RSMP_ERR_INVALID_ARGUMENT before any launch --; the seeds are per stream.  rsmp_fft_pcm_dither reads the setting back (either
+ * pointer may be NULL). */
+int rsmp_fft_set_pcm_dither(rsmp_fft* r, int dither, uint64_t seed);
+int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* seed);
 
 /* host-only: block sizes and the N/2-point Stockham stage lists for a rate pair
  * (planner.rs:35-245, optimizer.rs:6-64, radix_fft.rs:222-246). */

@@ -243,6 +243,10 @@ _SIGNATURES = [
       C.c_void_p]),
     ("rsmp_fft_batch_resample_bulk_pcm_device", C.c_int,
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), _szp, C.c_void_p]),
+    ("rsmp_fft_batch_resample_bulk_pcm_out_device", C.c_int,
+     [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, _szp, C.c_void_p]),
+    ("rsmp_fft_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    ("rsmp_fft_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     ("rsmp_fft_plan_sizes", C.c_int,
      [C.c_uint32, C.c_uint32, _szp, _szp, C.POINTER(C.c_int), _szp, C.POINTER(C.c_int), _szp, C.c_size_t]),
 ]
@@ -874,6 +878,19 @@ class ResamplerFft:
                                                    _dev_ptr(d_out), d_out.numel(), n_chunks,
                                                    C.c_void_p(stream or 0)))
 
+    def set_pcm_dither(self, dither: int, seed: int = 0) -> None:
+        """Dither of the PCM that FftBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fft_set_pcm_dither): Dither.NONE
+        (the default) or Dither.TPDF with the stream's own seed.  Output frame n of the stream, counted since the handle was made
+        through any entry, channel c, takes the noise of index n * channels + c -- f32_to_pcm_device(..., dither, seed,
+        first_index) of the float32 output gives the same bytes.  There is no reset: the sequence never starts again."""
+        _check(lib().rsmp_fft_set_pcm_dither(self._h, int(dither), int(seed) & _U64))
+
+    def pcm_dither(self) -> Tuple[int, int]:
+        """(dither mode, seed) as set_pcm_dither left them."""
+        d, s = C.c_int(), C.c_uint64()
+        _check(lib().rsmp_fft_pcm_dither(self._h, C.byref(d), C.byref(s)))
+        return d.value, s.value
+
 
 class FftBatch:
     """N ResamplerFft instances with one rate pair on one device, one launch per step."""
@@ -910,6 +927,26 @@ class FftBatch:
             pin[i], pout[i], ch[i] = a.data_ptr(), _dev_ptr(b), k
         self._keep_pcm = (list(d_pcms), list(d_outs))
         _check(lib().rsmp_fft_batch_resample_bulk_pcm_device(self._handles, n, pin, bits, pout, ch, C.c_void_p(stream or 0)))
+
+    def resample_bulk_pcm_out_device(self, d_ins, in_bits: int, d_out_pcms, out_bits: int, n_chunks: Sequence[int],
+                                     stream: Optional[int] = None) -> None:
+        """The bulk launch with the output as a WAV file stores it (rsmp_fft_batch_resample_bulk_pcm_out_device): d_out_pcms =
+        uint8 tensors that receive exactly n_chunks[i] * chunk_size_output * out_bits / 8 bytes of little-endian PCM of `out_bits`
+        (16 / 24 / 32), quantised where the kernel stores its frames (f32_to_pcm's rule; with the dither the streams were given by
+        ResamplerFft.set_pcm_dither -- one mode for all of them).  d_ins = float32 tensors (in_bits = 0) or uint8 tensors of PCM of
+        `in_bits`.  Two-channel streams of the pair kernel's rate pairs (44.1 <-> 48, 48 <-> 96 kHz ...), at least 4 chunks in the
+        longest stream; anything else raises ResampleError before anything is launched, written or changed: take float32 output
+        and f32_to_pcm_device."""
+        n = len(self.resamplers)
+        pin, pout, ch = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_size_t * n)()
+        for i, (a, b, k) in enumerate(zip(d_ins, d_out_pcms, n_chunks)):
+            r = self.resamplers[i]
+            assert b.is_cuda and b.is_contiguous() and str(b.dtype) == "torch.uint8"
+            assert a.numel() * a.element_size() >= k * r.chunk_size_input() * (in_bits // 8 if in_bits else 4)
+            assert b.numel() * 8 >= k * r.chunk_size_output() * out_bits
+            pin[i], pout[i], ch[i] = (_dev_ptr(a) if in_bits == 0 else a.data_ptr()), b.data_ptr(), k
+        self._keep_pcm = (list(d_ins), list(d_out_pcms))
+        _check(lib().rsmp_fft_batch_resample_bulk_pcm_out_device(self._handles, n, pin, in_bits, pout, out_bits, ch, C.c_void_p(stream or 0)))
 
 
 class InterpolationMode(enum.IntEnum):

@@ -23,6 +23,7 @@
 
 using rsmp::DeviceBuffer;
 using rsmp::DeviceGuard;
+using rsmp::FftPcmOutDesc;
 using rsmp::FftPlanDev;
 using rsmp::FftStreamDesc;
 using rsmp::PinnedBuffer;
@@ -154,6 +155,11 @@ struct rsmp_fft {
     std::shared_ptr<DevicePlan> plan;
     float* d_overlap = nullptr;   // 2 x [channels][fft_out] (ping-pong per launch), zero at construction (:81)
     int cur = 0;
+    // output frames produced since the handle was made, through any entry (there is no reset): where the dither sequence of
+    // the next PCM-output launch starts (rsmp_fft_set_pcm_dither)
+    uint64_t abs_out = 0;
+    int pcm_dither = RSMP_DITHER_NONE;
+    uint64_t pcm_dither_seed = 0;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // the stream of the handle's previous launch (launches of one handle are ordered)
     bool last_stream_valid = false;
@@ -189,9 +195,13 @@ struct FftJob {
     size_t n_blocks;
 };
 
-int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0) {
+// out_bits != 0: the jobs' d_out are byte buffers that receive PCM of that width (the caller has asked fft_pcm_out_served);
+// the streams' FftPcmOutDesc travel behind the descriptors, in the same table.
+int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0) {
     const size_t n = jobs.size();
-    const size_t bytes = n * sizeof(FftStreamDesc);
+    static_assert(sizeof(FftStreamDesc) % alignof(FftPcmOutDesc) == 0, "the PCM-output array starts where the descriptors end");
+    const size_t desc_bytes = n * sizeof(FftStreamDesc);
+    const size_t bytes = desc_bytes + (out_bits != 0 ? n * sizeof(FftPcmOutDesc) : 0);
     // A handle's launches are ordered (&mut self in the reference): launch k + 1 reads the overlap rows launch k
     // writes, so a caller that changes streams between two calls waits here for the first -- as the FIR path does.
     // A handle listed twice in one batch would read one old state through both descriptors: refused.
@@ -248,11 +258,14 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
         h[i].n_blocks = static_cast<uint32_t>(j.n_blocks);
         h[i].channels = static_cast<uint32_t>(j.r->channels);
         h[i].in_bits = pcm_bits;
-        h[i].pad = 0;
+        h[i].out_bits = out_bits;
         if (h[i].n_blocks > max_blocks) max_blocks = h[i].n_blocks;
         if (h[i].channels > max_channels) max_channels = h[i].channels;
         if (h[i].channels < min_channels) min_channels = h[i].channels;
     }
+    FftPcmOutDesc* h_pcm = out_bits != 0 ? reinterpret_cast<FftPcmOutDesc*>(h + n) : nullptr;
+    for (size_t i = 0; h_pcm && i < n; ++i)
+        h_pcm[i] = FftPcmOutDesc{jobs[i].r->pcm_dither_seed, jobs[i].r->abs_out, static_cast<uint32_t>(jobs[i].r->pcm_dither), 0};
     const FftStreamDesc* d_descs = h;   // (mapped host memory: the same address on the device)
     if (!direct) {
         RSMP_HIP_CHECK(hipMemcpyAsync(leader->d_desc.get(), h, bytes, hipMemcpyHostToDevice, stream));
@@ -260,10 +273,11 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
         leader->desc_pending = true;
         d_descs = leader->d_desc.as<FftStreamDesc>();
     }
+    const FftPcmOutDesc* d_pcm = out_bits != 0 ? reinterpret_cast<const FftPcmOutDesc*>(d_descs + n) : nullptr;
     if (leader->profiling) RSMP_HIP_CHECK(rsmp::event_record(leader->prof_start, stream));
     {
         const hipError_t e = rsmp::launch_fft_ola(leader->plan->dev, d_descs, static_cast<uint32_t>(n),
-                                                  max_blocks, max_channels, min_channels, stream, pcm_bits);
+                                                  max_blocks, max_channels, min_channels, stream, pcm_bits, out_bits, d_pcm);
         if (e == hipErrorNotSupported && pcm_bits != 0)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "ResamplerFft: PCM input is read in place by the two-channel wave kernel only "
                                                        "(this rate pair / channel count has none): convert with rsmp_pcm_to_stereo_f32_device first");
@@ -284,6 +298,7 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
     }
     for (const FftJob& j : jobs) {
         if (j.n_blocks != 0) j.r->cur ^= 1;   // (a stream without blocks in this launch keeps its state where it is)
+        j.r->abs_out += j.n_blocks * j.r->plan->host.fft_out;
         j.r->last_launch = leader->launch_ev;
     }
     return RSMP_OK;
@@ -484,4 +499,59 @@ extern "C" int rsmp_fft_batch_resample_bulk_pcm_device(rsmp_fft* const* rs, size
     jobs.reserve(n);
     for (size_t i = 0; i < n; ++i) jobs.push_back(FftJob{rs[i], static_cast<const float*>(d_pcm[i]), d_out[i], n_chunks[i]});
     return launch_fft_jobs(rs[0], jobs, s, static_cast<uint32_t>(bits));
+}
+
+// The other half of a file-to-file pipeline: the pair kernel stores PCM of `out_bits` (fft_pair_pcm_out.hip).  Everything that
+// kernel does not serve is refused here, before launch_fft_jobs touches a handle.
+extern "C" int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, size_t n, const void* const* d_in, int in_bits,
+                                                           void* const* d_out_pcm, int out_bits, const size_t* n_chunks, void* stream) {
+    static const char* const kWayOut = "take f32 output and convert with rsmp_f32_to_pcm_device";
+    if (n == 0) return RSMP_OK;
+    if (!rs || !d_in || !d_out_pcm || !n_chunks)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_batch_resample_bulk_pcm_out_device: null argument (%s)", kWayOut);
+    if ((in_bits != 0 && in_bits != 16 && in_bits != 24 && in_bits != 32) || (out_bits != 16 && out_bits != 24 && out_bits != 32))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_batch_resample_bulk_pcm_out_device: in_bits 0 / 16 / 24 / 32, out_bits 16 / 24 / 32 (%s)", kWayOut);
+    size_t max_blocks = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!rs[i] || rs[i]->device != rs[0]->device || rs[i]->plan != rs[0]->plan || rs[i]->channels != 2)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one device and one rate pair and have two channels (%s)", kWayOut);
+        if (rs[i]->pcm_dither != rs[0]->pcm_dither)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one dither mode: stream %zu differs (%s)", i, kWayOut);
+        if (!d_in[i] || !d_out_pcm[i])
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_batch_resample_bulk_pcm_out_device: null buffer of stream %zu (%s)", i, kWayOut);
+        if (in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % (in_bits == 32 ? 16 : in_bits == 16 ? 8 : 4) != 0)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input must be aligned to 8 (16-bit), 4 (24-bit) or 16 (32-bit) bytes (%s)", kWayOut);
+        if (reinterpret_cast<uintptr_t>(d_out_pcm[i]) % 4 != 0)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output must be aligned to 4 bytes (%s)", kWayOut);
+        if (n_chunks[i] > 0xFFFFFFFFu)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_batch_resample_bulk_pcm_out_device: too many chunks (%s)", kWayOut);
+        max_blocks = std::max(max_blocks, n_chunks[i]);
+    }
+    if (max_blocks == 0) return RSMP_OK;
+    DeviceGuard guard(rs[0]->device);
+    if (!rsmp::fft_pcm_out_served(rs[0]->plan->dev, static_cast<uint32_t>(n), static_cast<uint32_t>(max_blocks), static_cast<uint32_t>(in_bits),
+                                  static_cast<uint32_t>(out_bits)))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "ResamplerFft: PCM output is stored by the two-channel pair kernel only -- one of its rate pairs, at least "
+                                                   "4 chunks in the longest stream, not the exact build: %s", kWayOut);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : rs[0]->stream;
+    std::vector<FftJob> jobs;
+    jobs.reserve(n);
+    for (size_t i = 0; i < n; ++i)
+        jobs.push_back(FftJob{rs[i], static_cast<const float*>(d_in[i]), static_cast<float*>(d_out_pcm[i]), n_chunks[i]});
+    return launch_fft_jobs(rs[0], jobs, s, static_cast<uint32_t>(in_bits), static_cast<uint32_t>(out_bits));
+}
+
+extern "C" int rsmp_fft_set_pcm_dither(rsmp_fft* r, int dither, uint64_t seed) {
+    if (!r || (dither != RSMP_DITHER_NONE && dither != RSMP_DITHER_TPDF))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_set_pcm_dither: null handle, or dither not RSMP_DITHER_NONE / RSMP_DITHER_TPDF");
+    r->pcm_dither = dither;
+    r->pcm_dither_seed = seed;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* seed) {
+    if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_dither: null handle");
+    if (dither) *dither = r->pcm_dither;
+    if (seed) *seed = r->pcm_dither_seed;
+    return RSMP_OK;
 }

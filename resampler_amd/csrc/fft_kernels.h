@@ -39,18 +39,33 @@ struct FftStreamDesc {
     uint32_t n_blocks;
     uint32_t channels;
     uint32_t in_bits;     // 0: `in` is f32; 16 / 24 / 32: `in` is little-endian PCM of that width (two-channel streams on the wave kernel only)
-    uint32_t pad;
+    uint32_t out_bits;    // 0: `out` receives f32; 16 / 24 / 32: `out` is a byte buffer that receives little-endian PCM of that width
+                          // (24-bit packed), n_blocks * fft_out frames (the PCM-output builds of the pair kernel only: no other kernel reads it)
+};
+// What the PCM-output builds know about a stream beyond its FftStreamDesc: an array parallel to the descriptors, passed to
+// those builds alone.  Value (frame n of the launch, channel c) takes the noise of index (abs_out + n) * 2 + c (fir_pcm_dither).
+struct FftPcmOutDesc {
+    uint64_t seed;        // the stream's own
+    uint64_t abs_out;     // output frames the handle had produced before this launch
+    uint32_t dither;      // RSMP_DITHER_NONE / RSMP_DITHER_TPDF: one mode for all the streams of a launch
+    uint32_t reserved;
 };
 
 // pcm_bits != 0: every stream's `in` is PCM of that width (FftStreamDesc::in_bits); hipErrorNotSupported where no kernel
 // that reads PCM serves the plan / channel count.  Which kernel, grid, block and LDS a launch gets: fft_launch.h.
+// out_bits != 0 (with d_pcm, the streams' FftPcmOutDesc): every stream's `out` receives PCM of that width
+// (FftStreamDesc::out_bits); hipErrorNotSupported where the launch is not the pair kernel's (fft_pcm_out_served).
 hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
                           uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                          hipStream_t stream, uint32_t pcm_bits = 0);
+                          hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0, const FftPcmOutDesc* d_pcm = nullptr);
+// Whether a launch of two-channel streams with PCM output gets a kernel: asked before anything is touched.
+bool fft_pcm_out_served(const FftPlanDev& plan, uint32_t n_streams, uint32_t max_blocks, uint32_t pcm_bits, uint32_t out_bits);
 // The kernel files' launchers: the build `c` names (fft_choose), launched as it says; hipErrorNotSupported where the file
 // was not built with it (the timing experiments' builds).  fft_pair.hip: one wave per two-channel stream, the frame
 // (L, R) as the complex sample L + i R; fft_wave.hip: a wave per channel; fft_kernels.hip: the workgroup kernels.
 hipError_t launch_fft_ola_pair(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream);
+hipError_t launch_fft_ola_pair_pcm_out(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, const FftPcmOutDesc* d_pcm,
+                                       hipStream_t stream);   // fft_pair_pcm_out.hip: the pair launch of a request with out_bits != 0
 hipError_t launch_fft_ola_wave(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream);
 hipError_t launch_fft_ola_workgroup(FftLaunch c, const FftRequest& rq, const FftPlanDev& plan, const FftStreamDesc* d_descs,
                                     hipStream_t stream);

@@ -200,10 +200,13 @@ FftLaunch fft_choose(const FftShape& s, const FftRequest& rq) {
     const bool stereo = rq.max_channels == 2 && rq.min_channels == 2;
     // (PCM input is read by the two-channel kernels only: FftStreamDesc::in_bits)
     if (rq.pcm_bits != 0 && (no_wave || !stereo)) return out;
+    if (rq.out_bits != 0 && rq.out_bits != 16 && rq.out_bits != 24 && rq.out_bits != 32) return out;
     // two-channel streams: a wave per stream, the frame as one complex sample (not in the exact build)
     // (a launch of a block or two per stream is a streaming call: there the wave-per-channel kernel's two waves per stream
     // finish sooner than one wave running both chains -- 32.6 against 36.3 us per one-block call, tools/fft_call_latency.py)
     if (!no_wave && !no_pair && stereo && rq.max_blocks >= 4 && !rq.exact && choose_pair(s, rq, &out)) return out;
+    // (PCM output is stored by the pair kernel only: FftStreamDesc::out_bits)
+    if (rq.out_bits != 0) return FftLaunch{};
     if (!no_wave && (choose_wave(s, rq, &out) || rq.pcm_bits != 0)) return out;
     choose_workgroup(s, rq, &out);
     return out;

@@ -25,6 +25,9 @@ struct FftRequest {
     uint32_t pcm_bits;                    // 0: f32 input
     bool exact;                           // fft_wave_is_exact(): whole twiddle rows in the wave kernels, no pair kernel
     int cus;
+    // 0: f32 output.  16 / 24 / 32: PCM of that width from the kernel's store -- the pair kernel's launch exactly as for
+    // out_bits = 0 (the same cut into runs), kNotSupported where that request would get another family.
+    uint32_t out_bits = 0;
 };
 
 enum class FftFamily : uint8_t {

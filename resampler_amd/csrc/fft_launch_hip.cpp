@@ -22,17 +22,31 @@ FftShape shape_of(const FftPlanDev& p) {
 size_t fft_big_lds_bytes(const FftPlanDev& plan) { return fft_big_lds_bytes(shape_of(plan)); }
 size_t fft_ola_lds_bytes(const FftPlanDev& plan, uint32_t channels) { return fft_ola_lds_bytes(shape_of(plan), channels); }
 
-hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
-                          uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                          hipStream_t stream, uint32_t pcm_bits) {
-    if (n_streams == 0 || max_blocks == 0) return hipSuccess;
+namespace {
+
+FftRequest request_of(uint32_t n_streams, uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels, uint32_t pcm_bits, uint32_t out_bits) {
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const FftRequest rq{n_streams, max_blocks, max_channels, min_channels, pcm_bits, fft_wave_is_exact(), cus};
+    return FftRequest{n_streams, max_blocks, max_channels, min_channels, pcm_bits, fft_wave_is_exact(), cus, out_bits};
+}
+
+}  // namespace
+
+bool fft_pcm_out_served(const FftPlanDev& plan, uint32_t n_streams, uint32_t max_blocks, uint32_t pcm_bits, uint32_t out_bits) {
+    if (n_streams == 0 || max_blocks == 0 || out_bits == 0) return false;
+    return fft_choose(shape_of(plan), request_of(n_streams, max_blocks, 2, 2, pcm_bits, out_bits)).family == FftFamily::kPair;
+}
+
+hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
+                          uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
+                          hipStream_t stream, uint32_t pcm_bits, uint32_t out_bits, const FftPcmOutDesc* d_pcm) {
+    if (n_streams == 0 || max_blocks == 0) return hipSuccess;
+    const FftRequest rq = request_of(n_streams, max_blocks, max_channels, min_channels, pcm_bits, out_bits);
     const FftLaunch c = fft_choose(shape_of(plan), rq);
     switch (c.family) {
-        case FftFamily::kPair: return launch_fft_ola_pair(c, plan, d_descs, stream);
+        case FftFamily::kPair:
+            return out_bits != 0 ? launch_fft_ola_pair_pcm_out(c, plan, d_descs, d_pcm, stream) : launch_fft_ola_pair(c, plan, d_descs, stream);
         case FftFamily::kWave: return launch_fft_ola_wave(c, plan, d_descs, stream);
         case FftFamily::kNotSupported: return hipErrorNotSupported;
         case FftFamily::kInvalid: return hipErrorInvalidValue;
