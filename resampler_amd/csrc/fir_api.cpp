@@ -238,8 +238,7 @@ int run_staged(rsmp_fir* r, const float* in, size_t in_len, float* out, size_t o
 
 // One launch of a list of streams: a plan per distinct (state, amount of input), then launch_jobs led by the first handle.
 int batch_bulk_piece(rsmp_fir* const* rs, size_t n, const float* const* d_in, const size_t* in_lens, size_t chunk_len,
-                     float* const* d_out, const size_t* out_caps, size_t* consumed, size_t* produced, void* stream, uint32_t pcm_bits = 0,
-                     uint32_t out_bits = 0) {
+                     float* const* d_out, const size_t* out_caps, size_t* consumed, size_t* produced, void* stream, const rsmp::FirFormat& format = {}) {
     switch (rsmp::batch_handles_fault(rs, n)) {
         case rsmp::BatchFault::NullOrOtherDevice: return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "batch streams must share one device");
         case rsmp::BatchFault::Duplicate: return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "batch lists the same stream twice");
@@ -299,7 +298,7 @@ int batch_bulk_piece(rsmp_fir* const* rs, size_t n, const float* const* d_in, co
                               j.plan->produced_frames * rs[i]->channels, out_caps[i]);
     }
     const auto t_planned = std::chrono::steady_clock::now();
-    const int rc = launch_jobs(rs[0], jobs, s, pcm_bits, out_bits);
+    const int rc = launch_jobs(rs[0], jobs, s, format);
     if (rc != RSMP_OK) return rc;
     if (verbose_t) {
         const auto t_end = std::chrono::steady_clock::now();
@@ -312,6 +311,40 @@ int batch_bulk_piece(rsmp_fir* const* rs, size_t n, const float* const* d_in, co
         if (produced) produced[i] = jobs[i].produced();
     }
     return RSMP_OK;
+}
+
+// Both PCM entries.  Before anything is planned: the arguments (required_bits: the entry's own width, which may not be 0), the format -- the
+// widths and the handles' settings as one FirFormat -- against every stream (format_stream_fault; the periodic groups' part of the rule is
+// launch_jobs'), one dither mode and statistics for all or none, the PCM buffers' alignment, and at most one launch's worth of input per
+// stream.  Then one launch, the buffers under the types of the f32 path (the kernels read the descriptors' in_bits / out_bits).
+template <class Out>
+int pcm_call(const char* entry, rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits, const size_t* in_lens, size_t chunk_len,
+             Out* const* d_out, int out_bits, const size_t* out_caps, int required_bits, size_t* consumed, size_t* produced, void* stream) {
+    if (n == 0) return RSMP_OK;
+    if (!rs || !rs[0] || !d_in || !in_lens || !d_out || !out_caps || chunk_len == 0 || required_bits == 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "%s: null / zero argument", entry);
+    const rsmp::FirFormat f{static_cast<uint32_t>(in_bits), static_cast<uint32_t>(out_bits),   // (the handles' settings: read only where PCM is written)
+                            out_bits != 0 ? static_cast<uint32_t>(rs[0]->pcm_dither) : 0u, out_bits != 0 && rs[0]->pcm_stats};
+    std::vector<const float*> in(n);
+    std::vector<float*> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!rs[i]) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "%s: null stream", entry);
+        const size_t ch = rs[i]->channels;
+        if (const rsmp::FormatFault fault = rsmp::format_stream_fault(f, ch); fault != rsmp::FormatFault::kNone)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "%s", rsmp::format_fault_text(fault));
+        if (out_bits != 0 && static_cast<uint32_t>(rs[i]->pcm_dither) != f.dither)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: one dither mode for all the streams of a batch (rsmp_fir_set_pcm_dither; the seeds may differ)");
+        if (out_bits != 0 && rs[i]->pcm_stats != f.stats)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: statistics for all the streams of a batch or for none (rsmp_fir_set_pcm_stats)");
+        if ((in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) || (out_bits != 0 && reinterpret_cast<uintptr_t>(d_out[i]) % 4 != 0))
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input and output must be 4-byte aligned");
+        // (a launch's coefficient rows are mixed for one drift: more input -- 16 minutes of audio -- goes through the f32 entry point, which cuts it)
+        if (chunk_len % ch == 0 && in_lens[i] % ch == 0 && in_lens[i] > rsmp::launch_input_values(rs[i]->mirror.ratio(), ch, chunk_len))
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "%s: more than one launch's worth of input (46 M outputs)", entry);
+        in[i] = static_cast<const float*>(d_in[i]);
+        out[i] = static_cast<float*>(d_out[i]);
+    }
+    return batch_bulk_piece(rs, n, in.data(), in_lens, chunk_len, out.data(), out_caps, consumed, produced, stream, f);
 }
 
 }  // namespace
@@ -661,22 +694,7 @@ extern "C" int rsmp_fir_batch_resample_bulk_device_ex(rsmp_fir* const* rs, size_
 extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size_t n, const void* const* d_pcm, int bits,
                                                        const size_t* in_lens, size_t chunk_len, float* const* d_out,
                                                        const size_t* out_caps, size_t* consumed, size_t* produced, void* stream) {
-    if (n == 0) return RSMP_OK;
-    if (!rs || !d_pcm || !in_lens || !d_out || !out_caps || chunk_len == 0 || (bits != 16 && bits != 24 && bits != 32))
-        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_device: null / zero argument, or bits not 16 / 24 / 32");
-    std::vector<const float*> in(n);
-    for (size_t i = 0; i < n; ++i) {
-        if (!rs[i] || rs[i]->channels != 2)
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_device: two-channel streams only");
-        if (reinterpret_cast<uintptr_t>(d_pcm[i]) % 4 != 0)
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input must be 4-byte aligned");
-        // (a launch's coefficient rows are mixed for one drift: a stream offered more than one launch's worth of input
-        // goes through the f32 entry point, which cuts it -- 16 minutes of audio)
-        if (chunk_len % 2 == 0 && in_lens[i] % 2 == 0 && in_lens[i] > rsmp::launch_input_values(rs[i]->mirror.ratio(), 2, chunk_len))
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_device: more than one launch's worth of input (46 M outputs)");
-        in[i] = static_cast<const float*>(d_pcm[i]);
-    }
-    return batch_bulk_piece(rs, n, in.data(), in_lens, chunk_len, d_out, out_caps, consumed, produced, stream, static_cast<uint32_t>(bits));
+    return pcm_call("rsmp_fir_batch_resample_bulk_pcm_device", rs, n, d_pcm, bits, in_lens, chunk_len, d_out, 0, out_caps, bits, consumed, produced, stream);
 }
 
 // The same with the output as a WAV file stores it: d_out_pcm[i] receives little-endian PCM of `out_bits` (16 / 24 / 32; 24-bit
@@ -684,41 +702,16 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
 // per-frame stores, the generic kernels, the repair pass.  Input: interleaved f32 (in_bits = 0) or PCM as above.  Counts, end states
 // and buffered frames (f32) are those of rsmp_fir_batch_resample_bulk_device; the bytes are rsmp_f32_to_pcm_device's of that
 // entry's output, without the f32 ever reaching HBM (f32 written, f32 read, PCM written: two passes less).
-// Handles set to RSMP_DITHER_TPDF (rsmp_fir_set_pcm_dither; all of a batch or none: launch_jobs refuses a mix) add their noise at
+// Handles set to RSMP_DITHER_TPDF (rsmp_fir_set_pcm_dither; all of a batch or none: the entry refuses a mix) add their noise at
 // the same sites, value (frame n of the launch, channel c) with index (abs_out + n) * channels + c -- rsmp_f32_to_pcm_dither_device's
 // bytes with the handle's seed and first_index = abs_out * channels.
 // Handles set to count (rsmp_fir_set_pcm_stats; all of a batch or none) take the kernels' counting builds: the same bytes, and
 // rsmp_f32_to_pcm_stats's statistics of them in the handles' totals.
-// Streams: two channels (f32 or PCM input), or -- f32 input -- an even count of 4 .. 16 channels, written by the split kernel's
-// channel-pair builds a frame of a pair at a time (the same contract with `channels` for 2; launch_jobs holds the periodic groups
-// to the three 128-tap windows; streams it plans generic go to the latency kernel at any length).  One channel, odd counts, more than 16 and PCM input of other than two channels are refused here.
+// Which streams and launches: format_stream_fault and format_group_fault (fir_geometry.cpp).  Even counts of 4 .. 16 channels are written by the
+// split kernel's channel-pair builds a frame of a pair at a time; streams that are planned generic go to the latency kernel at any length.
 extern "C" int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                            const size_t* in_lens, size_t chunk_len, void* const* d_out_pcm, int out_bits,
                                                            const size_t* out_caps, size_t* consumed, size_t* produced, void* stream) {
-    if (n == 0) return RSMP_OK;
-    if (!rs || !d_in || !in_lens || !d_out_pcm || !out_caps || chunk_len == 0 || (in_bits != 0 && in_bits != 16 && in_bits != 24 && in_bits != 32) ||
-        (out_bits != 16 && out_bits != 24 && out_bits != 32))
-        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: null / zero argument, in_bits not 0 / 16 / 24 / 32 or "
-                                                     "out_bits not 16 / 24 / 32 (any other format: f32 output and rsmp_f32_to_pcm_device)");
-    std::vector<const float*> in(n);
-    std::vector<float*> out(n);
-    for (size_t i = 0; i < n; ++i) {
-        if (!rs[i]) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: null stream");
-        const size_t ch = rs[i]->channels;
-        if (in_bits != 0 && ch != 2)
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: PCM input: two-channel streams only "
-                                                         "(rsmp_pcm_to_stereo_f32_device converts a stereo file; pass any other count as f32)");
-        if (ch % 2 != 0 || ch > 16)
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: two-channel streams only or, from f32 input, "
-                                                         "an even count up to 16; one channel, odd counts, more than 16: f32 output and rsmp_f32_to_pcm_device");
-        if ((in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) || reinterpret_cast<uintptr_t>(d_out_pcm[i]) % 4 != 0)
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input and output must be 4-byte aligned");
-        // (one launch: a stream offered more than a launch's worth of input goes through the f32 entry point, which cuts it)
-        if (chunk_len % ch == 0 && in_lens[i] % ch == 0 && in_lens[i] > rsmp::launch_input_values(rs[i]->mirror.ratio(), ch, chunk_len))
-            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_batch_resample_bulk_pcm_out_device: more than one launch's worth of input (46 M outputs)");
-        in[i] = static_cast<const float*>(d_in[i]);
-        out[i] = static_cast<float*>(d_out_pcm[i]);
-    }
-    return batch_bulk_piece(rs, n, in.data(), in_lens, chunk_len, out.data(), out_caps, consumed, produced, stream, static_cast<uint32_t>(in_bits),
-                            static_cast<uint32_t>(out_bits));
+    return pcm_call("rsmp_fir_batch_resample_bulk_pcm_out_device", rs, n, d_in, in_bits, in_lens, chunk_len, d_out_pcm, out_bits, out_caps, out_bits,
+                    consumed, produced, stream);
 }

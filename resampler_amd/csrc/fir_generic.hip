@@ -378,14 +378,15 @@ __global__ __launch_bounds__(kBlock) void fir_pcm_stats_fold_kernel(const uint32
 }  // namespace
 
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done, bool* done_attached, uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
+                             hipEvent_t done, bool* done_attached, const FirFormat& format, const FirStatArgs& st) {
     if (n_streams == 0 || !nf.words || nf.chunks == 0) return hipSuccess;
     const uint32_t total = n_streams * nf.chunks;
-    if (st && st->table && out_bits != 0) {   // the counting build (never the last launch: the fold follows)
-        hipLaunchKernelGGL(fir_repair_pcm_stats_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf, *st);
+    const FirOut mode = format.out_mode();
+    if (mode == kFirOutPcmStats) {   // the counting build (never the last launch: the fold follows)
+        if (!st.table) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(fir_repair_pcm_stats_kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, d_descs, n_streams, nf, st);
         return hipGetLastError();
     }
-    const FirOut mode = fir_out_mode(out_bits, dither);
     const auto kernel = mode == kFirOutPcmTpdf ? fir_repair_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_repair_pcm_out_kernel : fir_repair_kernel;
     if (done && done_attached) {
         hipExtLaunchKernelGGL(kernel, dim3(total < 512 ? total : 512), dim3(kBlock), 0, stream, nullptr, done, 0,
@@ -398,11 +399,11 @@ hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, c
 }
 
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs,
-                                   uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached, uint32_t out_bits,
-                                   uint32_t dither, const FirStatArgs* st) {
+                                   uint32_t n_tail, uint32_t max_tail_values, hipEvent_t done, bool* done_attached, const FirFormat& format, const FirStatArgs& st) {
     if (done_attached) *done_attached = false;
-    const bool counting = st && st->table && out_bits != 0;   // RepairJob::stat_first places each job in the launch's table
-    const FirOut mode = fir_out_mode(out_bits, dither);
+    const FirOut mode = format.out_mode();
+    const bool counting = mode == kFirOutPcmStats;   // RepairJob::stat_first places each job in the launch's table
+    if (counting && !st.table) return hipErrorInvalidValue;
     const auto kernel = mode == kFirOutPcmTpdf ? fir_repair_multi_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_repair_multi_pcm_out_kernel : fir_repair_multi_kernel;
     bool tail_left = tail_descs != nullptr && n_tail != 0 && max_tail_values != 0;
     for (size_t j = 0; j < n_jobs;) {
@@ -414,7 +415,7 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
             m.descs[n] = jobs[j].d_descs;
             m.n_streams[n] = jobs[j].n_streams;
             m.nf[n] = jobs[j].nf;
-            if (counting) tables.table[n] = st->table + static_cast<size_t>(jobs[j].stat_first) * st->chunks * 4;
+            if (counting) tables.table[n] = st.table + static_cast<size_t>(jobs[j].stat_first) * st.chunks * 4;
             max_total = std::max(max_total, jobs[j].n_streams * jobs[j].nf.chunks);
             ++n;
         }
@@ -429,7 +430,7 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
         }
         const dim3 grid(max_total < 512 ? max_total : 512, n + (with_tail ? 1u : 0u));
         if (counting) {
-            tables.chunks = st->chunks;
+            tables.chunks = st.chunks;
             hipLaunchKernelGGL(fir_repair_multi_pcm_stats_kernel, grid, dim3(kBlock), 0, stream, m, tables);
             if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
             continue;
@@ -447,16 +448,16 @@ hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStre
 }
 
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, uint32_t out_bits, uint32_t dither,
-                              const FirStatArgs* st) {
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail, const FirFormat& format, const FirStatArgs& st) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
     const uint32_t cz = (max_channels + kChannelsPerBlock - 1) / kChannelsPerBlock;
     const dim3 grid((max_out + kFirTile - 1) / kFirTile, n_streams, cz ? cz : 1);
-    if (st && st->table && out_bits != 0) {
-        hipLaunchKernelGGL(fir_generic_pcm_stats_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u, *st);
+    const FirOut mode = format.out_mode();
+    if (mode == kFirOutPcmStats) {
+        if (!st.table) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(fir_generic_pcm_stats_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u, st);
         return hipGetLastError();
     }
-    const FirOut mode = fir_out_mode(out_bits, dither);
     hipLaunchKernelGGL(mode == kFirOutPcmTpdf ? fir_generic_pcm_tpdf_kernel : mode == kFirOutPcm ? fir_generic_pcm_out_kernel : fir_generic_kernel, grid, dim3(kBlock), 0, stream, d_descs, fuse_tail ? 1u : 0u);
     return hipGetLastError();
 }

@@ -399,9 +399,9 @@ uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double 
 
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels, uint32_t uniform_taps,
-                                   uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
+                                   const FirFormat& format, const FirStatArgs& st) {
     if (n_streams == 0 || max_out == 0) return hipSuccess;
-    if (out_bits != 0 && uniform_channels != 2) return hipErrorNotSupported;
+    if (!generic_tiled_ok(format, uniform_channels, uniform_channels)) return hipErrorNotSupported;
     const uint32_t tile = fir_generic_bulk_tile(max_channels, max_taps, max_ratio);
     if (tile == 0) return hipErrorNotSupported;
     const uint32_t cap = kBulkWindowBytes / (4u * max_channels);
@@ -419,7 +419,8 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
                                                 reinterpret_cast<const void*>(fir_generic_bulk_pcm_tpdf_kernel<true>)};
     static const void* const fns_pcm_stats[2] = {reinterpret_cast<const void*>(fir_generic_bulk_pcm_stats_kernel<false>),
                                                  reinterpret_cast<const void*>(fir_generic_bulk_pcm_stats_kernel<true>)};
-    const FirOut mode = fir_out_mode(out_bits, dither, st != nullptr && st->table != nullptr);
+    const FirOut mode = format.out_mode();
+    if (mode == kFirOutPcmStats && !st.table) return hipErrorInvalidValue;
     const void* fn = mode == kFirOutPcmStats ? fns_pcm_stats[full ? 1 : 0]
                      : mode == kFirOutPcmTpdf ? fns_pcm_tpdf[full ? 1 : 0] : mode == kFirOutPcm ? fns_pcm_out[full ? 1 : 0] : fns[ci][full ? 1 : 0];
     static bool granted[6][2] = {};   // (the attribute is per function and process: set once)
@@ -431,7 +432,7 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
     }
     const dim3 grid((max_out + tile - 1) / tile, n_streams);
     uint32_t tile_arg = tile, cap_arg = cap;
-    FirStatArgs st_arg = mode == kFirOutPcmStats ? *st : FirStatArgs{nullptr, 0};
+    FirStatArgs st_arg = mode == kFirOutPcmStats ? st : FirStatArgs{nullptr, 0};
     void* kargs[4] = {&d_descs, &tile_arg, &cap_arg, &st_arg};   // (the counting builds alone take the fourth)
     if (hipError_t e = hipLaunchKernel(fn, grid, dim3(kBulkBlock), kargs, lds, stream); e != hipSuccess) return e;
     return hipGetLastError();

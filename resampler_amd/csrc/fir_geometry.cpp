@@ -296,7 +296,8 @@ void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_ou
 // kNotSupported for any other geometry (the caller converts with rsmp_f32_to_pcm_device afterwards).
 // dither != 0 (FirStreamDesc::dither): their twins that add TPDF dither.  stats: their twins that count what they store, with or
 // without dither (one build for both: a uniform branch).
-SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither, bool stats) {
+SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, const FirFormat& format) {
+    const uint32_t pcm_bits = format.in_bits, out_bits = format.out_bits;
     const bool one_channel = geo.cg == 1, odd_count = geo.cg == 3;
     const bool wide = geo.lp > 1 || one_channel;
     const bool two_rounds = geo.rounds == 2;
@@ -322,11 +323,36 @@ SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm
         if ((wide && !pairs_out) || one_channel || odd_count || geo.planes != 2 || diag || !window_ok || (pcm_bits != 0 && !width_ok(pcm_bits)) ||
             (out_bits != 0 && !width_ok(out_bits)))
             return {b, BuildError::kNotSupported};
-        const bool counted = out_bits != 0 && stats;
-        b = SplitBuild{nk, 2, false, pairs_out ? 1 : 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, out_bits != 0 && dither != 0 && !counted, counted};
+        const FirOut mode = format.out_mode();
+        b = SplitBuild{nk, 2, false, pairs_out ? 1 : 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, mode == kFirOutPcmTpdf, mode == kFirOutPcmStats};
     }
     return {b, BuildError::kNone};
 }
+
+// ---- the format rule: which streams and launches read or write PCM (fir_format.h, fir_periodic_plan.h) ----------------------
+FormatFault format_stream_fault(const FirFormat& format, size_t channels) {
+    const auto width_ok = [](uint32_t w) { return w == 0 || w == 16 || w == 24 || w == 32; };
+    if (!width_ok(format.in_bits) || !width_ok(format.out_bits)) return FormatFault::kWidth;
+    if (format.in_bits != 0 && channels != 2) return FormatFault::kInChannels;
+    if (format.out_bits != 0 && (channels % 2 != 0 || channels > 16)) return FormatFault::kOutChannels;
+    return FormatFault::kNone;
+}
+FormatFault format_group_fault(const FirFormat& format, const PeriodicGeometry& geo) {
+    if (!format.pcm()) return FormatFault::kNone;
+    if (geo.mfma == 3 && split_build_for(geo, false, format).error == BuildError::kNone) return FormatFault::kNone;
+    return format.in_bits != 0 ? FormatFault::kInGroup : FormatFault::kOutGroup;
+}
+const char* format_fault_text(FormatFault fault) {
+    static const char* const texts[] = {   // (in FormatFault's order)
+        "", "PCM widths: in_bits 0 (f32) / 16 / 24 / 32, out_bits 16 / 24 / 32 (any other format: f32 output and rsmp_f32_to_pcm_device)",
+        "PCM input: two-channel streams only (rsmp_pcm_to_stereo_f32_device converts a stereo file; pass any other count as f32)",
+        "PCM output: two-channel streams only or, from f32 input, an even count up to 16; one channel, odd counts, more than 16: f32 output and rsmp_f32_to_pcm_device",
+        "PCM input is read in place by the two-channel split kernel of the 128-tap rate pairs only (44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): convert with rsmp_pcm_to_stereo_f32_device first",
+        "PCM output is written in place by the split kernel of the 128-tap rate pairs only, for two channels or an even count up to 16 (44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): take f32 output and convert with rsmp_f32_to_pcm_device"};
+    return texts[static_cast<int>(fault)];
+}
+bool generic_tiled_ok(const FirFormat& format, uint32_t min_channels, uint32_t max_channels) { return format.out_bits == 0 || (min_channels == 2 && max_channels == 2); }
+bool split_groups_may_share(const FirFormat& format) { return !format.pcm(); }
 
 // Slots of launch_fir_periodic's kernel table.  0..2 = vector kernel: two channels with one lane per period / CG 2,
 // any even channel count / CG 1.  (4-tap chunks with 16-wave workgroups at 8 waves per SIMD measured

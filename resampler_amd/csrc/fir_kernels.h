@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/resampler_amd.h"
+#include "fir_format.h"
 #include "fir_nonfinite.h"
 
 namespace rsmp {
@@ -205,12 +206,6 @@ __device__ __forceinline__ void fir_pcm_store_code(void* out, uint32_t bits, siz
     }
 }
 __device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y) { fir_pcm_store_code(out, bits, i, fir_pcm_quantise(y, bits)); }
-// How a build stores its sums: f32, PCM, PCM with TPDF dither (the launchers' choice by out_bits and dither) -- and PCM that is
-// counted as it is stored (rsmp_fir_set_pcm_stats): builds of their own, with the dither a uniform branch on FirStreamDesc::dither.
-enum FirOut : int { kFirOutF32 = 0, kFirOutPcm = 1, kFirOutPcmTpdf = 2, kFirOutPcmStats = 3 };
-__host__ __device__ constexpr FirOut fir_out_mode(uint32_t out_bits, uint32_t dither, bool stats = false) {
-    return out_bits == 0 ? kFirOutF32 : stats ? kFirOutPcmStats : dither == RSMP_DITHER_TPDF ? kFirOutPcmTpdf : kFirOutPcm;
-}
 // A counting build's store of value `i` (as fir_out_store below): the bytes of the plain / dithered builds, and `s` says what was done.
 __device__ __forceinline__ void fir_out_store_stat(const FirStreamDesc& d, size_t i, float y, FirPcmStat& s) {
     const float noise = d.dither == RSMP_DITHER_TPDF ? fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i) : 0.0f;
@@ -229,29 +224,26 @@ __device__ __forceinline__ void fir_out_store(const FirStreamDesc& d, size_t i, 
 constexpr uint32_t kFirTile = 32;   // output frames per workgroup tile (generic kernel): one pass of 32 x 8 lanes
 
 // Generic kernel: any ratio, reference-form two-row interpolation; grid = (max tiles, streams).
-// (out_bits / dither, here and below: FirStreamDesc::out_bits / dither of the launch's streams -- out_bits != 0 selects the builds
-// that store PCM, dither their dithered twins)
+// (format, here and below: the launch's FirFormat (fir_format.h) -- format.out_mode() selects the builds that store f32, PCM, dithered
+// PCM or counted PCM; st, for a counting launch: its statistics table, stream s's entries the s-th row; hipErrorInvalidValue without one)
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
-                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, uint32_t out_bits = 0, uint32_t dither = 0,
-                              const FirStatArgs* st = nullptr);   // (st with a table, here and below: the counting builds; stream s's entries are st->table's s-th row)
+                              uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
 // The same arithmetic for LONG launches (fir_generic_bulk.hip): tiles of up to 4096 output frames per workgroup, their outputs sorted
 // by phase row, the tile's input window in LDS.  hipErrorNotSupported where no tile fits the LDS (fir_generic_bulk_tile == 0);
 // does not copy the tails (launch_fir_tail_copy).
 uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double max_ratio);
-// (uniform_channels: 1 / 2 = every stream has that many channels -- the builds for them --, anything else = any counts)
+// (uniform_channels: 1 / 2 = every stream has that many channels -- the builds for them --, anything else = any counts; PCM output: generic_tiled_ok or hipErrorNotSupported)
 hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
                                    uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels = 0,
                                    uint32_t uniform_taps = 0,    // (uniform_taps: 128 = every stream has 128 taps)
-                                   uint32_t out_bits = 0,       // (PCM output: two-channel streams only, hipErrorNotSupported otherwise)
-                                   uint32_t dither = 0, const FirStatArgs* st = nullptr);
+                                   const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
 constexpr uint32_t kFirBulkMinOut = 8192;   // launches whose longest generic stream produces fewer frames keep fir_generic_kernel
 // Re-evaluates, in the reference's two-row form, the output chunks a periodic launch marked as non-finite
 // (fir_nonfinite.h); exits at once when the launch marked nothing.
 // (done / done_attached, here and in launch_fir_tail_copy: as in launch_fir_repair_multi below -- the launch completes `done`
 // itself; *done_attached stays false when there was nothing to launch)
 hipError_t launch_fir_repair(const FirStreamDesc* d_descs, uint32_t n_streams, const NfArgs& nf, hipStream_t stream,
-                             hipEvent_t done = nullptr, bool* done_attached = nullptr, uint32_t out_bits = 0, uint32_t dither = 0,
-                             const FirStatArgs* st = nullptr);   // (counting: never completes `done` -- the fold follows)
+                             hipEvent_t done = nullptr, bool* done_attached = nullptr, const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});   // (counting: never completes `done` -- the fold follows)
 // The same for up to eight groups of streams (each with its own marks) in one launch.
 struct RepairJob {
     const FirStreamDesc* d_descs;
@@ -266,7 +258,7 @@ constexpr uint32_t kMaxRepairJobs = 8;
 // own behind the kernel as hipEventRecord puts there; *done_attached = false: there was no such launch, record it yourself)
 hipError_t launch_fir_repair_multi(const RepairJob* jobs, size_t n_jobs, hipStream_t stream, const FirStreamDesc* tail_descs = nullptr,
                                    uint32_t n_tail = 0, uint32_t max_tail_values = 0, hipEvent_t done = nullptr, bool* done_attached = nullptr,
-                                   uint32_t out_bits = 0, uint32_t dither = 0, const FirStatArgs* st = nullptr);
+                                   const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
 // Behind a counting launch and its repair pass: a workgroup per stream sums the stream's row of st.table into d_targets[s]
 // (device memory).  (done / done_attached: as above)
 hipError_t launch_fir_pcm_stats_fold(const FirStatArgs& st, uint32_t n_streams, const FirStatTarget* d_targets, hipStream_t stream,

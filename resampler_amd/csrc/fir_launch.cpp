@@ -58,19 +58,13 @@ struct Launch {
     rsmp_fir* const leader;
     std::vector<FirJob>& jobs;
     const hipStream_t stream;
-    const uint32_t pcm_bits, out_bits;
-    uint32_t dither = 0;   // PCM output: the handles' dither mode (rsmp_fir_set_pcm_dither), one for the launch
-    // PCM output: the handles count what they store (rsmp_fir_set_pcm_stats), all of them or none.  st: the launch's table in the
-    // leader's d_stat_table, a row of st.chunks entries per stream in launch order; targets_off: the FirStatTarget of every stream,
-    // in the workspace behind the plans' arrays.
-    bool stats = false;
+    const FirFormat format;   // (one for the launch: the entry has held every handle to it)
+    // A counting launch (format.stats).  st: the launch's table in the leader's d_stat_table, a row of st.chunks entries per stream
+    // in launch order; targets_off: the FirStatTarget of every stream, in the workspace behind the plans' arrays.
     FirStatArgs st{nullptr, 0};
     size_t targets_off = 0;
-    const FirStatArgs* stat_rows(size_t first, FirStatArgs& rows) const {   // (the table from stream `first` of the launch on; nullptr: not counting)
-        if (!stats) return nullptr;
-        rows = FirStatArgs{st.table + first * st.chunks * 4, st.chunks};
-        return &rows;
-    }
+    // (the table from stream `first` of the launch on; none: not counting)
+    FirStatArgs stat_rows(size_t first) const { return format.stats ? FirStatArgs{st.table + first * st.chunks * 4, st.chunks} : FirStatArgs{}; }
     const size_t n;
     // launch order: generic jobs, then periodic jobs grouped by geometry (one launch per geometry)
     std::vector<size_t> order;
@@ -91,8 +85,7 @@ struct Launch {
     bool tail_fused = false;   // the last main kernel copies the tails as well: no tail-copy launch
     hipEvent_t done = nullptr;
     bool done_attached = false;
-    Launch(rsmp_fir* l, std::vector<FirJob>& j, hipStream_t s, uint32_t bits, uint32_t obits)
-        : leader(l), jobs(j), stream(s), pcm_bits(bits), out_bits(obits), n(j.size()) {}
+    Launch(rsmp_fir* l, std::vector<FirJob>& j, hipStream_t s, const FirFormat& f) : leader(l), jobs(j), stream(s), format(f), n(j.size()) {}
 };
 
 int order_streams(Launch& L) {
@@ -122,47 +115,10 @@ int bind_and_group(Launch& L) {
         if (!found) L.groups.push_back(Group{j.r->periodic.geo, {i}});
     }
     for (const Group& g : L.groups) for (size_t i : g.members) L.order.push_back(i);
-    // PCM input: two-channel streams, periodic groups on the split kernel's builds for them.  PCM output: the same, or -- from f32
-    // input -- an even count of 4 .. 16 channels on the channel-pair builds of the same three windows (split_build_for).
-    if (L.out_bits != 0) {
-        L.dither = static_cast<uint32_t>(jobs[0].r->pcm_dither);
-        for (const FirJob& j : jobs)
-            if (static_cast<uint32_t>(j.r->pcm_dither) != L.dither)
-                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: one dither mode for all the streams of a batch (rsmp_fir_set_pcm_dither; "
-                                                       "the seeds may differ)");
-    }
-    if (L.out_bits != 0) {
-        L.stats = jobs[0].r->pcm_stats;
-        for (const FirJob& j : jobs)
-            if (j.r->pcm_stats != L.stats)
-                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: statistics for all the streams of a batch or for none (rsmp_fir_set_pcm_stats)");
-    }
-    if (L.pcm_bits != 0 || L.out_bits != 0) {
-        for (const FirJob& j : jobs) {
-            const size_t ch = j.r->channels;
-            if (L.pcm_bits != 0 && ch != 2)
-                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM input: two-channel streams only (rsmp_pcm_to_stereo_f32_device converts a stereo file; "
-                                                       "pass any other count as f32)");
-            if (ch % 2 != 0 || ch > 16)
-                return fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: two-channel streams only or, from f32 input, an even count up to 16; "
-                                                       "one channel, odd counts, more than 16: f32 output and rsmp_f32_to_pcm_device");
-        }
-        for (const Group& g : L.groups) {
-            const uint32_t nk = g.geo.row_len / 32;
-            const bool window_ok = (g.geo.rounds == 1 && nk == 5) || (g.geo.rounds == 2 && (nk == 5 || nk == 6));
-            const bool stereo = g.geo.lp == 1 && g.geo.cg == 2;
-            const bool pairs_out = L.pcm_bits == 0 && g.geo.lp > 1 && g.geo.cg == 2;   // (PCM output alone: 4, 6, 8 .. 16 channels)
-            const bool ok = g.geo.mfma == 3 && g.geo.planes == 2 && (stereo || pairs_out) && window_ok;
-            if (!ok && L.pcm_bits != 0)
-                return fail(RSMP_ERR_INVALID_ARGUMENT,
-                            "PCM input is read in place by the two-channel split kernel of the 128-tap rate pairs only "
-                            "(44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): convert with rsmp_pcm_to_stereo_f32_device first");
-            if (!ok)
-                return fail(RSMP_ERR_INVALID_ARGUMENT,
-                            "PCM output is written in place by the split kernel of the 128-tap rate pairs only, for two channels or "
-                            "an even count up to 16 (44.1 <-> 48, 96 -> 44.1 / 48 kHz ...): take f32 output and convert with rsmp_f32_to_pcm_device");
-        }
-    }
+    // PCM in or out: every periodic group needs a build of the split kernel for it (the streams' part of the rule: the entry)
+    for (const Group& g : L.groups)
+        if (const FormatFault f = format_group_fault(L.format, g.geo); f != FormatFault::kNone)
+            return fail(RSMP_ERR_INVALID_ARGUMENT, "%s", format_fault_text(f));
     return RSMP_OK;
 }
 
@@ -188,7 +144,7 @@ void lay_out_workspace(Launch& L) {
             bytes = align_up(bytes + words * sizeof(uint32_t), 256);
         }
     }
-    if (L.stats) {
+    if (L.format.stats) {
         L.targets_off = bytes;
         bytes = align_up(bytes + L.n * sizeof(FirStatTarget), 256);
     }
@@ -297,10 +253,10 @@ int fill_descriptors(Launch& L) {
         ds.den = static_cast<uint32_t>(r->mirror.den());
         ds.abs_out = r->mirror.abs_out();
         ds.abs_consumed = r->mirror.abs_consumed();
-        ds.in_bits = L.pcm_bits;
-        ds.out_bits = L.out_bits;
-        ds.dither = L.dither;
-        ds.dither_seed = L.out_bits != 0 ? r->pcm_dither_seed : 0;
+        ds.in_bits = L.format.in_bits;
+        ds.out_bits = L.format.out_bits;
+        ds.dither = L.format.dither;
+        ds.dither_seed = L.format.out_bits != 0 ? r->pcm_dither_seed : 0;
         if (ds.tail_frames * ch > L.max_tail_values) L.max_tail_values = ds.tail_frames * ch;
         if (!pl.periodic) {
             ds.segs = reinterpret_cast<const rsmp_fir_segment*>(L.d + pp.seg_off);
@@ -317,14 +273,14 @@ int fill_descriptors(Launch& L) {
             return rc;
         }
         pp.written = true;
-        if (L.stats) reinterpret_cast<FirStatTarget*>(L.h + L.targets_off)[slot] = FirStatTarget{r->d_pcm_stats.as<rsmp_pcm_stats>(), r->pcm_stats_cleared ? 1u : 0u, 0u};
+        if (L.format.stats) reinterpret_cast<FirStatTarget*>(L.h + L.targets_off)[slot] = FirStatTarget{r->d_pcm_stats.as<rsmp_pcm_stats>(), r->pcm_stats_cleared ? 1u : 0u, 0u};
     }
     return RSMP_OK;
 }
 
 // A counting launch's table: a row of chunks per stream, zero before the main kernels (on the launch stream).
 int reserve_stat_table(Launch& L) {
-    if (!L.stats) return RSMP_OK;
+    if (!L.format.stats) return RSMP_OK;
     rsmp_fir* leader = L.leader;
     uint32_t max_out = 0;
     for (const FirJob& j : L.jobs)
@@ -373,21 +329,19 @@ int launch_generic(Launch& L) {
     static const bool bulk_on = [] { const char* e = knob("RSMP_FIR_GENERIC_BULK"); return !e || atoi(e) != 0; }();
     const bool generic_bulk = bulk_on && L.n_generic != 0 && L.max_out_generic >= kFirBulkMinOut &&
                               fir_generic_bulk_tile(L.max_ch_generic, L.max_taps_generic, L.max_ratio_generic) != 0 &&
-                              // (PCM output: the tiled kernel's builds are two-channel; a generic stream of more channels -- a launch
-                              // too short to be worth the periodic kernels, a rate pair without a short period -- keeps the batch's
-                              // generic streams on the latency kernel, which stores by value index for any count, at any length)
-                              (L.out_bits == 0 || (L.min_ch_generic == 2 && L.max_ch_generic == 2));
-    FirStatArgs rows;
-    const FirStatArgs* st = L.stat_rows(0, rows);   // (the generic streams are the launch's first)
+                              // (PCM output: the tiled kernel's builds are two-channel; a generic stream of more channels -- a launch too short for the periodic kernels, a rate
+                              // pair without a short period -- keeps the batch's generic streams on the latency kernel, which stores by value index for any count, at any length)
+                              generic_tiled_ok(L.format, L.min_ch_generic, L.max_ch_generic);
+    const FirStatArgs st = L.stat_rows(0);   // (the generic streams are the launch's first)
     if (generic_bulk) {
         L.tail_fused = false;
         RSMP_HIP_CHECK(launch_fir_generic_bulk(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic,
                                                L.max_taps_generic, L.max_ratio_generic, L.stream,
                                                L.min_ch_generic == L.max_ch_generic ? L.max_ch_generic : 0u,
-                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.out_bits, L.dither, st));
+                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.format, st));
     } else if (L.n_generic)
         RSMP_HIP_CHECK(launch_fir_generic(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic, L.stream,
-                                          L.tail_fused, L.out_bits, L.dither, st));
+                                          L.tail_fused, L.format, st));
     return RSMP_OK;
 }
 
@@ -455,15 +409,13 @@ int launch_periodic_groups(Launch& L) {
         if (++leader->nf_tag == 0) leader->nf_tag = 1;
         rp.nf.tag = leader->nf_tag;
         const uint64_t key = items_key(L, g, max_blocks);
-        FirStatArgs rows;
-        if (L.groups.size() > 1 && g.geo.mfma == 3 && L.pcm_bits == 0 && L.out_bits == 0) {
+        if (L.groups.size() > 1 && g.geo.mfma == 3 && split_groups_may_share(L.format)) {
             // several rate pairs in one batch: those of the split kernel share launches (launch_fir_split_multi: one item
             // table launch, one kernel launch per kernel build among them), as in rsmp_fir_lockstep_run
             split_jobs.push_back(SplitJob{L.d_descs + first, static_cast<uint32_t>(g.members.size()), &g.geo, max_blocks, rp.nf});
         } else {
             RSMP_HIP_CHECK(launch_fir_periodic(L.d_descs + first, static_cast<uint32_t>(g.members.size()), g.geo, max_blocks,
-                                               leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.pcm_bits, L.out_bits,
-                                               L.dither, L.stat_rows(first, rows)));
+                                               leader->d_work_counter, rp.nf, L.stream, L.tail_fused, key, L.format, L.stat_rows(first)));
         }
         first += g.members.size();
     }
@@ -526,21 +478,20 @@ int launch_followups(Launch& L) {
     if (int rc = launch_event(leader)) return rc;
     const bool wrap_last = n > n_generic && L.max_wraps > 0 && L.tail_fused;
     // (a counting launch: the fold behind the repair pass takes the repair pass's place as the last launch)
-    const bool fold_last = L.stats && L.tail_fused && !wrap_last;
-    const bool repair_last = L.tail_fused && !wrap_last && !L.stats;
+    const bool fold_last = L.format.stats && L.tail_fused && !wrap_last;
+    const bool repair_last = L.tail_fused && !wrap_last && !L.format.stats;
     L.done = L.stream != reinterpret_cast<hipStream_t>(RSMP_STREAM_LEGACY) ? leader->launch_ev->ev : nullptr;
     if (L.repairs.size() > 1) {
         std::vector<RepairJob> rj;
         for (const Repair& rp : L.repairs) rj.push_back(RepairJob{L.d_descs + rp.first, rp.count, rp.nf, static_cast<uint32_t>(rp.first)});
         RSMP_HIP_CHECK(launch_fir_repair_multi(rj.data(), rj.size(), L.stream, nullptr, 0, 0, repair_last ? L.done : nullptr,
-                                               &L.done_attached, L.out_bits, L.dither, L.stats ? &L.st : nullptr));
+                                               &L.done_attached, L.format, L.st));
     } else {
-        FirStatArgs rows;
         for (const Repair& rp : L.repairs)
             RSMP_HIP_CHECK(launch_fir_repair(L.d_descs + rp.first, rp.count, rp.nf, L.stream, repair_last ? L.done : nullptr,
-                                             &L.done_attached, L.out_bits, L.dither, L.stat_rows(rp.first, rows)));
+                                             &L.done_attached, L.format, L.stat_rows(rp.first)));
     }
-    if (L.stats)
+    if (L.format.stats)
         RSMP_HIP_CHECK(launch_fir_pcm_stats_fold(L.st, static_cast<uint32_t>(n), reinterpret_cast<const FirStatTarget*>(L.d + L.targets_off),
                                                  L.stream, fold_last ? L.done : nullptr, &L.done_attached));
     if (n > n_generic && L.max_wraps > 0)
@@ -562,15 +513,15 @@ void commit(Launch& L) {
         j.r->last_periodic = j.plan->periodic;
         j.r->mirror = j.plan->planned;
         j.r->cur ^= 1;
-        if (L.stats) j.r->pcm_stats_cleared = false;   // (the fold has written the handle's totals)
+        if (L.format.stats) j.r->pcm_stats_cleared = false;   // (the fold has written the handle's totals)
         if (j.r->last_launch != L.leader->launch_ev) j.r->last_launch = L.leader->launch_ev;   // (no reference count traffic per launch)
     }
 }
 
 }  // namespace
 
-int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits, uint32_t out_bits) {
-    Launch L(leader, jobs, stream, pcm_bits, out_bits);
+int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, const FirFormat& format) {
+    Launch L(leader, jobs, stream, format);
     if (int rc = order_streams(L)) return rc;
     if (int rc = bind_and_group(L)) return rc;
     lay_out_workspace(L);

@@ -6,6 +6,7 @@
 #include <memory>
 #include <vector>
 
+#include "fir_format.h"
 #include "fir_handle.h"
 #include "fir_hostplan.h"
 
@@ -41,11 +42,8 @@ int order_behind_handle(rsmp_fir* h, hipStream_t stream, const FirLaunchEvent*& 
 
 // Assembles and enqueues the launches for a set of planned jobs on one device / stream.
 // `leader` owns the launch workspace.
-// pcm_bits != 0: every job's d_in is a WAV file's PCM of that width, read in place (FirStreamDesc::in_bits): two-channel
-// streams on the generic kernel (short launches) or the split kernel's PCM builds.
-// out_bits != 0: every job's d_out receives PCM of that width (FirStreamDesc::out_bits); the same streams and kernels.  The
-// handles' dither setting (rsmp_fir_set_pcm_dither) applies: one mode for all of them -- RSMP_ERR_INVALID_ARGUMENT otherwise, before
-// anything is launched or changed --, a seed each.
-int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0);
+// format (fir_format.h): what every job's d_in and d_out hold and how PCM output is stored -- the entry has built it from the widths and the handles'
+// settings and held every handle to it; the periodic groups are held to it here (format_group_fault): RSMP_ERR_INVALID_ARGUMENT before anything is launched or changed.
+int launch_jobs(rsmp_fir* leader, std::vector<FirJob>& jobs, hipStream_t stream, const FirFormat& format = FirFormat{});
 
 }  // namespace rsmp

@@ -80,16 +80,12 @@ int class_table_for(int device, const std::vector<float>& table, const PeriodicG
 // `nf`: where non-finite sums are marked (fir_nonfinite.h); the caller follows up with launch_fir_repair.
 // items_key: a hash of everything the split kernel's item table depends on (the streams' counters in launch order; 0 =
 // none): a launch with the key of the table already in the stream's workspace does not rebuild it.
-// pcm_bits != 0: the streams' `in` is PCM of that width (FirStreamDesc::in_bits): the split kernel's two-channel builds
-// read it; hipErrorNotSupported for any other kernel.  out_bits != 0: the streams' `out` is PCM of that width
-// (FirStreamDesc::out_bits), written by the same split-kernel builds, dithered where dither = RSMP_DITHER_TPDF
-// (FirStreamDesc::dither; the seeds are the descriptors'); hipErrorNotSupported for any other kernel.  st with a table: the
-// builds that also count what they store into it (FirStatArgs, fir_kernels.h; stream s of d_descs has row s).
+// format: the launch's (fir_format.h; the descriptors' in_bits / out_bits / dither say the same).  PCM in or out: the split kernel's builds for it; hipErrorNotSupported
+// where format_group_fault names a fault.  st, for a counting format: the table the builds count what they store into (FirStatArgs, fir_kernels.h; stream s of d_descs has row s).
 hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
                                const PeriodicGeometry& geo, uint32_t max_blocks,
                                unsigned long long* d_work_counter, const NfArgs& nf, hipStream_t stream,
-                               bool fuse_tail = false, uint64_t items_key = 0, uint32_t pcm_bits = 0, uint32_t out_bits = 0,
-                               uint32_t dither = 0, const FirStatArgs* st = nullptr);
+                               bool fuse_tail = false, uint64_t items_key = 0, const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
 // Recomputes the outputs listed in each stream's `wraps` with row 1023 / previous frame
 // (only for geometries without inline wraps).
 // (done / done_attached: as in launch_fir_repair_multi, fir_kernels.h)
@@ -99,8 +95,7 @@ hipError_t launch_fir_wrap_fixup(const FirStreamDesc* d_descs, uint32_t n_stream
 // fuse_tail: the kernel also copies every stream's still-buffered tail into hist_next (no tail-copy launch)
 hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, const PeriodicGeometry& geo,
                             uint32_t max_blocks, uint32_t cus, bool fuse_tail, const NfArgs& nf, hipStream_t stream,
-                            uint64_t items_key = 0, uint32_t pcm_bits = 0, uint32_t out_bits = 0, uint32_t dither = 0,
-                            const FirStatArgs* st = nullptr);
+                            uint64_t items_key = 0, const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
 
 // Several rate pairs in as few launches as their geometries allow (one item-table launch for all of them, then one
 // launch of the kernel per window length among them): `jobs[j]` = the streams d_descs[0 .. n_streams) of geometry

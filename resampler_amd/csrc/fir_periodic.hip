@@ -1663,14 +1663,14 @@ GeoArgs to_args(const PeriodicGeometry& g) {
 hipError_t launch_fir_periodic(const FirStreamDesc* d_descs, uint32_t n_streams,
                                const PeriodicGeometry& geo, uint32_t max_blocks,
                                unsigned long long* d_work_counter, const NfArgs& nf, hipStream_t stream,
-                               bool fuse_tail, uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
+                               bool fuse_tail, uint64_t items_key, const FirFormat& format, const FirStatArgs& st) {
     if (n_streams == 0 || max_blocks == 0) return hipSuccess;
     int device = 0;
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess) return e;
     const uint32_t cus = device_cus(device);
-    if (geo.mfma == 3) return launch_fir_split(d_descs, n_streams, geo, max_blocks, cus, fuse_tail, nf, stream, items_key, pcm_bits, out_bits, dither, st);
-    if (pcm_bits != 0 || out_bits != 0) return hipErrorNotSupported;
+    if (geo.mfma == 3) return launch_fir_split(d_descs, n_streams, geo, max_blocks, cus, fuse_tail, nf, stream, items_key, format, st);
+    if (format_group_fault(format, geo) != FormatFault::kNone) return hipErrorNotSupported;   // (PCM: the split kernel alone)
     // the build: a slot of the table (periodic_slot_for, fir_geometry.cpp), in its plain or its diagnostic row
     static const int mfma_dbg = [] {   // RSMP_FIR_MFMA_DBG: 1 hot coefficient line, 2 no LDS reads, 3 both
         const char* e = rsmp::knob("RSMP_FIR_MFMA_DBG");

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "fir_format.h"
 #include "fir_plan.h"
 
 namespace rsmp {
@@ -92,10 +93,11 @@ struct SplitChoice {
     SplitBuild build;
     BuildError error;
 };
-// diag: RSMP_FIR_DEBUG or RSMP_FIR_WTRACE is set; pcm_bits / out_bits / dither: FirStreamDesc::in_bits / out_bits / dither of the
-// launch's streams; stats: the PCM output is counted (rsmp_fir_set_pcm_stats).
-SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, uint32_t pcm_bits, uint32_t out_bits = 0, uint32_t dither = 0,
-                            bool stats = false);
+// diag: RSMP_FIR_DEBUG or RSMP_FIR_WTRACE is set; format: the launch's (fir_format.h).
+SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, const FirFormat& format);
+// The periodic groups' part of the format rule (fir_format.h): a launch that reads or writes PCM needs a build of the split kernel for
+// every periodic group -- split_build_for decides.  kInGroup where the format reads PCM, else kOutGroup; kNone for f32 in and out.
+FormatFault format_group_fault(const FirFormat& format, const PeriodicGeometry& geo);
 // Slot of launch_fir_periodic's kernel table for a geometry of the vector or f32 matrix-core kernels, or -1 (no such
 // build).  mfma_dbg: RSMP_FIR_MFMA_DBG (0 .. 3); mfma_ring: mfma_ring_knob().
 constexpr int kPeriodicSlots = 20;

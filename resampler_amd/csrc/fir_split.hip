@@ -1917,11 +1917,10 @@ const void* split_kernel_for(const SplitBuild& build) {
 
 hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, const PeriodicGeometry& geo,
                             uint32_t max_blocks, uint32_t cus, bool fuse_tail, const NfArgs& nf, hipStream_t stream,
-                            uint64_t items_key, uint32_t pcm_bits, uint32_t out_bits, uint32_t dither, const FirStatArgs* st) {
+                            uint64_t items_key, const FirFormat& format, const FirStatArgs& st) {
     static const char* wtrace_path = rsmp::knob("RSMP_FIR_WTRACE");
     const bool diag = fir_debug_knob() != 0 || wtrace_path != nullptr;
-    const bool counted = st != nullptr && st->table != nullptr && out_bits != 0;
-    const SplitChoice choice = split_build_for(geo, diag, pcm_bits, out_bits, dither, counted);
+    const SplitChoice choice = split_build_for(geo, diag, format);
     if (choice.error != BuildError::kNone) return choice.error == BuildError::kInvalid ? hipErrorInvalidValue : hipErrorNotSupported;
     const void* fn = split_kernel_for(choice.build);
     if (fn == nullptr) return hipErrorInvalidValue;
@@ -1930,7 +1929,8 @@ hipError_t launch_fir_split(const FirStreamDesc* d_descs, uint32_t n_streams, co
     if (e != hipSuccess) return e;
     if ((e = grant_dynamic_lds(device, fn, kLdsLimit)) != hipSuccess) return e;
     SplitArgs args = make_split_args(geo, n_streams, max_blocks, fuse_tail, nf);
-    if (counted) args.stat = *st;
+    if (format.out_mode() == kFirOutPcmStats && !st.table) return hipErrorInvalidValue;
+    args.stat = st;   // (read by the counting builds alone)
     const dim3 grid(args.total_items < cus ? args.total_items : cus);
     static const bool verbose = rsmp::knob("RSMP_FIR_VERBOSE") != nullptr;
     if (verbose)

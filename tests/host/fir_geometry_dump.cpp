@@ -44,7 +44,7 @@ int main() {
                         static const struct { bool diag; uint32_t bits; } asks[3] = {{false, 0}, {true, 0}, {false, 16}};
                         printf(" |");
                         for (const auto& q : asks) {
-                            const rsmp::SplitChoice c = rsmp::split_build_for(g, q.diag, q.bits);
+                            const rsmp::SplitChoice c = rsmp::split_build_for(g, q.diag, rsmp::FirFormat{q.bits, 0, 0, false});
                             if (c.error != rsmp::BuildError::kNone) printf(" split:%s", c.error == rsmp::BuildError::kInvalid ? "invalid" : "unsupported");
                             else printf(" split:%d,%d,%d,%d,%d,%d", c.build.nk, c.build.planes, c.build.diag ? 1 : 0, c.build.wide, c.build.rounds, c.build.bits);
                         }

@@ -4,7 +4,8 @@
 // dither 0 / 1 and statistics off / on: one row per question.  tests/test_pcm_out_wide_host.py builds it as plain C++ under
 // ASan + UBSan and holds the rows to the rule (even counts of 4 .. 16 channels write PCM from the channel-pair builds) and, for
 // two channels and for f32 output, to tests/golden/split_pcm_wide.json (tests/golden/make_split_pcm_wide_fixture.py: this
-// program compiled against the sources of the commit before the rule changed).
+// program compiled against the sources of the commit before the rule changed -- as it was at ef8e494, before split_build_for
+// came to take a FirFormat; the rows it prints are the same).
 #include <cstdint>
 #include <cstdio>
 #include <numeric>
@@ -31,7 +32,7 @@ int main() {
                                 printf(" -\n");
                                 continue;
                             }
-                            const rsmp::SplitChoice s = rsmp::split_build_for(g, false, pcm_bits, out_bits, dither, stats != 0);
+                            const rsmp::SplitChoice s = rsmp::split_build_for(g, false, rsmp::FirFormat{pcm_bits, out_bits, dither, stats != 0});
                             if (s.error != rsmp::BuildError::kNone) printf(" %s\n", s.error == rsmp::BuildError::kInvalid ? "invalid" : "unsupported");
                             else printf(" split:%d,%d,%d,%d,%d,%d,%d,%d,%d\n", s.build.nk, s.build.planes, s.build.diag ? 1 : 0, s.build.wide, s.build.rounds,
                                         s.build.bits, s.build.pcm_out ? 1 : 0, s.build.dither ? 1 : 0, s.build.stats ? 1 : 0);

@@ -206,3 +206,50 @@ def test_refusals_write_nothing():
     out = torch.zeros(h.bulk_output_bound(2 * frames, CHUNK) * 2, dtype=torch.uint8, device=dev)
     c, p = ra.FirBatch([h]).resample_bulk_pcm_out_device([x], 0, [out], 16, CHUNK)
     assert int(c[0]) == 2 * frames and int(p[0]) > 0
+
+
+def test_refusals_of_the_entry_leave_a_batch_as_it_was():
+    """What the entry checks before anything is planned, one reason at a time, on a batch of two streams: a dither mix, a statistics
+    mix, an output at an odd byte address, a width that is none.  Each is RSMP_ERR_INVALID_ARGUMENT, no byte of either output is
+    written and neither handle's state moves; the same handles then take the accepted call, whose bytes are the quantiser's of the
+    f32 entry's output on twin handles."""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    frames = 20000
+    hs, twins = [_fir(), _fir()], [_fir(), _fir()]
+    assert hs[0].taps == 128
+    x = [torch.from_numpy(np.roll(synth.sweep(frames, 2, 44100.0) * np.float32(0.9), 2 * 77 * i)).to(dev) for i in range(2)]
+    cap = hs[0].bulk_output_bound(2 * frames, CHUNK)
+    batch = ra.FirBatch(hs)
+
+    def refused(out_bits=16, shift=0):
+        bigs = [torch.full((GUARD + cap * 4 + GUARD,), FILL, dtype=torch.uint8, device=dev) for _ in hs]
+        outs = [bigs[0][GUARD + shift:GUARD + shift + cap * 4], bigs[1][GUARD:GUARD + cap * 4]]
+        before = [h.state() for h in hs]
+        with pytest.raises(ra.ResampleError) as e:
+            batch.resample_bulk_pcm_out_device(x, 0, outs, out_bits, CHUNK)
+        torch.cuda.synchronize()
+        assert e.value.code == RSMP_ERR_INVALID_ARGUMENT, str(e.value)
+        assert all(bool((b == FILL).all()) for b in bigs) and [h.state() for h in hs] == before
+
+    hs[0].set_pcm_dither(ra.Dither.TPDF, 5)
+    refused()
+    hs[0].set_pcm_dither(ra.Dither.NONE)
+    hs[1].set_pcm_stats(True)
+    refused()
+    hs[1].set_pcm_stats(False)
+    refused(shift=1)
+    refused(out_bits=8)
+
+    out_f32 = [torch.zeros(cap, device=dev) for _ in twins]
+    b_twin = ra.FirBatch(twins)
+    b_twin.bind(x, out_f32)
+    c2, p2 = b_twin.resample_bulk_device(CHUNK)
+    got = [torch.zeros(cap * 2, dtype=torch.uint8, device=dev) for _ in hs]
+    c1, p1 = batch.resample_bulk_pcm_out_device(x, 0, got, 16, CHUNK)
+    torch.cuda.synchronize()
+    assert [int(v) for v in c1] == [int(v) for v in c2] == [2 * frames] * 2 and [int(v) for v in p1] == [int(v) for v in p2]
+    for i in range(2):
+        want = ra.f32_to_pcm(out_f32[i][:int(p2[i])].cpu().numpy(), 16)
+        assert any(want) and got[i][:int(p2[i]) * 2].cpu().numpy().tobytes() == want, i
+        assert hs[i].state() == twins[i].state()
