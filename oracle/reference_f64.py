@@ -212,12 +212,15 @@ def fft_f64(x: np.ndarray, channels: int, in_hz: int, out_hz: int, blocks: int, 
 # Beyond these the gate stops rejecting the modelled defects of tests/test_reference_f64.py: no family's margin may pass them.
 M_RMS_CAP = 3.0
 M_MAX_CAP = 4.0
-# (M_RMS, M_MAX) per kernel family: 1.25 x the worst ratio over the family's cases in tests/test_accuracy_f64_gpu.py on an
-# MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
+# (M_RMS, M_MAX) per kernel family: 1.25 x the worst ratio over the family's cases in tests/test_accuracy_f64_gpu.py
+# ("fft_pair_io": tests/test_fft_pair_builds_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
 MARGINS = {
     "fir_bulk": (1.5, 1.6),    # worst x1.191 / x1.256: the f32 periodic kernels (pre-mixed rows); the split kernel x0.78 / x0.92
     "lockstep": (1.0, 1.1),    # worst x0.784 / x0.867
     "fft": (1.4, 1.4),         # worst x1.068 / x1.115 (per-call, 512-frame blocks)
+    # tests/test_fft_pair_builds_gpu.py: every build of the two-channel pair kernel, 17 blocks each (as few as 2176 values: the
+    # max ratio over so few is noisier than "fft"'s): worst x1.319 (768 -> 256 frames, 24-bit input) / x1.416 (1536 -> 64, 24-bit)
+    "fft_pair_io": (1.7, 1.8),
 }
 
 

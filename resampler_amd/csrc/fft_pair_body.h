@@ -198,10 +198,37 @@ struct PairPrep {
     }
 };
 
+// pdft<8> (fft_butterflies_pk.h) with the roundings of its two products by H spelled out, for the PCM-output builds of the plans
+// whose last inverse stage has fewer butterflies than the wave has lanes (FO <= 256).  pdft<8> leaves it to the compiler
+// (fp contract(fast)) whether xe +- H x is one rounding or two, and the compiler decides by where the code ends up: in the f32
+// builds of those plans it moves outputs 5 and 7 of the ODD chain's last butterfly behind the `emit` branches of the store loop,
+// away from their products -- two roundings -- and fuses outputs 1 and 3; in the PCM builds, whose store is longer, it fused all
+// four, and up to 3 % of the values of the frames n = i + 5 MI and i + 7 MI came out one unit in the last place off the f32 build's: PCM bytes that
+// were not the converter's of the f32 output (tests/test_fft_pair_builds_gpu.py).  What the f32 builds compute is the definition
+// (tests/test_fft_gpu.py holds it to the oracle); here it is written down.
+__device__ __forceinline__ void pair_pdft8_as_f32_build(const cf (&t)[8], cf (&o)[8]) {
+    const float H = 0.70710678118654752440f;
+    const cf ea0 = t[0] + t[4], ea1 = t[0] - t[4], ea2 = t[2] + t[6], ea3 = t[2] - t[6];
+    const cf xe0 = ea0 + ea2, xe2 = ea0 - ea2, xe1 = cf_add_nrot(ea1, ea3), xe3 = cf_sub_nrot(ea1, ea3);
+    const cf oa0 = t[1] + t[5], oa1 = t[1] - t[5], oa2 = t[3] + t[7], oa3 = t[3] - t[7];
+    const cf xo0 = oa0 + oa2, xo2 = oa0 - oa2, xo1 = cf_add_nrot(oa1, oa3), xo3 = cf_sub_nrot(oa1, oa3);
+    o[0] = xe0 + xo0;
+    o[4] = xe0 - xo0;
+    o[2] = cf_add_nrot(xe2, xo2);
+    o[6] = cf_sub_nrot(xe2, xo2);
+    const cf r1 = cf_add_nrot(xo1, xo1), r3 = cf_sub_nrot(xo3, xo3), h = cf_make(H, H);
+    o[1] = __builtin_elementwise_fma(r1, h, xe1);              // one rounding
+    o[3] = __builtin_elementwise_fma(-r3, h, xe3);
+    cf w1 = H * r1, w3 = H * r3;
+    asm("" : "+v"(w1), "+v"(w3));                              // the rounded products: nothing is fused into what follows
+    o[5] = xe1 - w1;
+    o[7] = xe3 + w3;
+}
+
 // The last stage of a plan (stride = M: a butterfly's points are its own) with its outputs left in registers: butterfly
 // i = lane + 64 it yields o[it][q] = X[i + q M].  Every read is issued before the first butterfly (what follows overwrites
-// the buffer).  QS / IPP: where the stage's inputs lie (wave_stage).
-template <int N, int R, int QS, int IPP>
+// the buffer).  QS / IPP: where the stage's inputs lie (wave_stage).  AS_F32: pair_pdft8_as_f32_build for the butterfly.
+template <int N, int R, int QS, int IPP, bool AS_F32 = false>
 __device__ __forceinline__ void wave_last_regs(const cf* buf, const cf* __restrict__ tw, int lane, cf (&o)[(N / R + 63) / 64][R]) {
     constexpr int M = N / R;
     constexpr int ITER = (M + 63) / 64;
@@ -226,7 +253,8 @@ __device__ __forceinline__ void wave_last_regs(const cf* buf, const cf* __restri
             t[0] = o[it][0];
 #pragma unroll
             for (int q = 1; q < R; ++q) t[q] = cf_mul(twr[q], o[it][q]);
-            pdft<R>(t, o[it]);
+            if constexpr (AS_F32) pair_pdft8_as_f32_build(t, o[it]);
+            else pdft<R>(t, o[it]);
         }
     }
 }
@@ -579,7 +607,12 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
                         for (int q = 0; q < RLI; ++q) uv[it][q] = lds_ld(chirp_u + i + q * MI);
                     }
                 }
+#if RSMP_PAIR_PCM_OUT
+                // (the roundings of the f32 build's butterfly, which the compiler does not arrive at by itself here: see there)
+                wave_last_regs<FO, RLI, MI + INV::in_pad(SI - 1), INV::in_period(SI - 1), RLI == 8 && MI < 64>(buf, tw_i + INV::tab(SI - 1, kWholeRows), lane, B);
+#else
                 wave_last_regs<FO, RLI, MI + INV::in_pad(SI - 1), INV::in_period(SI - 1)>(buf, tw_i + INV::tab(SI - 1, kWholeRows), lane, B);
+#endif
                 // F[n] = A + u B -> frame n = conj(F[n]) + conj(carry[n]); F[n + FO] = A - u B is the next carry
 #pragma unroll
                 for (int it = 0; it < ITI; ++it) {
