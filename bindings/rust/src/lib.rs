@@ -126,6 +126,9 @@ extern "C" {
                                                    stream: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_fft_set_pcm_dither(r: *mut rsmp_fft, dither: c_int, seed: u64) -> c_int;
     fn rsmp_fft_pcm_dither(r: *const rsmp_fft, dither: *mut c_int, seed: *mut u64) -> c_int;
+    fn rsmp_fft_set_pcm_stats(r: *mut rsmp_fft, enable: c_int) -> c_int;
+    fn rsmp_fft_pcm_stats(r: *mut rsmp_fft, stats: *mut PcmStats) -> c_int;
+    fn rsmp_fft_pcm_stats_clear(r: *mut rsmp_fft) -> c_int;
     // additions to the reference API: a fixed set of streams stepped together on device-resident state
     fn rsmp_fir_lockstep_new(rs: *const *mut rsmp_fir, n: usize, max_step_frames: usize) -> *mut rsmp_fir_lockstep;
     fn rsmp_fir_lockstep_free(ls: *mut rsmp_fir_lockstep);
@@ -409,6 +412,21 @@ impl ResamplerFft {
         let (mut d, mut s): (c_int, u64) = (0, 0);
         unsafe { rsmp_fft_pcm_dither(self.handle, &mut d, &mut s) };
         (d as i32, s)
+    }
+    /// Addition to the reference API: count what `resample_bulk_pcm_out_device` stores for this stream (off by default, a setting of
+    /// the handle).  The bytes do not change; `pcm_stats` reads the totals.
+    pub fn set_pcm_stats(&mut self, enable: bool) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fft_set_pcm_stats(self.handle, enable as c_int) })
+    }
+    /// Totals of every PCM-output launch of this handle since the setting was turned on or the last `pcm_stats_clear`: the statistics
+    /// `f32_to_pcm_stats` gives for the f32 output.  Waits for the handle's last launch.  All zero with the setting off.
+    pub fn pcm_stats(&mut self) -> Result<PcmStats, ResampleError> {
+        let mut st = PcmStats::default();
+        status(unsafe { rsmp_fft_pcm_stats(self.handle, &mut st) }).map(|_| st)
+    }
+    /// Zeroes the totals: ordered like a launch of the handle, enqueues nothing.
+    pub fn pcm_stats_clear(&mut self) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fft_pcm_stats_clear(self.handle) })
     }
     pub fn resample(&mut self, input: &[f32], output: &mut [f32]) -> Result<(), ResampleError> {
         status(unsafe {

@@ -558,10 +558,10 @@ int rsmp_fft_batch_resample_bulk_pcm_device(rsmp_fft* const* rs, size_t n, const
  * Served: what the two-channel pair kernel serves -- two-channel streams of one of its 19 rate pairs (44.1 <-> 48 kHz,
  * 48 <-> 96 kHz ...), at least 4 chunks in the batch's longest stream, the default library (not libresampler_amd_fftexact.so).
  * Everything else -- other channel counts, other rate pairs, fewer than 4 chunks, the exact build, out_bits not 16 / 24 / 32,
- * null arguments, misalignment, a mix of dither modes -- is RSMP_ERR_INVALID_ARGUMENT before any launch: nothing is written, no
- * state and no counter changes; take f32 output and convert with rsmp_f32_to_pcm_device.
- * Dither is a setting of the handles (rsmp_fft_set_pcm_dither below, default RSMP_DITHER_NONE).  No statistics
- * (rsmp_pcm_stats) from this store. */
+ * null arguments, misalignment, a mix of dither modes or of statistics settings -- is RSMP_ERR_INVALID_ARGUMENT before any
+ * launch: nothing is written, no state, no counter and no total changes; take f32 output and convert with rsmp_f32_to_pcm_device.
+ * Dither is a setting of the handles (rsmp_fft_set_pcm_dither below, default RSMP_DITHER_NONE), and so are the statistics of
+ * what this store did (rsmp_fft_set_pcm_stats below, default off). */
 int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, size_t n, const void* const* d_in, int in_bits,
                                                 void* const* d_out_pcm, int out_bits, const size_t* n_chunks, void* stream);
 /* Dither of the PCM the entry above writes for this handle: RSMP_DITHER_NONE (the default) or RSMP_DITHER_TPDF with the stream's
@@ -576,6 +576,27 @@ int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, size_t n, c
  * pointer may be NULL). */
 int rsmp_fft_set_pcm_dither(rsmp_fft* r, int dither, uint64_t seed);
 int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* seed);
+/* Statistics of the PCM that rsmp_fft_batch_resample_bulk_pcm_out_device writes for this handle: the twins of
+ * rsmp_fir_set_pcm_stats / rsmp_fir_pcm_stats / rsmp_fir_pcm_stats_clear.
+ * The setting belongs to the handle, is off by default and stays until it is changed (ResamplerFft has no reset).  Turning it on
+ * the first time allocates the handle's totals, one rsmp_pcm_stats of 32 bytes in device memory, zeroed.
+ * With the setting on, a launch through rsmp_fft_batch_resample_bulk_pcm_out_device counts every value it stores by
+ * rsmp_f32_to_pcm_stats's rule and merges the counts into the totals: they are exactly rsmp_f32_to_pcm_stats's of the f32
+ * entry's output for the same state, n_chunks and batch, with the handle's dither mode, its seed and first_index = abs_out * 2.
+ * Counts add over launches, the peak is the larger one.  The bytes written do not change, the overlap state ends bit-equal to
+ * the f32 entry's and abs_out advances as before.  Never counted: the block before its run that a wave recomputes and does not
+ * store; a stream with 0 chunks in the launch (its totals stay); anything the f32-output entries produce (they advance abs_out as
+ * they always did).  One setting for all the streams of a batch: a mix is RSMP_ERR_INVALID_ARGUMENT before any launch, nothing
+ * written, counted or changed -- as is every request the entry refuses with the setting off.
+ * rsmp_fft_pcm_stats waits for the handle's last launch through that launch's event -- not through the caller's stream, which
+ * may no longer exist -- and copies the 32 bytes; with the setting off it gives all zero.  A null handle or a null `stats` is
+ * RSMP_ERR_INVALID_ARGUMENT and nothing is written.
+ * rsmp_fft_pcm_stats_clear is ordered like a call of the handle and enqueues nothing itself: the handle's next counting launch
+ * starts from zero (it zeroes the totals on its own stream in front of its kernel), and rsmp_fft_pcm_stats between the clear and
+ * that launch gives zeros. */
+int rsmp_fft_set_pcm_stats(rsmp_fft* r, int enable);
+int rsmp_fft_pcm_stats(rsmp_fft* r, rsmp_pcm_stats* stats);
+int rsmp_fft_pcm_stats_clear(rsmp_fft* r);
 
 /* host-only: block sizes and the N/2-point Stockham stage lists for a rate pair
  * (planner.rs:35-245, optimizer.rs:6-64, radix_fft.rs:222-246). */

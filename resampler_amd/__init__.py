@@ -247,6 +247,9 @@ _SIGNATURES = [
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, _szp, C.c_void_p]),
     ("rsmp_fft_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("rsmp_fft_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("rsmp_fft_set_pcm_stats", C.c_int, [C.c_void_p, C.c_int]),
+    ("rsmp_fft_pcm_stats", C.c_int, [C.c_void_p, C.POINTER(PcmStats)]),
+    ("rsmp_fft_pcm_stats_clear", C.c_int, [C.c_void_p]),
     ("rsmp_fft_plan_sizes", C.c_int,
      [C.c_uint32, C.c_uint32, _szp, _szp, C.POINTER(C.c_int), _szp, C.POINTER(C.c_int), _szp, C.c_size_t]),
 ]
@@ -890,6 +893,24 @@ class ResamplerFft:
         d, s = C.c_int(), C.c_uint64()
         _check(lib().rsmp_fft_pcm_dither(self._h, C.byref(d), C.byref(s)))
         return d.value, s.value
+
+    def set_pcm_stats(self, enable: bool) -> None:
+        """Statistics of the PCM that FftBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fft_set_pcm_stats): off by
+        default, a setting of the handle.  With it on a launch counts every value it stores -- the bytes do not change -- and
+        pcm_stats() reads the totals.  One setting for all the streams of a batch."""
+        _check(lib().rsmp_fft_set_pcm_stats(self._h, 1 if enable else 0))
+
+    def pcm_stats(self) -> PcmStats:
+        """Totals of every PCM-output launch of this handle since the setting was turned on or the last pcm_stats_clear()
+        (rsmp_fft_pcm_stats: waits for the handle's last launch): f32_to_pcm_stats' of the f32 output with the handle's dither, seed
+        and first_index = output frames before the launch * 2.  All zero with the setting off."""
+        st = PcmStats()
+        _check(lib().rsmp_fft_pcm_stats(self._h, C.byref(st)))
+        return st
+
+    def pcm_stats_clear(self) -> None:
+        """Zeroes the totals (rsmp_fft_pcm_stats_clear): ordered like a launch of the handle, enqueues nothing."""
+        _check(lib().rsmp_fft_pcm_stats_clear(self._h))
 
 
 class FftBatch:

@@ -160,6 +160,13 @@ struct rsmp_fft {
     uint64_t abs_out = 0;
     int pcm_dither = RSMP_DITHER_NONE;
     uint64_t pcm_dither_seed = 0;
+    // Statistics of the PCM the pair kernel stores for this handle (rsmp_fft_set_pcm_stats): a setting like the dither.  The totals
+    // are one rsmp_pcm_stats in device memory, allocated and zeroed when the setting is first turned on; the counting builds
+    // (fft_pair_pcm_stats.hip) merge into it.  A clear sets pcm_stats_cleared and nothing else: the handle's next counting launch
+    // zeroes the totals on its own stream in front of its kernel, and rsmp_fft_pcm_stats answers zeros meanwhile.
+    bool pcm_stats = false;
+    bool pcm_stats_cleared = false;
+    rsmp_pcm_stats* d_pcm_stats = nullptr;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // the stream of the handle's previous launch (launches of one handle are ordered)
     bool last_stream_valid = false;
@@ -196,12 +203,17 @@ struct FftJob {
 };
 
 // out_bits != 0: the jobs' d_out are byte buffers that receive PCM of that width (the caller has asked fft_pcm_out_served);
-// the streams' FftPcmOutDesc travel behind the descriptors, in the same table.
-int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0) {
+// the streams' FftPcmOutDesc travel behind the descriptors, in the same table.  stats (with out_bits != 0; every handle has the
+// setting on): the counting builds, and the handles' totals -- a pointer per stream -- as a third array behind those.
+int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0,
+                    bool stats = false) {
     const size_t n = jobs.size();
     static_assert(sizeof(FftStreamDesc) % alignof(FftPcmOutDesc) == 0, "the PCM-output array starts where the descriptors end");
+    static_assert((sizeof(FftStreamDesc) + sizeof(FftPcmOutDesc)) % alignof(rsmp_pcm_stats*) == 0, "the totals' pointers start where the PCM-output array ends");
     const size_t desc_bytes = n * sizeof(FftStreamDesc);
-    const size_t bytes = desc_bytes + (out_bits != 0 ? n * sizeof(FftPcmOutDesc) : 0);
+    const size_t acc_off = desc_bytes + (out_bits != 0 ? n * sizeof(FftPcmOutDesc) : 0);
+    // (all three arrays count towards the 16 KB of a table that is read in place, below)
+    const size_t bytes = acc_off + (stats ? n * sizeof(rsmp_pcm_stats*) : 0);
     // A handle's launches are ordered (&mut self in the reference): launch k + 1 reads the overlap rows launch k
     // writes, so a caller that changes streams between two calls waits here for the first -- as the FIR path does.
     // A handle listed twice in one batch would read one old state through both descriptors: refused.
@@ -217,6 +229,16 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
             RSMP_HIP_CHECK(rsmp::stream_wait_event(stream, h->last_launch->ev));
         h->last_stream = stream;
         h->last_stream_valid = true;
+    }
+    // A clear since the handle's last counting launch: its totals are zeroed here, on this launch's stream, behind everything the
+    // handle has launched (the wait above) and in front of the kernel that counts.  (A stream without blocks in this launch
+    // stores nothing: its flag stays, and its totals read as zeros until a launch of its own.)
+    for (size_t i = 0; stats && i < n; ++i) {
+        rsmp_fft* h = jobs[i].r;
+        if (h->pcm_stats_cleared && jobs[i].n_blocks != 0) {
+            RSMP_HIP_CHECK(hipMemsetAsync(h->d_pcm_stats, 0, sizeof(rsmp_pcm_stats), stream));
+            h->pcm_stats_cleared = false;
+        }
     }
     // (a launch of a block or two per stream -- a streaming call -- keeps the upload: the table read over the host link at the
     // kernel's start is on its critical path there, 33.6 against 32.1 us per call)
@@ -266,6 +288,8 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
     FftPcmOutDesc* h_pcm = out_bits != 0 ? reinterpret_cast<FftPcmOutDesc*>(h + n) : nullptr;
     for (size_t i = 0; h_pcm && i < n; ++i)
         h_pcm[i] = FftPcmOutDesc{jobs[i].r->pcm_dither_seed, jobs[i].r->abs_out, static_cast<uint32_t>(jobs[i].r->pcm_dither), 0};
+    rsmp_pcm_stats** h_acc = stats ? reinterpret_cast<rsmp_pcm_stats**>(reinterpret_cast<char*>(h) + acc_off) : nullptr;
+    for (size_t i = 0; h_acc && i < n; ++i) h_acc[i] = jobs[i].r->d_pcm_stats;
     const FftStreamDesc* d_descs = h;   // (mapped host memory: the same address on the device)
     if (!direct) {
         RSMP_HIP_CHECK(hipMemcpyAsync(leader->d_desc.get(), h, bytes, hipMemcpyHostToDevice, stream));
@@ -274,10 +298,11 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
         d_descs = leader->d_desc.as<FftStreamDesc>();
     }
     const FftPcmOutDesc* d_pcm = out_bits != 0 ? reinterpret_cast<const FftPcmOutDesc*>(d_descs + n) : nullptr;
+    rsmp_pcm_stats* const* d_acc = stats ? reinterpret_cast<rsmp_pcm_stats* const*>(reinterpret_cast<const char*>(d_descs) + acc_off) : nullptr;
     if (leader->profiling) RSMP_HIP_CHECK(rsmp::event_record(leader->prof_start, stream));
     {
         const hipError_t e = rsmp::launch_fft_ola(leader->plan->dev, d_descs, static_cast<uint32_t>(n),
-                                                  max_blocks, max_channels, min_channels, stream, pcm_bits, out_bits, d_pcm);
+                                                  max_blocks, max_channels, min_channels, stream, pcm_bits, out_bits, d_pcm, d_acc);
         if (e == hipErrorNotSupported && pcm_bits != 0)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "ResamplerFft: PCM input is read in place by the two-channel wave kernel only "
                                                        "(this rate pair / channel count has none): convert with rsmp_pcm_to_stereo_f32_device first");
@@ -356,6 +381,7 @@ extern "C" void rsmp_fft_free(rsmp_fft* r) {
     DeviceGuard guard(r->device);
     (void)hipDeviceSynchronize();
     if (r->d_overlap) (void)hipFree(r->d_overlap);
+    if (r->d_pcm_stats) (void)hipFree(r->d_pcm_stats);
     if (r->desc_copied) (void)hipEventDestroy(r->desc_copied);
     for (hipEvent_t e : r->desc_read)
         if (e) (void)hipEventDestroy(e);
@@ -517,6 +543,8 @@ extern "C" int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, 
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one device and one rate pair and have two channels (%s)", kWayOut);
         if (rs[i]->pcm_dither != rs[0]->pcm_dither)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one dither mode: stream %zu differs (%s)", i, kWayOut);
+        if (rs[i]->pcm_stats != rs[0]->pcm_stats)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one statistics setting (rsmp_fft_set_pcm_stats): stream %zu differs", i);
         if (!d_in[i] || !d_out_pcm[i])
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_batch_resample_bulk_pcm_out_device: null buffer of stream %zu (%s)", i, kWayOut);
         if (in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % (in_bits == 32 ? 16 : in_bits == 16 ? 8 : 4) != 0)
@@ -538,7 +566,7 @@ extern "C" int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, 
     jobs.reserve(n);
     for (size_t i = 0; i < n; ++i)
         jobs.push_back(FftJob{rs[i], static_cast<const float*>(d_in[i]), static_cast<float*>(d_out_pcm[i]), n_chunks[i]});
-    return launch_fft_jobs(rs[0], jobs, s, static_cast<uint32_t>(in_bits), static_cast<uint32_t>(out_bits));
+    return launch_fft_jobs(rs[0], jobs, s, static_cast<uint32_t>(in_bits), static_cast<uint32_t>(out_bits), rs[0]->pcm_stats);
 }
 
 extern "C" int rsmp_fft_set_pcm_dither(rsmp_fft* r, int dither, uint64_t seed) {
@@ -553,5 +581,44 @@ extern "C" int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* see
     if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_dither: null handle");
     if (dither) *dither = r->pcm_dither;
     if (seed) *seed = r->pcm_dither_seed;
+    return RSMP_OK;
+}
+
+// PCM output's statistics: a setting of the handle like the dither (there is no reset to survive); the totals live in device memory.
+extern "C" int rsmp_fft_set_pcm_stats(rsmp_fft* r, int enable) {
+    if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_set_pcm_stats: null handle");
+    if (enable && !r->d_pcm_stats) {
+        DeviceGuard guard(r->device);
+        rsmp_pcm_stats* d = nullptr;
+        RSMP_HIP_CHECK(hipMalloc(&d, sizeof(rsmp_pcm_stats)));
+        // (the handle's streams are non-blocking: the zeroes are in place before any of them can run a counting launch)
+        if (hipMemset(d, 0, sizeof(rsmp_pcm_stats)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(d);
+            return rsmp::fail(RSMP_ERR_HIP, "rsmp_fft_set_pcm_stats: cannot zero the totals");
+        }
+        r->d_pcm_stats = d;
+        r->pcm_stats_cleared = false;
+    }
+    r->pcm_stats = enable != 0;
+    return RSMP_OK;
+}
+
+// Waits for the handle's last launch through its event -- the caller's stream may be gone by now --, then copies the 32 bytes.
+extern "C" int rsmp_fft_pcm_stats(rsmp_fft* r, rsmp_pcm_stats* stats) {
+    if (!r || !stats) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_stats: null argument");
+    rsmp_pcm_stats t{};
+    if (r->pcm_stats && !r->pcm_stats_cleared && r->d_pcm_stats) {
+        DeviceGuard guard(r->device);
+        if (r->last_launch) RSMP_HIP_CHECK(hipEventSynchronize(r->last_launch->ev));
+        RSMP_HIP_CHECK(hipMemcpy(&t, r->d_pcm_stats, sizeof t, hipMemcpyDeviceToHost));
+    }
+    *stats = t;
+    return RSMP_OK;
+}
+
+// Ordered like a call of the handle, enqueues nothing: the next counting launch starts from zero (launch_fft_jobs).
+extern "C" int rsmp_fft_pcm_stats_clear(rsmp_fft* r) {
+    if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_stats_clear: null handle");
+    if (r->d_pcm_stats) r->pcm_stats_cleared = true;
     return RSMP_OK;
 }

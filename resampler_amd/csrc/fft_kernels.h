@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "../../include/resampler_amd.h"   // rsmp_pcm_stats
 #include "fft_launch.h"
 
 namespace rsmp {
@@ -57,7 +58,11 @@ struct FftPcmOutDesc {
 // (FftStreamDesc::out_bits); hipErrorNotSupported where the launch is not the pair kernel's (fft_pcm_out_served).
 hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
                           uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                          hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0, const FftPcmOutDesc* d_pcm = nullptr);
+                          hipStream_t stream, uint32_t pcm_bits = 0, uint32_t out_bits = 0, const FftPcmOutDesc* d_pcm = nullptr,
+                          rsmp_pcm_stats* const* d_acc = nullptr);
+// d_acc != nullptr (with out_bits != 0): the launch also counts what it stores (the counting builds, fft_pair_pcm_stats.hip) and
+// merges stream i's counts into *d_acc[i], its handle's totals in device memory -- a table of its own behind the FftPcmOutDesc
+// array, whose 24 bytes per stream every PCM build reads and which therefore stays as it is.
 // Whether a launch of two-channel streams with PCM output gets a kernel: asked before anything is touched.
 bool fft_pcm_out_served(const FftPlanDev& plan, uint32_t n_streams, uint32_t max_blocks, uint32_t pcm_bits, uint32_t out_bits);
 // The kernel files' launchers: the build `c` names (fft_choose), launched as it says; hipErrorNotSupported where the file
@@ -66,6 +71,8 @@ bool fft_pcm_out_served(const FftPlanDev& plan, uint32_t n_streams, uint32_t max
 hipError_t launch_fft_ola_pair(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream);
 hipError_t launch_fft_ola_pair_pcm_out(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, const FftPcmOutDesc* d_pcm,
                                        hipStream_t stream);   // fft_pair_pcm_out.hip: the pair launch of a request with out_bits != 0
+hipError_t launch_fft_ola_pair_pcm_stats(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, const FftPcmOutDesc* d_pcm,
+                                         rsmp_pcm_stats* const* d_acc, hipStream_t stream);   // fft_pair_pcm_stats.hip: ... and pcm_stats
 hipError_t launch_fft_ola_wave(const FftLaunch& c, const FftPlanDev& plan, const FftStreamDesc* d_descs, hipStream_t stream);
 hipError_t launch_fft_ola_workgroup(FftLaunch c, const FftRequest& rq, const FftPlanDev& plan, const FftStreamDesc* d_descs,
                                     hipStream_t stream);

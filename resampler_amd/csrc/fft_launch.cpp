@@ -201,10 +201,14 @@ FftLaunch fft_choose(const FftShape& s, const FftRequest& rq) {
     // (PCM input is read by the two-channel kernels only: FftStreamDesc::in_bits)
     if (rq.pcm_bits != 0 && (no_wave || !stereo)) return out;
     if (rq.out_bits != 0 && rq.out_bits != 16 && rq.out_bits != 24 && rq.out_bits != 32) return out;
+    if (rq.pcm_stats && rq.out_bits == 0) return out;   // (the statistics are of a PCM store: an f32 launch has none)
     // two-channel streams: a wave per stream, the frame as one complex sample (not in the exact build)
     // (a launch of a block or two per stream is a streaming call: there the wave-per-channel kernel's two waves per stream
     // finish sooner than one wave running both chains -- 32.6 against 36.3 us per one-block call, tools/fft_call_latency.py)
-    if (!no_wave && !no_pair && stereo && rq.max_blocks >= 4 && !rq.exact && choose_pair(s, rq, &out)) return out;
+    if (!no_wave && !no_pair && stereo && rq.max_blocks >= 4 && !rq.exact && choose_pair(s, rq, &out)) {
+        out.pcm_stats = rq.pcm_stats;   // (which kernel file's build, fft_launch_hip.cpp: nothing of the launch depends on it)
+        return out;
+    }
     // (PCM output is stored by the pair kernel only: FftStreamDesc::out_bits)
     if (rq.out_bits != 0) return FftLaunch{};
     if (!no_wave && (choose_wave(s, rq, &out) || rq.pcm_bits != 0)) return out;

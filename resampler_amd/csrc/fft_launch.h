@@ -28,6 +28,9 @@ struct FftRequest {
     // 0: f32 output.  16 / 24 / 32: PCM of that width from the kernel's store -- the pair kernel's launch exactly as for
     // out_bits = 0 (the same cut into runs), kNotSupported where that request would get another family.
     uint32_t out_bits = 0;
+    // The counting builds of the PCM store (fft_pair_pcm_stats.hip): the launch of the same request without it, field for field
+    // -- the flag picks the kernel file, nothing else --; with out_bits = 0 there is nothing to count: kNotSupported.
+    bool pcm_stats = false;
 };
 
 enum class FftFamily : uint8_t {
@@ -55,6 +58,7 @@ struct FftLaunch {
     // pair: the runs of the four ages, groups per stream, total_waves; workgroup kernels: run
     uint32_t args[6] = {0, 0, 0, 0, 0, 0};
     int n_args = 0;
+    bool pcm_stats = false;   // pair, out_bits != 0: the request's flag, carried to the launcher (fft_pair_pcm_stats.hip's builds)
 };
 
 // Blocks per run.  Every run after a stream's first recomputes its predecessor block (1 / run extra work), and the launch

@@ -24,11 +24,12 @@ size_t fft_ola_lds_bytes(const FftPlanDev& plan, uint32_t channels) { return fft
 
 namespace {
 
-FftRequest request_of(uint32_t n_streams, uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels, uint32_t pcm_bits, uint32_t out_bits) {
+FftRequest request_of(uint32_t n_streams, uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels, uint32_t pcm_bits, uint32_t out_bits,
+                      bool pcm_stats = false) {
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return FftRequest{n_streams, max_blocks, max_channels, min_channels, pcm_bits, fft_wave_is_exact(), cus, out_bits};
+    return FftRequest{n_streams, max_blocks, max_channels, min_channels, pcm_bits, fft_wave_is_exact(), cus, out_bits, pcm_stats};
 }
 
 }  // namespace
@@ -40,12 +41,13 @@ bool fft_pcm_out_served(const FftPlanDev& plan, uint32_t n_streams, uint32_t max
 
 hipError_t launch_fft_ola(const FftPlanDev& plan, const FftStreamDesc* d_descs, uint32_t n_streams,
                           uint32_t max_blocks, uint32_t max_channels, uint32_t min_channels,
-                          hipStream_t stream, uint32_t pcm_bits, uint32_t out_bits, const FftPcmOutDesc* d_pcm) {
+                          hipStream_t stream, uint32_t pcm_bits, uint32_t out_bits, const FftPcmOutDesc* d_pcm, rsmp_pcm_stats* const* d_acc) {
     if (n_streams == 0 || max_blocks == 0) return hipSuccess;
-    const FftRequest rq = request_of(n_streams, max_blocks, max_channels, min_channels, pcm_bits, out_bits);
+    const FftRequest rq = request_of(n_streams, max_blocks, max_channels, min_channels, pcm_bits, out_bits, d_acc != nullptr);
     const FftLaunch c = fft_choose(shape_of(plan), rq);
     switch (c.family) {
         case FftFamily::kPair:
+            if (c.pcm_stats) return launch_fft_ola_pair_pcm_stats(c, plan, d_descs, d_pcm, d_acc, stream);
             return out_bits != 0 ? launch_fft_ola_pair_pcm_out(c, plan, d_descs, d_pcm, stream) : launch_fft_ola_pair(c, plan, d_descs, stream);
         case FftFamily::kWave: return launch_fft_ola_wave(c, plan, d_descs, stream);
         case FftFamily::kNotSupported: return hipErrorNotSupported;

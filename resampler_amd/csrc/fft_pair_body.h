@@ -1,7 +1,8 @@
 // fft_pair_body.h -- ResamplerFft block pipeline for TWO-CHANNEL streams: ONE WAVE per stream, the two channels of a frame
 // taken as ONE complex sample (gfx950).  The kernel; included once by fft_pair.hip (RSMP_PAIR_PCM_OUT 0: fft_ola_pair_kernel,
-// f32 output) and once by fft_pair_pcm_out.hip (RSMP_PAIR_PCM_OUT 1: fft_ola_pair_pcm_kernel, PCM output), which instantiate the
-// builds side by side under make -j.
+// f32 output), once by fft_pair_pcm_out.hip (RSMP_PAIR_PCM_OUT 1: fft_ola_pair_pcm_kernel, PCM output) and once by
+// fft_pair_pcm_stats.hip (RSMP_PAIR_PCM_OUT 2: fft_ola_pair_pcm_stats_kernel, PCM output that counts what it stores), which
+// instantiate the builds side by side under make -j.
 //
 // Replaces the same reference code as fft_wave.hip (FftResampler::resample, src/resampler_fft.rs:385-424; RadixFFT
 // forward / inverse, src/fft/radix_fft.rs:476-670; the Stockham stages and butterflies) -- and with it the two
@@ -41,7 +42,7 @@
 #pragma once
 
 #ifndef RSMP_PAIR_PCM_OUT
-#error "RSMP_PAIR_PCM_OUT: 0 (fft_pair.hip) or 1 (fft_pair_pcm_out.hip)"
+#error "RSMP_PAIR_PCM_OUT: 0 (fft_pair.hip), 1 (fft_pair_pcm_out.hip) or 2 (fft_pair_pcm_stats.hip)"
 #endif
 
 #include <type_traits>
@@ -296,7 +297,13 @@ __device__ __forceinline__ int32_t pair_pcm_code(float v, int32_t bottom, int32_
 // upper two; odd g: L's low two, then L's top byte and R).  A lane writes its frame's own bytes and no others; non-temporal like
 // the f32 frames.  Width and mode are the same for every lane of the wave; the product by the power of two and the sum with the
 // noise are separate operations, as in the converters.
+// RSMP_PAIR_PCM_OUT 2: `st` also takes what was done to the two values, by fir_pcm_stat's rule, from the x, the scaled value and the
+// rounded value that the store uses (its `values` is not used: the wave knows how many frames it emitted).
+#if RSMP_PAIR_PCM_OUT == 2
+__device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const FftPcmOutDesc& po, size_t frame0, uint32_t n, cf v, FirPcmStat& st) {
+#else
 __device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const FftPcmOutDesc& po, size_t frame0, uint32_t n, cf v) {
+#endif
 #pragma clang fp contract(off)
     typedef __attribute__((address_space(1))) char GChar;
     typedef __attribute__((address_space(1))) uint16_t GU16;
@@ -312,7 +319,14 @@ __device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const Fft
         sl += fir_dither_value(static_cast<uint32_t>(w));
         sr += fir_dither_value(static_cast<uint32_t>(w >> 32));
     }
+#if RSMP_PAIR_PCM_OUT == 2
+    const float vl = rintf(sl), vr = rintf(sr);
+    fir_pcm_stat(v.x, vl, bits, st);
+    fir_pcm_stat(v.y, vr, bits, st);
+    const uint32_t l = static_cast<uint32_t>(pair_pcm_code(vl, bottom, top)), r = static_cast<uint32_t>(pair_pcm_code(vr, bottom, top));
+#else
     const uint32_t l = static_cast<uint32_t>(pair_pcm_code(rintf(sl), bottom, top)), r = static_cast<uint32_t>(pair_pcm_code(rintf(sr), bottom, top));
+#endif
     // (the block's first byte is the same for every lane; a lane's offset within the block fits 32 bits)
     GChar* block = (GChar*)d.out + frame0 * (bits / 4);
     if (bits == 16) {
@@ -340,12 +354,23 @@ constexpr int pair_waves() { return pair_budget<FWD, INV>(kWholeRows).waves; }
 // FftPcmOutDesc::dither = RSMP_DITHER_TPDF, by rsmp_f32_to_pcm_dither's with the index (abs_out + frame) * 2 + channel: the
 // bytes are the converter's of the f32 build's output.  The width and the dither mode are uniform run-time values, so a rate
 // pair and input width has ONE such build.  The overlap stays f32.  `pcm`: the streams' FftPcmOutDesc, read by these builds only.
+// RSMP_PAIR_PCM_OUT 2, the counting builds (one more per rate pair and input width): the same stores, and every lane keeps a
+// FirPcmStat in registers over all the blocks of its run -- clipped, nans and peak of the values it stored (pair_pcm_store) --;
+// at the end of the run the wave's 64 lanes, those without a frame with their zeros, sum them once (fir_stat_wave_sum) and one
+// lane merges the wave's share into the stream's totals `acc[stream]` (rsmp_pcm_stats in device memory): 64-bit atomic adds for
+// the counts, an unsigned maximum on the peak's bit pattern, none for a zero.  `values` is the frames the wave emitted, times two.
+// The predecessor block a run recomputes is not stored and so not counted; a wave that returns early has counted nothing.
 //
 // The output mode is the including file's RSMP_PAIR_PCM_OUT and not a template parameter: the f32 kernel keeps its name and,
 // token for token, its text, so fft_pair.o's machine code is what it was before the PCM builds existed (a parameter renames
 // every build; the body as an inlined function under two kernels compiled 75 of the 76 builds to other code).
 template <class FWD, class INV, int BITS>
-#if RSMP_PAIR_PCM_OUT
+#if RSMP_PAIR_PCM_OUT == 2
+__global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 4) * 64, 1) void fft_ola_pair_pcm_stats_kernel(FftPlanDev plan, const FftStreamDesc* __restrict__ descs,
+                                                              const FftPcmOutDesc* __restrict__ pcm, rsmp_pcm_stats* const* __restrict__ acc,
+                                                              uint32_t run0, uint32_t run1, uint32_t run2, uint32_t run3,
+                                                              uint32_t pairs_per_stream, uint32_t total_waves) {
+#elif RSMP_PAIR_PCM_OUT
 __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 4) * 64, 1) void fft_ola_pair_pcm_kernel(FftPlanDev plan, const FftStreamDesc* __restrict__ descs,
                                                               const FftPcmOutDesc* __restrict__ pcm,
                                                               uint32_t run0, uint32_t run1, uint32_t run2, uint32_t run3,
@@ -460,6 +485,9 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
             for (int q = 0; q < RLI; ++q) carry[it][q] = lane + 64 * it < MI ? cf_make(ca[it][q], -cb[it][q]) : cf_make(0.f, 0.f);
     }
     const int64_t b_begin = first == 0 ? 0 : static_cast<int64_t>(first) - 1;
+#if RSMP_PAIR_PCM_OUT == 2
+    FirPcmStat stat{0, 0, 0, 0};   // what this lane stored, over the whole run
+#endif
 
     for (int64_t b = b_begin; b < static_cast<int64_t>(last); ++b) {
         const bool emit = b >= static_cast<int64_t>(first);
@@ -630,7 +658,11 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
                                 // every block, and hoisted out of the block loop it would occupy registers for all 24 frames of a lane)
                                 uint32_t n = static_cast<uint32_t>(i + q * MI);
                                 asm volatile("" : "+v"(n));
+#if RSMP_PAIR_PCM_OUT == 2
+                                pair_pcm_store(d, po, out_frame0, n, v, stat);
+#else
                                 pair_pcm_store(d, po, out_frame0, n, v);
+#endif
 #elif RSMP_FEAT & 1
                                 xout[i + q * MI] = f2{v.x, v.y};
 #else
@@ -674,6 +706,22 @@ __global__ __launch_bounds__((pair_waves<FWD, INV>() ? pair_waves<FWD, INV>() : 
             }
         }
     }
+#if RSMP_PAIR_PCM_OUT == 2
+    {
+        // (all 64 lanes are here: the branches above are on the lane's frames, none returns)
+        stat.values = 0;
+        const FirPcmStat w = fir_stat_wave_sum(stat);
+        if (lane == 0) {
+            typedef unsigned long long u64a;
+            rsmp_pcm_stats* t = acc[stream_idx];
+            static_assert(sizeof(u64a) == sizeof(uint64_t) && sizeof(rsmp_pcm_stats) == 32, "rsmp_pcm_stats: three 64-bit counts, the peak's bits, a reserved word");
+            (void)atomicAdd(reinterpret_cast<u64a*>(&t->values), static_cast<u64a>(last - first) * (2u * FO));
+            if (w.clipped) (void)atomicAdd(reinterpret_cast<u64a*>(&t->clipped), static_cast<u64a>(w.clipped));
+            if (w.nans) (void)atomicAdd(reinterpret_cast<u64a*>(&t->nans), static_cast<u64a>(w.nans));
+            if (w.peak) (void)atomicMax(reinterpret_cast<uint32_t*>(&t->peak), w.peak);
+        }
+    }
+#endif
 }
 
 }  // namespace
