@@ -344,7 +344,9 @@ def test_whole_file_driver_matches_reference_loop():
 def test_even_channel_counts_run_as_channel_pairs(ch, in_hz, out_hz, blocks):
     """Streams of 4, 6, 8 .. channels: channel pairs on the two-channel wave kernel (8-byte accesses at the frame's
     stride, the pair's waves exchange their final values through LDS).  Expectation: the reference run per channel;
-    two bulk calls, so the second starts from a carried overlap and both contain more than one run of blocks."""
+    two bulk calls, so the second starts from a carried overlap and both contain more than one run of blocks.
+    (Nine rate pairs here; tests/test_fft_wave_builds_gpu.py runs the channel-pairs build of every plan of WavePairs, with 4 and
+    6 channels, against the f64 reference.)"""
     torch = pytest.importorskip("torch")
     dev = torch.device("cuda:0")
     g = ra.ResamplerFft.new(ch, sr(in_hz), sr(out_hz))

@@ -313,3 +313,98 @@ def test_lockstep_rules_as_before_the_move(tmp_path):
     for setting, switches in maker.SHAPE_SETTINGS.items():
         assert rows_of("shape", switches).splitlines() == fx["shape"][setting] and len(fx["shape"][setting]) == 11 * 8, setting
     assert len({tuple(fx["shape"][s]) for s in fx["shape"]}) == 4   # (every switch changes rows)
+
+
+# ---- the builds of the FFT wave kernel that tests/test_fft_wave_builds_gpu.py launches ------------------------------------------
+def test_fft_wave_builds_fixture_names_every_build(tmp_path):
+    """tests/host/fft_wave_builds_dump.cpp (plain C++, g++ with ASan + UBSan, linked with fft_launch.cpp): what the launch rules
+    answer, on 256 CUs in the ordinary library, to every request of tests/test_fft_wave_builds_gpu.py for every ordered pair of the
+    ten sample rates, and the budget of every entry of WavePairs straight from fft_wave_plan.h -- byte for byte
+    tests/golden/fft_wave_builds.json, which so cannot go stale.  From the fixture and the GPU module's own table of cases:
+      - PAIRS there is WavePairs, entry for entry (block sizes, membership of PairPairs), so a 49th pair has no case and fails here;
+      - every launch of every case answers `wave` with the case's plan, the CHM of its channel count and the OCC of the plan's
+        budget: together all 48 x 3 = 144 builds of fft_wave.hip, of which every PCM request names a CHM 1 build and none of a
+        short case the pair kernel;
+      - a long case's first launch has two runs per stream or more: the second recomputes its predecessor block;
+      - OCC 1, 2 and 3 occur, the OCC = 1 workgroups are 128 to 512 threads wide and the widths 2, 3, 4, 6 and 8 waves all occur;
+      - the 72 rate pairs with a wave build reach all 48 entries; the other 18 answer notsupported to two-channel PCM of every
+        width, whatever the launch."""
+    import test_fft_wave_builds_gpu as w   # (its table of cases: nothing of it needs a GPU)
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fft_wave_builds_dump.cpp"
+    exe = str(tmp_path / "fft_wave_builds_dump")
+    srcs = [os.path.join(ROOT, "tests", "host", "fft_wave_builds_dump.cpp")]
+    srcs += [os.path.join(CSRC, f) for f in ("fft_launch.cpp", "fft_plan.cpp", "filter_design.cpp", "common.cpp")]
+    subprocess.run([gxx] + SANITIZE + ["-Wno-unknown-pragmas"] + srcs + ["-o", exe], check=True)
+    run = subprocess.run([exe], env={k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}, capture_output=True, text=True, timeout=300)
+    _clean(run)
+    with open(os.path.join(ROOT, "tests", "golden", "fft_wave_builds.json")) as fh:
+        text = fh.read()
+    assert run.stdout == text, "tests/golden/fft_wave_builds.json is not what tests/host/fft_wave_builds_dump.cpp prints"
+    fx = json.loads(text)
+    assert fx["cus"] == 256
+
+    # ---- WavePairs, from the header: index fft_in fft_out served occ_any occ_c2 wide in_pair_pairs
+    budgets = [tuple(int(v) for v in p.split()) for p in fx["pairs"]]
+    assert [b[0] for b in budgets] == list(range(len(budgets))) and len(budgets) == len(w.PAIRS) == 48
+    assert [b[1:3] for b in budgets] == [p[2:] for p in w.PAIRS]
+    assert all(b[3] == 1 for b in budgets)
+    assert tuple(b[0] for b in budgets if b[7]) == w.IN_PAIR_PAIRS and len(w.IN_PAIR_PAIRS) == 19
+
+    def launch_of(text):
+        f = text.split()
+        out = {"request": (int(f[0]), int(f[1])), "family": f[2]}
+        out.update((k, v) for k, v in (kv.split("=") for kv in f[3:]))
+        return out
+
+    rows = {}
+    for row in fx["rows"]:
+        head, case, *launches = row.split(" | ")
+        in_hz, out_hz, fi, fo = (int(v) for v in head.split())
+        channels, bits, kind = case.split()
+        assert ((in_hz, out_hz), (int(channels), int(bits), kind == "refuse")) not in rows
+        rows[(in_hz, out_hz), (int(channels), int(bits), kind == "refuse")] = (fi, fo, kind, [launch_of(t) for t in launches])
+    rate_pairs = sorted({k[0] for k in rows})
+    assert len(rate_pairs) == 90 and len(rows) == 90 * (len(w.IO) + 1)
+
+    # ---- the GPU module's cases
+    chm_of = {1: 0, 3: 0, 2: 1, 4: 2, 6: 2}
+    builds, widths, short_cases = set(), set(), 0
+    for pair, (in_hz, out_hz, fi, fo) in enumerate(w.PAIRS):
+        _, _, _, served, occ_any, occ_c2, wide, _ = budgets[pair]
+        for channels, bits in w.IO:
+            r_fi, r_fo, kind, launches = rows[(in_hz, out_hz), (channels, bits, False)]
+            case = (pair, channels, bits)
+            assert (r_fi, r_fo) == (fi, fo), case
+            assert kind == ("short" if w.launches_of(pair, channels) is w.SHORT else "long"), case
+            assert [ln["request"] for ln in launches] == w.requests_of(pair, channels), case
+            short_cases += kind == "short"
+            for ln in launches:
+                want_occ = occ_c2 if channels == 2 else occ_any
+                assert (ln["family"], int(ln["pair"]), int(ln["chm"]), int(ln["occ"])) == ("wave", pair, chm_of[channels], want_occ), (case, ln)
+                builds.add((pair, int(ln["chm"]), int(ln["occ"])))
+                if want_occ == 1:
+                    assert int(ln["block"]) == 64 * wide and 128 <= int(ln["block"]) <= 512, (case, ln)
+                    widths.add(wide)
+            if kind == "long":
+                assert int(launches[0]["args"].split(",")[1]) >= 2, case   # runs_per_stream
+    assert short_cases == 19 * 4
+    assert builds == {(p, chm, b[5] if chm == 1 else b[4]) for p, b in enumerate(budgets) for chm in (0, 1, 2)} and len(builds) == 144
+    assert {b[2] for b in builds} == {1, 2, 3} and widths == {2, 3, 4, 6, 8}
+
+    # ---- the other rate pairs
+    reached, refused = set(), []
+    for rp in rate_pairs:
+        mono = rows[rp, (1, 0, False)][3][0]
+        if mono["family"] == "wave":
+            reached.add(int(mono["pair"]))
+            assert rows[rp, (1, 0, False)][:2] == w.PAIRS[int(mono["pair"])][2:], rp
+            for bits in (16, 24, 32):
+                assert all((ln["family"], ln["chm"]) == ("wave", "1") for ln in rows[rp, (2, bits, False)][3]), (rp, bits)
+        else:
+            refused.append(rp)
+            assert rows[rp, (2, 16, True)][3][0]["family"] == "notsupported", rp
+            assert rows[rp, (2, 16, True)][3][1]["family"] in ("generic", "big"), rp   # (the f32 launch that follows)
+            for bits in (16, 24, 32):
+                assert all(ln["family"] == "notsupported" for ln in rows[rp, (2, bits, False)][3]), (rp, bits)
+    assert reached == set(range(48)) and len(refused) == 18 and len(rate_pairs) - len(refused) == 72

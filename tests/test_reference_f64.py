@@ -311,5 +311,72 @@ def test_fft_defects_are_rejected_at_the_margins_in_use(fft_setup, name):
     assert old_rms <= OLD_RMS_GATE
     assert r_rms > R.MARGINS["fft"][0], (r_rms, R.MARGINS["fft"])
     assert r_rms > R.MARGINS["fft_pair_io"][0], (r_rms, R.MARGINS["fft_pair_io"])   # (the pair kernel's builds, a few blocks each)
+    assert r_rms > R.MARGINS["fft_wave_builds"][0], (r_rms, R.MARGINS["fft_wave_builds"])   # (the wave kernel's builds, likewise)
     clean = R.budget(s["ref"].astype(np.float32), s["ref"], s["yard"])
+    assert clean[0] <= 1.0 and clean[1] <= 1.0
+
+
+# ---- the gate of tests/test_fft_wave_builds_gpu.py can fail ---------------------------------------------------------------
+def fft_f64_forgetting(x, channels, in_hz, out_hz, blocks, forget):
+    """R.fft_f64 with a defect in what it carries: in front of block b the frames forget[b] (a slice) of the overlap are zero."""
+    fi, fo, _, _ = o.fft_plan(in_hz, out_hz)
+    H = R.fft_filter_f64(fi, fo)
+    keep = min(fi + 1, fo)
+    xs = x[:blocks * fi * channels].reshape(blocks, fi, channels).astype(np.float64)
+    out = np.empty((blocks, fo, channels), np.float64)
+    for c in range(channels):
+        overlap = np.zeros(fo, np.float64)
+        for b in range(blocks):
+            if b in forget:
+                overlap[forget[b]] = 0.0
+            buf = np.zeros(2 * fi, np.float64)
+            buf[:fi] = xs[b, :, c]
+            spec = np.zeros(fo + 1, np.complex128)
+            spec[:keep] = np.fft.rfft(buf)[:keep] * H[:keep]
+            y = np.fft.irfft(spec, 2 * fo) * float(2 * fo)
+            out[b, :, c] = y[:fo] + overlap
+            overlap = y[fo:]
+    return out.reshape(-1)
+
+
+# name, the overlap frames forgotten in front of which block of stream 0, passes the older gate, rejected by which bound
+OVERLAP_DEFECTS = [
+    ("second launch starts from a zero overlap", {9: slice(None)}, False, "rms"),
+    ("second run starts from a zero overlap", {6: slice(None)}, False, "rms"),
+    ("second run forgets the last frame of the overlap", {6: slice(63, 64)}, True, "max"),
+]
+
+
+@pytest.mark.parametrize("name,forget,passes_today,rejected_on", OVERLAP_DEFECTS, ids=[d[0] for d in OVERLAP_DEFECTS])
+def test_a_dropped_carried_overlap_fails_the_wave_builds_gate(name, forget, passes_today, rejected_on):
+    """The one-channel case of 384 -> 48 kHz (512 -> 64 frames) of tests/test_fft_wave_builds_gpu.py, its smallest pool: 1408
+    values, stream 0 with launches of 9 (runs of 6 and 3) and 4 blocks.  The defect is applied to the f64 overlap-add of stream 0
+    and the result rounded to f32 -- a kernel whose ONLY fault is the defect -- then pooled and gated as the GPU test does.
+    Measured (RMS against the scalar oracle, then against f64 in multiples of the oracle's 1.50e-7 / 4.48e-7):
+        second launch starts from a zero overlap              1.36e-1     x9.1e5   x2.3e6
+        second run starts from a zero overlap                 1.37e-1     x9.2e5   x2.3e6
+        second run forgets the last frame of the overlap      1.60e-7     x0.35    x3.85
+    The last one is ONE output of 1408 that misses a carried value of 1.7e-6: it passes 1e-6 RMS against the oracle and the
+    RMS bound here, and is rejected on the max bound."""
+    import test_fft_wave_builds_gpu as w
+    pair, channels = 2, 1
+    in_hz, out_hz, fi, fo = w.PAIRS[pair]
+    assert (in_hz, out_hz, fo) == (384000, 48000, 64) and w.launches_of(pair, channels) is w.LONG
+    assert w.blocks_of(w.LONG) == [13, 4, 5] and w.LONG[0][1][0] == 9
+    data = w.case_data(pair, channels, 0)
+    ref = np.concatenate([d[2] for d in data])
+    yard = np.concatenate([d[3] for d in data])
+    assert ref.size == 1408
+    assert np.array_equal(fft_f64_forgetting(data[0][1], channels, in_hz, out_hz, 13, {}), data[0][2])
+    y = np.concatenate([fft_f64_forgetting(data[0][1], channels, in_hz, out_hz, 13, forget)] + [d[2] for d in data[1:]]).astype(np.float32)
+    old_rms, _ = R.errors(y, yard)
+    r_rms, r_max = R.budget(y, ref, yard)
+    print(f"{name}: against the oracle {old_rms:.3e}; against f64 x{r_rms:.3g} rms, x{r_max:.3g} max")
+    assert (old_rms <= OLD_RMS_GATE) == passes_today
+    m_rms, m_max = R.MARGINS["fft_wave_builds"]
+    if rejected_on == "rms":
+        assert r_rms > m_rms and r_max > m_max, (r_rms, r_max)
+    else:
+        assert r_rms <= m_rms and r_max > m_max, (r_rms, r_max, m_max)
+    clean = R.budget(ref.astype(np.float32), ref, yard)
     assert clean[0] <= 1.0 and clean[1] <= 1.0

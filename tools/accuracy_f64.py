@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Distances of the FIR and FFT kernels from the f64 reference (oracle/reference_f64.py), in multiples of the scalar
-spec's own distance: runs every case of tests/test_accuracy_f64_gpu.py and of tests/test_fft_pair_builds_gpu.py without
-asserting its ratios and writes the table the margins in oracle/reference_f64.py (MARGINS) are set from.
+spec's own distance: runs every case of tests/test_accuracy_f64_gpu.py, of tests/test_fft_pair_builds_gpu.py and of
+tests/test_fft_wave_builds_gpu.py without asserting its ratios and writes the table the margins in oracle/reference_f64.py (MARGINS) are set from.
 
     python tools/accuracy_f64.py [profiles/accuracy_f64.txt]        (needs an MI355X)
 """
@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import test_accuracy_f64_gpu as t  # noqa: E402
 import test_fft_pair_builds_gpu as tp  # noqa: E402
+import test_fft_wave_builds_gpu as tw  # noqa: E402
 from oracle import reference_f64 as R  # noqa: E402
 
 
@@ -29,14 +30,17 @@ def main() -> int:
     t.measure_all()
     tp.ENFORCE = False
     tp.measure_all()
-    lines = ["# tools/accuracy_f64.py: every case of tests/test_accuracy_f64_gpu.py and tests/test_fft_pair_builds_gpu.py on one MI355X.",
+    tw.ENFORCE = False
+    tw.measure_all()
+    lines = ["# tools/accuracy_f64.py: every case of tests/test_accuracy_f64_gpu.py, tests/test_fft_pair_builds_gpu.py and",
+             "# tests/test_fft_wave_builds_gpu.py on one MI355X.",
              "# ratio = error against the f64 reference / the scalar spec's error against it, over the same outputs;",
              "# 'spec' = the scalar spec's own RMS / max error (absolute).  Margin = 1.25 x the family's worst ratio, rounded up",
              "# to one decimal, capped at %.1f (RMS) / %.1f (max)." % (R.M_RMS_CAP, R.M_MAX_CAP),
              "#",
              "# family    rms ratio  max ratio   spec rms   spec max    values  case"]
     worst = {}
-    for family, label, r_rms, r_max, s_rms, s_max, n in t.OBSERVED + tp.OBSERVED:
+    for family, label, r_rms, r_max, s_rms, s_max, n in t.OBSERVED + tp.OBSERVED + tw.OBSERVED:
         lines.append(f"{family:10s} {r_rms:9.3f}  {r_max:9.3f}  {s_rms:9.2e}  {s_max:9.2e}  {n:8d}  {label}")
         w = worst.setdefault(family, [0.0, 0.0])
         w[0], w[1] = max(w[0], r_rms), max(w[1], r_max)
