@@ -35,8 +35,9 @@ test_every_other_plan_refuses_pcm: each of the 18 ordered rate pairs whose plan 
 (RSMP_ERR_INVALID_ARGUMENT), leaves the guarded output alone and the handle as it was: a following f32 launch equals a fresh
 handle's.  Refused and served rate pairs add up to 90.
 
-Not covered here: the exact library (libresampler_amd_fftexact.so, a second set of 144 builds with whole twiddle rows), the
-RSMP_DEBUG switches (RSMP_FFT_WAVE_NOC2, RSMP_FFT_WAVE_WIDE, ...) and the workgroup kernels (fft_kernels.hip).
+Not covered here: the exact library (libresampler_amd_fftexact.so, a second set of 144 builds with whole twiddle rows) and the
+RSMP_DEBUG switches (RSMP_FFT_WAVE_NOC2, RSMP_FFT_WAVE_WIDE, ...).  The workgroup kernels (fft_kernels.hip), which serve those 18 rate
+pairs and every batch of mixed channel counts, have tests/test_fft_workgroup_builds_gpu.py.
 
 The margins of "fft_wave_builds" (oracle/reference_f64.py, MARGINS) are set like the other families', from
 profiles/accuracy_f64.txt: tools/accuracy_f64.py runs measure_all() of this module too.

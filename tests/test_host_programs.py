@@ -408,3 +408,94 @@ def test_fft_wave_builds_fixture_names_every_build(tmp_path):
             for bits in (16, 24, 32):
                 assert all(ln["family"] == "notsupported" for ln in rows[rp, (2, bits, False)][3]), (rp, bits)
     assert reached == set(range(48)) and len(refused) == 18 and len(rate_pairs) - len(refused) == 72
+
+
+# ---- the builds of the FFT workgroup kernels that tests/test_fft_workgroup_builds_gpu.py launches --------------------------------
+def test_fft_workgroup_builds_fixture_names_every_build(tmp_path):
+    """tests/host/fft_workgroup_builds_dump.cpp (plain C++, g++ with ASan + UBSan, linked with fft_launch.cpp): what fft_choose
+    answers, and fft_choose_run for an occupancy of 1, 2 and 4, on 256 CUs in the ordinary library, to every request of
+    tests/test_fft_workgroup_builds_gpu.py for every ordered pair of the ten sample rates -- a process without a debug switch and
+    one under RSMP_DEBUG=1 RSMP_FFT_WAVE=0, their outputs as the two members of tests/golden/fft_workgroup_builds.json byte for
+    byte, which so cannot go stale.  From the fixture and the GPU module's own list of cases:
+      - every launch of every mixed, uniform, switched and per-call case answers ct, ct2, generic or big;
+      - every first launch is cut into runs of 8 blocks with grid.x = 2, whatever the occupancy: the second run recomputes its
+        predecessor block;
+      - every distinct plan of the 90 rate pairs has a mixed case (its first rate pair), and the module's list is exactly that set;
+      - together the cases name generic at 64, 256, 512 and 1024 threads, ct 0 and 1 and big, and under the switch ct2 0 and 1:
+        every pointer workgroup_kernel() (fft_kernels.hip) can return;
+      - the uniform set is exactly the 18 rate pairs that answer notsupported to two-channel PCM in tests/golden/fft_wave_builds.json
+        (test_every_other_plan_refuses_pcm counts the same ones);
+      - check (b) of the module: a stream of a uniform or switched case gets the same build alone, so its output must be bit-equal;
+        a stream of a mixed case on a plan with a wave build goes to the wave or the pair kernel alone."""
+    import itertools
+    import test_fft_workgroup_builds_gpu as g   # (its lists of cases: nothing of them needs a GPU)
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fft_workgroup_builds_dump.cpp"
+    exe = str(tmp_path / "fft_workgroup_builds_dump")
+    srcs = [os.path.join(ROOT, "tests", "host", "fft_workgroup_builds_dump.cpp")]
+    srcs += [os.path.join(CSRC, f) for f in ("fft_launch.cpp", "fft_plan.cpp", "filter_design.cpp", "common.cpp")]
+    subprocess.run([gxx] + SANITIZE + ["-Wno-unknown-pragmas"] + srcs + ["-o", exe], check=True)
+    plain = {k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}
+    outs = []
+    for setting, env in (("default", plain), ("switched", dict(plain, RSMP_DEBUG="1", RSMP_FFT_WAVE="0"))):
+        run = subprocess.run([exe, setting], env=env, capture_output=True, text=True, timeout=300)
+        _clean(run)
+        outs.append(run.stdout)
+    with open(os.path.join(ROOT, "tests", "golden", "fft_workgroup_builds.json")) as fh:
+        text = fh.read()
+    assert '{"default":\n' + outs[0] + ',"switched":\n' + outs[1] + "}\n" == text, \
+        "tests/golden/fft_workgroup_builds.json is not what tests/host/fft_workgroup_builds_dump.cpp prints"
+    fx = json.loads(text)
+    assert fx["default"]["cus"] == fx["switched"]["cus"] == 256
+    assert len(fx["default"]["rows"]) == 90 * 8 and len(fx["switched"]["rows"]) == 90 * 4
+    g.fixture.cache_clear()
+    rows = g.fixture()
+    rate_pairs = list(itertools.permutations(g.RATES, 2))
+    assert sorted({k[0] for k in rows["default"]}) == sorted(rate_pairs) and len(rate_pairs) == 90
+
+    # ---- the module's lists
+    plans = {}
+    for rp in rate_pairs:
+        plans.setdefault(g.plan_of(*rp), rp)
+    assert [c[1:3] for c in g.MIXED] == list(plans.values()) and len(set(plans.values())) == len(plans) == len(g.MIXED) > 48
+    assert all(c[0] == "mixed" and c[3] == (1, 3, 2) for c in g.MIXED)
+    with open(os.path.join(ROOT, "tests", "golden", "fft_wave_builds.json")) as fh:
+        wave_rows = [r.split(" | ") for r in json.load(fh)["rows"]]
+    refused = {tuple(int(v) for v in r[0].split()[:2]) for r in wave_rows if r[1] == "2 16 refuse" and r[2].split()[2] == "notsupported"}
+    no_wave = [rp for rp in rate_pairs if rows["default"][rp, "uniform 1"][0]["family"] in g.WORKGROUP]
+    assert set(no_wave) == refused and len(no_wave) == 18
+    assert g.UNIFORM == [("uniform", a, b, (c,) * 3) for a, b in no_wave for c in (1, 2, 3)]
+    with_wave = {g.plan_of(*rp) for rp in rate_pairs if rp not in refused}
+    assert len(with_wave) == 48 and len(with_wave | {g.plan_of(*rp) for rp in refused}) == len(plans)
+
+    # ---- every launch of every case
+    names = {"default": set(), "switched": set()}
+    same_build = {"mixed, a wave build": set(), "mixed, no wave build": set(), "uniform": set(), "switched": set()}
+    for setting, cases in (("default", g.MIXED + g.UNIFORM), ("switched", g.SWITCHED)):
+        for case in cases:
+            kind, in_hz, out_hz, chans = case
+            launches = g.case_launches(setting, *case)   # (asserts that the requests are the case's)
+            assert len(launches) == 2 and all(ln["family"] in g.WORKGROUP for ln in launches), (setting, case)
+            assert launches[0]["runs"] == "8/2,8/2,8/2" and launches[1]["runs"] == "8/1,8/1,8/1", (setting, case)
+            for ln in launches:
+                assert int(ln["gridz"]) == (ln["request"][2] if ln["family"] == "big" or ln["block"] == "64" else 1), (setting, case)
+                names[setting].add(g.build_of(ln))
+            group = "switched" if setting == "switched" else kind if kind == "uniform" else \
+                "mixed, a wave build" if g.plan_of(in_hz, out_hz) in with_wave else "mixed, no wave build"
+            for s in range(3):
+                same = g.twin_on_the_same_builds(setting, *case, s)
+                same_build[group].add(same)
+                if group == "mixed, a wave build":   # (alone: the wave kernel, or the pair kernel for two channels)
+                    for blocks in (9, 4, 5):
+                        assert g.twin_launch(setting, in_hz, out_hz, chans[s], blocks)["family"] in ("wave", "pair"), (case, s)
+    assert same_build == {"mixed, a wave build": {False}, "mixed, no wave build": {False, True}, "uniform": {True}, "switched": {True}}
+    assert names["default"] == {("generic", 0, 64), ("generic", 0, 256), ("generic", 0, 512), ("generic", 0, 1024), ("ct", 0, 256), ("ct", 1, 256),
+                                ("big", 0, 1024)}
+    assert names["switched"] == {("ct2", 0, 256), ("ct2", 1, 256), ("ct", 0, 256), ("ct", 1, 256), ("generic", 0, 64)}
+    assert len(g.SWITCHED) == 5 and g.build_of(rows["switched"][(96000, 48000), "uniform 2"][0]) == ("generic", 0, 64)
+    assert rows["switched"][(96000, 48000), "uniform 2"][0]["gridz"] == "2"
+    per_call = [g.build_of(*rows["default"][rp, "percall 1"]) for rp in g.PER_CALL]
+    assert per_call == [("big", 0, 1024), ("generic", 0, 1024)]
+    # (check c: the list next to the margins names builds of these kernels, by family and block)
+    from oracle import reference_f64 as R
+    assert set(R.FFT_WORKGROUP_BIT_EQUAL) <= {(b[0], b[2]) for b in names["default"] | names["switched"]}

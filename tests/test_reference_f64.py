@@ -317,25 +317,28 @@ def test_fft_defects_are_rejected_at_the_margins_in_use(fft_setup, name):
 
 
 # ---- the gate of tests/test_fft_wave_builds_gpu.py can fail ---------------------------------------------------------------
-def fft_f64_forgetting(x, channels, in_hz, out_hz, blocks, forget):
-    """R.fft_f64 with a defect in what it carries: in front of block b the frames forget[b] (a slice) of the overlap are zero."""
+def fft_f64_forgetting(x, channels, in_hz, out_hz, blocks, forget, borrow=None):
+    """R.fft_f64 with a defect in what it carries: in front of block b the frames forget[b] (a slice) of the overlap are zero, and
+    channel borrow[b][0] starts from the overlap of channel borrow[b][1]."""
     fi, fo, _, _ = o.fft_plan(in_hz, out_hz)
     H = R.fft_filter_f64(fi, fo)
     keep = min(fi + 1, fo)
     xs = x[:blocks * fi * channels].reshape(blocks, fi, channels).astype(np.float64)
     out = np.empty((blocks, fo, channels), np.float64)
-    for c in range(channels):
-        overlap = np.zeros(fo, np.float64)
-        for b in range(blocks):
-            if b in forget:
-                overlap[forget[b]] = 0.0
+    overlap = np.zeros((channels, fo), np.float64)
+    for b in range(blocks):
+        if b in forget:
+            overlap[:, forget[b]] = 0.0
+        if borrow and b in borrow:
+            overlap[borrow[b][0]] = overlap[borrow[b][1]]
+        for c in range(channels):
             buf = np.zeros(2 * fi, np.float64)
             buf[:fi] = xs[b, :, c]
             spec = np.zeros(fo + 1, np.complex128)
             spec[:keep] = np.fft.rfft(buf)[:keep] * H[:keep]
             y = np.fft.irfft(spec, 2 * fo) * float(2 * fo)
-            out[b, :, c] = y[:fo] + overlap
-            overlap = y[fo:]
+            out[b, :, c] = y[:fo] + overlap[c]
+            overlap[c] = y[fo:]
     return out.reshape(-1)
 
 
@@ -378,5 +381,51 @@ def test_a_dropped_carried_overlap_fails_the_wave_builds_gate(name, forget, pass
         assert r_rms > m_rms and r_max > m_max, (r_rms, r_max)
     else:
         assert r_rms <= m_rms and r_max > m_max, (r_rms, r_max, m_max)
+    clean = R.budget(ref.astype(np.float32), ref, yard)
+    assert clean[0] <= 1.0 and clean[1] <= 1.0
+
+
+# ---- the gate of tests/test_fft_workgroup_builds_gpu.py can fail -----------------------------------------------------------------
+# name, stream, forget, borrow
+MIXED_BATCH_DEFECTS = [
+    ("the 3-channel stream's channel 1 starts its last block from channel 0's overlap", 1, {}, {3: (1, 0)}),
+    ("the 1-channel stream's carried overlap is dropped between the two launches", 0, {9: slice(None)}, None),
+]
+
+
+@pytest.mark.parametrize("name,stream,forget,borrow", MIXED_BATCH_DEFECTS, ids=[d[0] for d in MIXED_BATCH_DEFECTS])
+def test_a_mixed_batch_defect_fails_the_workgroup_builds_gate(name, stream, forget, borrow):
+    """The smallest mixed case of tests/test_fft_workgroup_builds_gpu.py (512 -> 64 frames; streams of 1, 3 and 2 channels with 13,
+    4 and 5 blocks: 2240 values), the two defects its launch path invites, each applied to the f64 overlap-add of one stream and
+    rounded to f32 -- a kernel whose ONLY fault is the defect -- then pooled and put through check (a) as the GPU test does.
+      - overlap rows read at another stride than the stream's own hand a channel another channel's overlap: here channel 1 of the
+        3-channel stream takes channel 0's in front of its last block, 64 outputs of the 2240 (that stream has four blocks and no
+        run boundary of its own; the last block is where the fewest outputs are wrong);
+      - the state of the 1-channel stream is lost between the launches: its block 9 starts from a zero overlap.
+    Measured (RMS against the scalar oracle, then against f64 in multiples of the oracle's own distance):
+        channel 1 starts from channel 0's overlap        2.04e-1     x1.5e6   x3.7e6
+        overlap dropped between the launches             1.08e-1     x7.8e5   x1.9e6
+    Both fail the RMS and the max bound by six orders of magnitude; the clean f64 result passes."""
+    import test_fft_workgroup_builds_gpu as g
+    case = min(g.MIXED, key=lambda c: g.plan_of(c[1], c[2])[:2][::-1])
+    kind, in_hz, out_hz, chans = case
+    assert g.plan_of(in_hz, out_hz)[:2] == (512, 64) and chans == (1, 3, 2)
+    blocks = g.blocks_of(g.LONG)
+    assert blocks == [13, 4, 5] and g.LONG[0][1][0] == 9
+    data = g.case_data(in_hz, out_hz, chans, blocks)
+    ref = np.concatenate([d[1] for d in data])
+    yard = np.concatenate([d[2] for d in data])
+    assert ref.size == 64 * (13 + 3 * 4 + 2 * 5)
+    for d, c, n in zip(data, chans, blocks):
+        assert np.array_equal(fft_f64_forgetting(d[0], c, in_hz, out_hz, n, {}), d[1])
+    parts = [d[1] for d in data]
+    parts[stream] = fft_f64_forgetting(data[stream][0], chans[stream], in_hz, out_hz, blocks[stream], forget, borrow)
+    assert int(np.count_nonzero(parts[stream] != data[stream][1])) <= 64 * (4 if stream == 0 else 1)
+    y = np.concatenate(parts).astype(np.float32)
+    old_rms, _ = R.errors(y, yard)
+    r_rms, r_max = R.budget(y, ref, yard)
+    print(f"{name}: against the oracle {old_rms:.3e}; against f64 x{r_rms:.3g} rms, x{r_max:.3g} max")
+    m_rms, m_max = R.MARGINS["fft_workgroup"]
+    assert r_rms > m_rms and r_max > m_max, (r_rms, r_max)
     clean = R.budget(ref.astype(np.float32), ref, yard)
     assert clean[0] <= 1.0 and clean[1] <= 1.0
