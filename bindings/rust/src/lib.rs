@@ -114,6 +114,13 @@ extern "C" {
                              out_pcm: *mut std::os::raw::c_void, stats: *mut PcmStats) -> c_int;
     fn rsmp_f32_to_pcm_stats_device(d_in: *const f32, n_values: usize, bits: c_int, dither: c_int, seed: u64, first_index: u64,
                                     d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats, stream: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_fir_set_pcm_gain(r: *mut rsmp_fir, gain: f32) -> c_int;
+    fn rsmp_fir_pcm_gain(r: *const rsmp_fir, gain: *mut f32) -> c_int;
+    fn rsmp_f32_to_pcm_gain(input: *const f32, n_values: usize, bits: c_int, gain: f32, dither: c_int, seed: u64, first_index: u64,
+                            out_pcm: *mut std::os::raw::c_void, stats: *mut PcmStats) -> c_int;
+    fn rsmp_f32_to_pcm_gain_device(d_in: *const f32, n_values: usize, bits: c_int, gain: f32, dither: c_int, seed: u64, first_index: u64,
+                                   d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats, stream: *mut std::os::raw::c_void) -> c_int;
+    fn rsmp_pcm_normalise_gain(stats: *const PcmStats, target_peak: f32, gain: *mut f32) -> c_int;
     fn rsmp_fir_set_pcm_stats(r: *mut rsmp_fir, enable: c_int) -> c_int;
     fn rsmp_fir_pcm_stats(r: *mut rsmp_fir, stats: *mut PcmStats) -> c_int;
     fn rsmp_fir_pcm_stats_clear(r: *mut rsmp_fir) -> c_int;
@@ -126,6 +133,8 @@ extern "C" {
                                                    stream: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_fft_set_pcm_dither(r: *mut rsmp_fft, dither: c_int, seed: u64) -> c_int;
     fn rsmp_fft_pcm_dither(r: *const rsmp_fft, dither: *mut c_int, seed: *mut u64) -> c_int;
+    fn rsmp_fft_set_pcm_gain(r: *mut rsmp_fft, gain: f32) -> c_int;
+    fn rsmp_fft_pcm_gain(r: *const rsmp_fft, gain: *mut f32) -> c_int;
     fn rsmp_fft_set_pcm_stats(r: *mut rsmp_fft, enable: c_int) -> c_int;
     fn rsmp_fft_pcm_stats(r: *mut rsmp_fft, stats: *mut PcmStats) -> c_int;
     fn rsmp_fft_pcm_stats_clear(r: *mut rsmp_fft) -> c_int;
@@ -254,6 +263,18 @@ impl ResamplerFir {
     pub fn set_pcm_dither(&mut self, dither: Dither, seed: u64) -> Result<(), ResampleError> {
         status(unsafe { rsmp_fir_set_pcm_dither(self.handle, dither as c_int, seed) })
     }
+    /// Output gain of the PCM the fused entry writes for this stream (rsmp_fir_set_pcm_gain), folded into the store's own factor: the
+    /// bytes are `f32_to_pcm_gain_device`'s of the f32 output.  A setting, default 1 (`reset` leaves it), per stream; finite,
+    /// 2^-32 <= |gain| <= 2^32, negative for a polarity flip -- anything else is an error and changes nothing.
+    pub fn set_pcm_gain(&mut self, gain: f32) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fir_set_pcm_gain(self.handle, gain) })
+    }
+    /// The gain as `set_pcm_gain` left it.
+    pub fn pcm_gain(&self) -> f32 {
+        let mut g = 1.0f32;
+        unsafe { rsmp_fir_pcm_gain(self.handle, &mut g) };
+        g
+    }
     /// (dither mode as RSMP_DITHER_*, seed) as `set_pcm_dither` left them.
     pub fn pcm_dither(&self) -> (i32, u64) {
         let (mut d, mut s): (c_int, u64) = (0, 0);
@@ -328,6 +349,28 @@ pub fn f32_to_pcm_dither(input: &[f32], bits: u32, dither: Dither, seed: u64, fi
 pub unsafe fn f32_to_pcm_dither_device(d_in: *const f32, n_values: usize, bits: u32, dither: Dither, seed: u64, first_index: u64,
                                        d_pcm: *mut std::os::raw::c_void) -> Result<(), ResampleError> {
     status(rsmp_f32_to_pcm_dither_device(d_in, n_values, bits as c_int, dither as c_int, seed, first_index, d_pcm, std::ptr::null_mut()))
+}
+
+/// `f32_to_pcm_stats` under an output gain (rsmp_f32_to_pcm_gain, include/resampler_amd.h): x * (gain * 2^(bits-1)) in one rounding,
+/// then the noise, the rounding and the saturation as ever; the statistics describe the gained values.  What the fused PCM stores do
+/// for a handle with `set_pcm_gain(gain)`.
+pub fn f32_to_pcm_gain(input: &[f32], bits: u32, gain: f32, dither: Dither, seed: u64, first_index: u64) -> Result<(Vec<u8>, PcmStats), ResampleError> {
+    let mut out = vec![0u8; input.len() * (bits as usize / 8)];
+    let mut st = PcmStats::default();
+    status(unsafe {
+        rsmp_f32_to_pcm_gain(input.as_ptr(), input.len(), bits as c_int, gain, dither as c_int, seed, first_index, out.as_mut_ptr() as *mut std::os::raw::c_void, &mut st)
+    })
+    .map(|_| (out, st))
+}
+/// The same on device pointers (rsmp_f32_to_pcm_gain_device; `d_stats` may be null), on the null stream.
+pub unsafe fn f32_to_pcm_gain_device(d_in: *const f32, n_values: usize, bits: u32, gain: f32, dither: Dither, seed: u64, first_index: u64,
+                                     d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats) -> Result<(), ResampleError> {
+    status(rsmp_f32_to_pcm_gain_device(d_in, n_values, bits as c_int, gain, dither as c_int, seed, first_index, d_pcm, d_stats, std::ptr::null_mut()))
+}
+/// The gain that brings a first pass's peak to `target_peak` in a second pass (rsmp_pcm_normalise_gain): target_peak / stats.peak.
+pub fn normalise_gain(stats: &PcmStats, target_peak: f32) -> Result<f32, ResampleError> {
+    let mut g = 0.0f32;
+    status(unsafe { rsmp_pcm_normalise_gain(stats, target_peak, &mut g) }).map(|_| g)
 }
 
 /// `f32_to_pcm_dither` that also says what it did (the definition of the statistics, on the host): the bytes -- those of
@@ -406,6 +449,18 @@ impl ResamplerFft {
     /// takes the noise of index n * channels + c.  ResamplerFft has no reset: the sequence never starts again.
     pub fn set_pcm_dither(&mut self, dither: Dither, seed: u64) -> Result<(), ResampleError> {
         status(unsafe { rsmp_fft_set_pcm_dither(self.handle, dither as c_int, seed) })
+    }
+    /// Output gain of the PCM the fused entry writes for this stream (rsmp_fft_set_pcm_gain), folded into the store's own factor: the
+    /// bytes are `f32_to_pcm_gain_device`'s of the f32 output.  A setting, default 1 , per stream; finite,
+    /// 2^-32 <= |gain| <= 2^32, negative for a polarity flip -- anything else is an error and changes nothing.
+    pub fn set_pcm_gain(&mut self, gain: f32) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fft_set_pcm_gain(self.handle, gain) })
+    }
+    /// The gain as `set_pcm_gain` left it.
+    pub fn pcm_gain(&self) -> f32 {
+        let mut g = 1.0f32;
+        unsafe { rsmp_fft_pcm_gain(self.handle, &mut g) };
+        g
     }
     /// (dither mode as RSMP_DITHER_*, seed) as `set_pcm_dither` left them.
     pub fn pcm_dither(&self) -> (i32, u64) {

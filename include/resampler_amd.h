@@ -107,7 +107,9 @@ typedef struct rsmp_pcm_stats {
     uint64_t values;     /* values quantised */
     uint64_t clipped;    /* ... of which lay outside the code range and were saturated */
     uint64_t nans;       /* ... of which were NaN and were stored as 0 (not counted as clipped) */
-    float peak;          /* largest |x| of the values that were not NaN, before scaling and dither; +inf possible; 0 if none */
+    float peak;          /* largest |x| of the values that were not NaN, before scaling and dither; +inf possible; 0 if none.
+                          * Under an output gain: of the gained values (rsmp_f32_to_pcm_gain).  What a second pass needs to choose its
+                          * gain: rsmp_pcm_normalise_gain */
     uint32_t reserved;   /* 0 */
 } rsmp_pcm_stats;
 
@@ -240,6 +242,18 @@ int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, c
  * changed --; the seeds are per stream.  rsmp_fir_pcm_dither reads the setting back (either pointer may be NULL). */
 int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed);
 int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* seed);
+/* Output gain of the PCM that entry writes for this handle, folded into the factor its stores multiply by anyway -- the rule is
+ * rsmp_f32_to_pcm_gain's (below), and the bytes are exactly rsmp_f32_to_pcm_gain_device's of the f32 entry's output with the
+ * handle's gain, dither, seed and first_index = abs_out * channels.  A setting, not state: the default is 1 (the bytes of a handle
+ * that never set it), it survives rsmp_fir_reset and rsmp_fir_seek, and a change takes effect at the handle's next PCM-output
+ * launch.  Only the PCM-output entry reads it: the f32 entries, the lock-step batch and the buffered history ignore it.  It is
+ * per stream: the streams of a batch may differ in it, unlike out_bits, the dither mode and the statistics setting.  Accepted:
+ * finite gains with 2^-32 <= |gain| <= 2^32, negative ones included (polarity); zero, NaN, infinities and anything outside the
+ * range are RSMP_ERR_INVALID_ARGUMENT and change nothing.  With statistics on, the totals describe the gained values
+ * (rsmp_f32_to_pcm_gain): a second pass at gain g reports about g times the first pass's peak.  rsmp_fir_pcm_gain reads the
+ * setting back (null handle or null `gain`: RSMP_ERR_INVALID_ARGUMENT). */
+int rsmp_fir_set_pcm_gain(rsmp_fir* r, float gain);
+int rsmp_fir_pcm_gain(const rsmp_fir* r, float* gain);
 /* Statistics of the PCM that entry writes for this handle: a setting, default 0 (off), that survives rsmp_fir_reset and
  * rsmp_fir_seek like the dither setting.  With it on, a PCM-output launch takes builds of its kernels that count every value they
  * store by rsmp_f32_to_pcm_stats's rule (below) -- the bytes are unchanged -- and adds the launch's counts to the handle's totals
@@ -504,6 +518,34 @@ int rsmp_f32_to_pcm_stats(const float* in, size_t n_values, int bits, int dither
                           void* out_pcm, rsmp_pcm_stats* stats);
 int rsmp_f32_to_pcm_stats_device(const float* d_in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
                                  void* d_pcm, rsmp_pcm_stats* d_stats, void* stream);
+/* The same under an output gain: what the fused PCM stores of both engines do (rsmp_fir_set_pcm_gain, rsmp_fft_set_pcm_gain),
+ * as a pass of its own.  For a value x with absolute index i, width `bits`, noise d (0 without dither):
+ *   k = f32(gain) * 2^(bits-1)              (exact: a power-of-two multiple of an f32; a normal f32 for every accepted gain)
+ *   p = f32(x * k)                          (one rounding)
+ *   q = saturate(round_half_to_even(f32(p + d(seed, i)))),  p NaN -> 0
+ * -- the product and the sum are two operations (no fma: for a gain that is no power of two it would round once and give other
+ * bytes); i, d, saturation and the 32-bit top code as above.  With gain == 1, k is 2^(bits-1) and the bytes are
+ * rsmp_f32_to_pcm_dither's for every input.
+ * Accepted gains: finite, 2^-32 <= |gain| <= 2^32, negative ones included (polarity).  Zero, NaN, infinities and anything outside
+ * the range: RSMP_ERR_INVALID_ARGUMENT, nothing written.
+ * Consequence: for a power-of-two gain the bytes equal rsmp_f32_to_pcm[_dither]'s of x * gain; for any gain they equal its bytes
+ * of f32(x * gain) wherever |x * gain| >= 2^-126 (both products then round at the same bit); below that both give code 0 without
+ * dither.
+ * The statistics describe what was quantised: nans counts p NaN; clipped goes by v = round_half_to_even(f32(p + d)), as above;
+ * peak is the largest |p| * 2^-(bits-1), computed in f32 -- the peak of the gained signal, so a second pass at gain g reports
+ * about g times the first pass's peak.  With gain 1 it is rsmp_f32_to_pcm_stats's |x|, except that an x whose product
+ * x * 2^(bits-1) overflows f32 (|x| >= 2^(129-bits)) counts as +inf here.
+ * Host version (needs no device: the definition): `stats` may be NULL, else *stats is OVERWRITTEN.  Device version: alignment and
+ * ordering as rsmp_f32_to_pcm_stats_device, the statistics MERGED into *d_stats, which may be NULL too.  out_pcm / d_pcm may be
+ * NULL where statistics are taken: measure only. */
+int rsmp_f32_to_pcm_gain(const float* in, size_t n_values, int bits, float gain, int dither, uint64_t seed, uint64_t first_index,
+                         void* out_pcm, rsmp_pcm_stats* stats);
+int rsmp_f32_to_pcm_gain_device(const float* d_in, size_t n_values, int bits, float gain, int dither, uint64_t seed,
+                                uint64_t first_index, void* d_pcm, rsmp_pcm_stats* d_stats, void* stream);
+/* The gain that brings a first pass's peak to target_peak in a second pass: *gain = f32(target_peak / stats->peak).
+ * RSMP_ERR_INVALID_ARGUMENT, *gain untouched, when the peak is 0 or not finite, when the result is no accepted gain, or for a null
+ * pointer.  The second pass's peak is target_peak to within two f32 roundings (the quotient and the product). */
+int rsmp_pcm_normalise_gain(const rsmp_pcm_stats* stats, float target_peak, float* gain);
 /* Measurement aid (no counterpart in the reference): a plain streaming copy of n_values floats, 16 bytes per lane --
  * the rate a kernel that reads as much as it writes can reach on this GPU; bench.py reports it next to every
  * roofline fraction.  16-byte aligned device pointers, n_values a multiple of 4, asynchronous on `stream`. */
@@ -576,6 +618,12 @@ int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, size_t n, c
  * pointer may be NULL). */
 int rsmp_fft_set_pcm_dither(rsmp_fft* r, int dither, uint64_t seed);
 int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* seed);
+/* Output gain of the PCM that entry writes for this handle: rsmp_fir_set_pcm_gain's twin, the rule rsmp_f32_to_pcm_gain's.  The
+ * bytes are exactly rsmp_f32_to_pcm_gain_device's of the f32 entry's output with the handle's gain, dither, seed and
+ * first_index = abs_out * 2; with statistics on, the totals describe the gained values.  A setting with default 1, per stream
+ * (a batch may mix gains), read at every PCM-output launch and by nothing else; the accepted gains and the refusals are the same. */
+int rsmp_fft_set_pcm_gain(rsmp_fft* r, float gain);
+int rsmp_fft_pcm_gain(const rsmp_fft* r, float* gain);
 /* Statistics of the PCM that rsmp_fft_batch_resample_bulk_pcm_out_device writes for this handle: the twins of
  * rsmp_fir_set_pcm_stats / rsmp_fir_pcm_stats / rsmp_fir_pcm_stats_clear.
  * The setting belongs to the handle, is off by default and stays until it is changed (ResamplerFft has no reset).  Turning it on

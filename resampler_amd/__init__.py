@@ -146,6 +146,8 @@ _SIGNATURES = [
     ("rsmp_fir_set_profiling", C.c_int, [C.c_void_p, C.c_int]),
     ("rsmp_fir_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("rsmp_fir_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("rsmp_fir_set_pcm_gain", C.c_int, [C.c_void_p, C.c_float]),
+    ("rsmp_fir_pcm_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rsmp_fir_set_pcm_stats", C.c_int, [C.c_void_p, C.c_int]),
     ("rsmp_fir_pcm_stats", C.c_int, [C.c_void_p, C.POINTER(PcmStats)]),
     ("rsmp_fir_pcm_stats_clear", C.c_int, [C.c_void_p]),
@@ -219,6 +221,9 @@ _SIGNATURES = [
     ("rsmp_f32_to_pcm_dither_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rsmp_f32_to_pcm_stats", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(PcmStats)]),
     ("rsmp_f32_to_pcm_stats_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rsmp_f32_to_pcm_gain", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(PcmStats)]),
+    ("rsmp_f32_to_pcm_gain_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rsmp_pcm_normalise_gain", C.c_int, [C.POINTER(PcmStats), C.c_float, C.POINTER(C.c_float)]),
     ("rsmp_device_stream_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rsmp_fft_new", C.c_void_p, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     ("rsmp_fft_free", None, [C.c_void_p]),
@@ -247,6 +252,8 @@ _SIGNATURES = [
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, _szp, C.c_void_p]),
     ("rsmp_fft_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("rsmp_fft_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("rsmp_fft_set_pcm_gain", C.c_int, [C.c_void_p, C.c_float]),
+    ("rsmp_fft_pcm_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rsmp_fft_set_pcm_stats", C.c_int, [C.c_void_p, C.c_int]),
     ("rsmp_fft_pcm_stats", C.c_int, [C.c_void_p, C.POINTER(PcmStats)]),
     ("rsmp_fft_pcm_stats_clear", C.c_int, [C.c_void_p]),
@@ -438,6 +445,19 @@ class ResamplerFir:
         d, sd = C.c_int(), C.c_uint64()
         _check(lib().rsmp_fir_pcm_dither(self._h, C.byref(d), C.byref(sd)))
         return d.value, sd.value
+
+    def set_pcm_gain(self, gain: float) -> None:
+        """Output gain of the PCM that FirBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fir_set_pcm_gain), folded
+        into the store's own factor: f32_to_pcm_device(..., gain=gain) of the f32 output gives the same bytes.  A setting, default 1:
+        reset() and seek() leave it, the f32 entries ignore it, the streams of a batch may differ in it.  Finite, 2^-32 <= |gain| <=
+        2^32, negative for a polarity flip; anything else raises and changes nothing."""
+        _check(lib().rsmp_fir_set_pcm_gain(self._h, float(gain)))
+
+    def pcm_gain(self) -> float:
+        """The gain as set_pcm_gain left it (an f32)."""
+        g = C.c_float()
+        _check(lib().rsmp_fir_pcm_gain(self._h, C.byref(g)))
+        return g.value
 
     def set_pcm_stats(self, enable: bool) -> None:
         """Statistics of the PCM that FirBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fir_set_pcm_stats): off by
@@ -894,6 +914,17 @@ class ResamplerFft:
         _check(lib().rsmp_fft_pcm_dither(self._h, C.byref(d), C.byref(s)))
         return d.value, s.value
 
+    def set_pcm_gain(self, gain: float) -> None:
+        """Output gain of the PCM that FftBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fft_set_pcm_gain):
+        ResamplerFir.set_pcm_gain's twin -- a setting, default 1, per stream, read by the PCM-output entry alone."""
+        _check(lib().rsmp_fft_set_pcm_gain(self._h, float(gain)))
+
+    def pcm_gain(self) -> float:
+        """The gain as set_pcm_gain left it (an f32)."""
+        g = C.c_float()
+        _check(lib().rsmp_fft_pcm_gain(self._h, C.byref(g)))
+        return g.value
+
     def set_pcm_stats(self, enable: bool) -> None:
         """Statistics of the PCM that FftBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fft_set_pcm_stats): off by
         default, a setting of the handle.  With it on a launch counts every value it stores -- the bytes do not change -- and
@@ -1004,13 +1035,18 @@ def pcm_to_stereo_f32_device(d_pcm, bits: int, channels: int, d_out, stream: Opt
                                                C.c_void_p(d_out.data_ptr()), C.c_void_p(stream or 0)))
 
 
-def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0) -> bytes:
+def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, gain: float = 1.0) -> bytes:
     """f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host, no device needed (rsmp_f32_to_pcm[_dither]): the
     library's quantiser -- round half to even of x * 2^(bits-1), saturated, NaN -> 0.  dither = Dither.TPDF: value j takes, before
-    the rounding, the triangular noise of (seed, first_index + j) -- the rule is stated at rsmp_f32_to_pcm_dither."""
+    the rounding, the triangular noise of (seed, first_index + j) -- the rule is stated at rsmp_f32_to_pcm_dither.  gain other than
+    1: the quantiser under an output gain (rsmp_f32_to_pcm_gain: x * (gain * 2^(bits-1)) in one rounding), what the fused PCM stores
+    do for a handle with set_pcm_gain(gain)."""
     a = _np_f32(x).reshape(-1)
     out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8)
-    if dither == 0:
+    if gain != 1.0:
+        _check(lib().rsmp_f32_to_pcm_gain(C.c_void_p(a.ctypes.data), a.size, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                          C.c_void_p(out.ctypes.data), None))
+    elif dither == 0:
         _check(lib().rsmp_f32_to_pcm(C.c_void_p(a.ctypes.data), a.size, bits, C.c_void_p(out.ctypes.data)))
     else:
         _check(lib().rsmp_f32_to_pcm_dither(C.c_void_p(a.ctypes.data), a.size, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
@@ -1018,43 +1054,64 @@ def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 
     return out.tobytes()
 
 
-def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None, dither: int = 0, seed: int = 0, first_index: int = 0) -> None:
+def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None, dither: int = 0, seed: int = 0, first_index: int = 0,
+                      gain: float = 1.0) -> None:
     """The same on HBM-resident torch tensors (rsmp_f32_to_pcm[_dither]_device): d_in = float32, d_pcm = uint8 with room for
-    d_in.numel() * bits / 8 bytes, 4-byte aligned; exactly those bytes are written."""
+    d_in.numel() * bits / 8 bytes, 4-byte aligned; exactly those bytes are written.  gain other than 1: rsmp_f32_to_pcm_gain_device."""
     n = d_in.numel()
     if bits in (16, 24, 32):
         assert d_pcm.numel() >= n * (bits // 8)
-    if dither == 0:
+    if gain != 1.0:
+        _check(lib().rsmp_f32_to_pcm_gain_device(C.c_void_p(_dev_ptr(d_in)), n, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                                 C.c_void_p(d_pcm.data_ptr()), None, C.c_void_p(stream or 0)))
+    elif dither == 0:
         _check(lib().rsmp_f32_to_pcm_device(C.c_void_p(_dev_ptr(d_in)), n, bits, C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
     else:
         _check(lib().rsmp_f32_to_pcm_dither_device(C.c_void_p(_dev_ptr(d_in)), n, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
                                                    C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
 
 
-def f32_to_pcm_stats(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, want_pcm: bool = True):
+def f32_to_pcm_stats(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, want_pcm: bool = True, gain: float = 1.0):
     """f32_to_pcm that also says what it did (rsmp_f32_to_pcm_stats, host, no device needed: the definition of the statistics):
     returns (bytes, PcmStats) -- the bytes are f32_to_pcm's with the same arguments; (None, PcmStats) with want_pcm = False
-    (out_pcm = NULL: measure only)."""
+    (out_pcm = NULL: measure only).  gain other than 1: rsmp_f32_to_pcm_gain, whose statistics describe the gained values."""
     a = _np_f32(x).reshape(-1)
     out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8) if want_pcm else None
     st = PcmStats()
+    if gain != 1.0:
+        _check(lib().rsmp_f32_to_pcm_gain(C.c_void_p(a.ctypes.data), a.size, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                          C.c_void_p(out.ctypes.data) if want_pcm else None, C.byref(st)))
+        return (out.tobytes() if want_pcm else None), st
     _check(lib().rsmp_f32_to_pcm_stats(C.c_void_p(a.ctypes.data), a.size, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
                                        C.c_void_p(out.ctypes.data) if want_pcm else None, C.byref(st)))
     return (out.tobytes() if want_pcm else None), st
 
 
 def f32_to_pcm_stats_device(d_in, bits: int, d_pcm, d_stats, stream: Optional[int] = None, dither: int = 0, seed: int = 0,
-                            first_index: int = 0) -> None:
+                            first_index: int = 0, gain: float = 1.0) -> None:
     """The same on HBM-resident torch tensors (rsmp_f32_to_pcm_stats_device): d_pcm as f32_to_pcm_device's, or None to measure only;
     d_stats = a tensor of 32 bytes, 8-byte aligned, that the caller zeroed -- the call's statistics are MERGED into it, so a buffer
-    converted in pieces accumulates one result (PcmStats.from_tensor reads it)."""
+    converted in pieces accumulates one result (PcmStats.from_tensor reads it).  gain other than 1: rsmp_f32_to_pcm_gain_device."""
     n = d_in.numel()
     if d_pcm is not None and bits in (16, 24, 32):
         assert d_pcm.numel() >= n * (bits // 8)
     assert d_stats.numel() * d_stats.element_size() >= C.sizeof(PcmStats)
+    if gain != 1.0:
+        _check(lib().rsmp_f32_to_pcm_gain_device(C.c_void_p(_dev_ptr(d_in)), n, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
+                                                 C.c_void_p(d_pcm.data_ptr()) if d_pcm is not None else None, C.c_void_p(d_stats.data_ptr()),
+                                                 C.c_void_p(stream or 0)))
+        return
     _check(lib().rsmp_f32_to_pcm_stats_device(C.c_void_p(_dev_ptr(d_in)), n, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
                                               C.c_void_p(d_pcm.data_ptr()) if d_pcm is not None else None, C.c_void_p(d_stats.data_ptr()),
                                               C.c_void_p(stream or 0)))
+
+
+def normalise_gain(stats: "PcmStats", target_peak: float) -> float:
+    """The gain that brings a first pass's peak to target_peak in a second pass (rsmp_pcm_normalise_gain): f32(target_peak /
+    stats.peak).  Raises where the peak is 0 or not finite, or the quotient is no gain set_pcm_gain accepts."""
+    g = C.c_float()
+    _check(lib().rsmp_pcm_normalise_gain(C.byref(stats), float(target_peak), C.byref(g)))
+    return g.value
 
 
 def fft_plan_sizes(input_rate_hz: int, output_rate_hz: int):

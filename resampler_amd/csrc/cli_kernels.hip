@@ -6,7 +6,8 @@
 //     (`s as f32 / (1 << (bits - 1)) as f32`) with mono duplicated to stereo, so a decoded file goes from
 //     its PCM bytes in HBM to the interleaved f32 frames the resamplers take in one pass;
 //   * the way back, f32 -> 16 / 24 / 32-bit little-endian PCM (fir_pcm_quantise, fir_kernels.h: round half to even, saturate,
-//     NaN -> 0), without or with TPDF dither (fir_pcm_quantise_dither), on the host and as a streaming pass on the device.
+//     NaN -> 0), without or with TPDF dither (fir_pcm_quantise_dither), on the host and as a streaming pass on the device,
+//     and the same under an output gain (fir_pcm_quantise_gain: the two-pass reference of the fused stores' gain).
 // Both are HBM-bound elementwise kernels: coalesced loads / stores, nothing to stage.
 #include <hip/hip_runtime.h>
 
@@ -401,6 +402,142 @@ extern "C" int rsmp_f32_to_pcm_stats_device(const float* d_in, size_t n_values, 
     }
 #undef RSMP_STATS_LAUNCH
     RSMP_HIP_CHECK(hipGetLastError());
+    return RSMP_OK;
+}
+
+// ---- the quantiser under a gain (fir_pcm_quantise_gain, fir_kernels.h): what the fused PCM stores do, as a pass of its own -----
+// The two-pass reference of the fused paths' output gain.  The entries above keep their kernels and their arithmetic; these are
+// builds of their own, by width and dither mode, that take the factor k = gain * 2^(bits-1) as an argument and count when asked.
+namespace {
+
+// f32_to_pcm_stats_kernel's lanes, loads and stores; `out` and `stats` may each be null.
+template <int BITS, bool TPDF>
+__global__ __launch_bounds__(kThreads) void f32_to_pcm_gain_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, uint64_t n, float k, uint64_t seed,
+                                                                   uint64_t first, rsmp_pcm_stats* __restrict__ stats) {
+    typedef float v4f_in __attribute__((ext_vector_type(4)));
+    const uint64_t n4 = n / 4, stride = static_cast<uint64_t>(gridDim.x) * kThreads;
+    rsmp::FirPcmStat mine{0, 0, 0, 0};
+    auto code = [&](float x, uint64_t i) {
+        const float d = TPDF ? rsmp::fir_pcm_dither(seed, first + i) : 0.0f;
+        return static_cast<uint32_t>(rsmp::fir_pcm_quantise_gain_stat(x, k, BITS, d, mine));
+    };
+    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(kThreads) + threadIdx.x; i <= n4; i += stride) {
+        if (i == n4) {   // the 0 .. 3 values behind the last whole four
+            for (uint64_t j = 4 * n4; j < n; ++j) {
+                const int32_t q = static_cast<int32_t>(code(in[j], j));
+                if (out) rsmp::fir_pcm_store_code(out, BITS, j, q);
+            }
+            break;
+        }
+        const v4f_in x = reinterpret_cast<const v4f_in*>(in)[i];
+        const uint32_t q0 = code(x.x, 4 * i), q1 = code(x.y, 4 * i + 1), q2 = code(x.z, 4 * i + 2), q3 = code(x.w, 4 * i + 3);
+        if (!out) continue;
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + i * (BITS / 2));
+        if constexpr (BITS == 16) {
+            o[0] = (q0 & 0xFFFFu) | (q1 << 16);
+            o[1] = (q2 & 0xFFFFu) | (q3 << 16);
+        } else if constexpr (BITS == 24) {
+            o[0] = (q0 & 0xFFFFFFu) | (q1 << 24);
+            o[1] = ((q1 >> 8) & 0xFFFFu) | (q2 << 16);
+            o[2] = ((q2 >> 16) & 0xFFu) | (q3 << 8);
+        } else {
+            o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
+        }
+    }
+    if (!stats) return;   // (uniform: a kernel argument)
+    __shared__ rsmp::FirPcmStat waves[kThreads / 64];
+    const rsmp::FirPcmStat w = rsmp::fir_stat_wave_sum(mine);
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long values = 0, clipped = 0, nans = 0;
+        uint32_t peak = 0;
+        for (int j = 0; j < kThreads / 64; ++j) {
+            values += waves[j].values;
+            clipped += waves[j].clipped;
+            nans += waves[j].nans;
+            peak = waves[j].peak > peak ? waves[j].peak : peak;
+        }
+        if (values) (void)atomicAdd(reinterpret_cast<unsigned long long*>(&stats->values), values);
+        if (clipped) (void)atomicAdd(reinterpret_cast<unsigned long long*>(&stats->clipped), clipped);
+        if (nans) (void)atomicAdd(reinterpret_cast<unsigned long long*>(&stats->nans), nans);
+        if (peak) (void)atomicMax(reinterpret_cast<uint32_t*>(&stats->peak), peak);
+    }
+}
+
+bool pcm_gain_args_ok(int bits, float gain, int dither) {
+    return (bits == 16 || bits == 24 || bits == 32) && rsmp::fir_pcm_gain_ok(gain) && (dither == RSMP_DITHER_NONE || dither == RSMP_DITHER_TPDF);
+}
+
+}  // namespace
+
+// The definition under a gain, on the host (no device needed): bytes and, where asked for, what was done.
+extern "C" int rsmp_f32_to_pcm_gain(const float* in, size_t n_values, int bits, float gain, int dither, uint64_t seed, uint64_t first_index, void* out_pcm,
+                                    rsmp_pcm_stats* stats) {
+    if (!pcm_gain_args_ok(bits, gain, dither) || (n_values != 0 && (!in || (!out_pcm && !stats))))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_gain: 16 / 24 / 32 bits, a finite gain with 2^-32 <= |gain| <= 2^32, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, non-null input, and output or statistics");
+    uint8_t* o = static_cast<uint8_t*>(out_pcm);
+    const size_t bytes = static_cast<size_t>(bits) / 8;
+    const float k = rsmp::fir_pcm_gain_scale(gain, static_cast<uint32_t>(bits));
+    rsmp::FirPcmStat acc{0, 0, 0, 0};
+    rsmp_pcm_stats t{};
+    for (size_t i = 0; i < n_values; ++i) {
+        rsmp::FirPcmStat one{0, 0, 0, acc.peak};
+        const uint32_t q = static_cast<uint32_t>(dither == RSMP_DITHER_TPDF
+                                                     ? rsmp::fir_pcm_quantise_gain_stat(in[i], k, static_cast<uint32_t>(bits), rsmp::fir_pcm_dither(seed, first_index + i), one)
+                                                     : rsmp::fir_pcm_quantise_gain_stat(in[i], k, static_cast<uint32_t>(bits), 0.0f, one));
+        t.values += one.values;
+        t.clipped += one.clipped;
+        t.nans += one.nans;
+        acc.peak = one.peak;
+        if (o)   // (null: measure only)
+            for (size_t b = 0; b < bytes; ++b) o[i * bytes + b] = static_cast<uint8_t>(q >> (8 * b));   // little-endian
+    }
+    if (stats) {
+        std::memcpy(&t.peak, &acc.peak, sizeof acc.peak);
+        *stats = t;
+    }
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_f32_to_pcm_gain_device(const float* d_in, size_t n_values, int bits, float gain, int dither, uint64_t seed, uint64_t first_index,
+                                           void* d_pcm, rsmp_pcm_stats* d_stats, void* stream) {
+    if (!pcm_gain_args_ok(bits, gain, dither) || (n_values != 0 && (!d_in || (!d_pcm && !d_stats))))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_gain_device: 16 / 24 / 32 bits, a finite gain with 2^-32 <= |gain| <= 2^32, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, non-null buffers");
+    if (reinterpret_cast<uintptr_t>(d_in) % 16 != 0 || reinterpret_cast<uintptr_t>(d_pcm) % 4 != 0 || reinterpret_cast<uintptr_t>(d_stats) % 8 != 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_gain_device: d_in 16-byte aligned, d_pcm 4-byte aligned, d_stats 8-byte aligned");
+    if (int rc = check_device()) return rc;
+    if (n_values == 0) return RSMP_OK;
+    const dim3 grid = f32_to_pcm_grid(n_values);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* o = static_cast<uint8_t*>(d_pcm);
+    const uint64_t n = n_values;
+    const float k = rsmp::fir_pcm_gain_scale(gain, static_cast<uint32_t>(bits));
+#define RSMP_GAIN_LAUNCH(BITS, TPDF) hipLaunchKernelGGL((f32_to_pcm_gain_kernel<BITS, TPDF>), grid, dim3(kThreads), 0, s, d_in, o, n, k, seed, first_index, d_stats)
+    if (dither == RSMP_DITHER_TPDF) {
+        if (bits == 16) RSMP_GAIN_LAUNCH(16, true);
+        else if (bits == 24) RSMP_GAIN_LAUNCH(24, true);
+        else RSMP_GAIN_LAUNCH(32, true);
+    } else {
+        if (bits == 16) RSMP_GAIN_LAUNCH(16, false);
+        else if (bits == 24) RSMP_GAIN_LAUNCH(24, false);
+        else RSMP_GAIN_LAUNCH(32, false);
+    }
+#undef RSMP_GAIN_LAUNCH
+    RSMP_HIP_CHECK(hipGetLastError());
+    return RSMP_OK;
+}
+
+// The gain a second pass needs to bring the first pass's peak to target_peak: f32(target_peak / peak).
+extern "C" int rsmp_pcm_normalise_gain(const rsmp_pcm_stats* stats, float target_peak, float* gain) {
+    if (!stats || !gain) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_pcm_normalise_gain: null argument");
+    const float peak = stats->peak;
+    if (!(peak > 0.0f) || std::isinf(peak))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_pcm_normalise_gain: the peak is zero or not finite: nothing to normalise by");
+    const float g = target_peak / peak;
+    if (!rsmp::fir_pcm_gain_ok(g))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_pcm_normalise_gain: target_peak / peak is no gain the PCM entries accept (finite, 2^-32 <= |gain| <= 2^32)");
+    *gain = g;
     return RSMP_OK;
 }
 

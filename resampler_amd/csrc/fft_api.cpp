@@ -20,6 +20,7 @@
 #include "device_util.h"
 #include "fft_kernels.h"
 #include "fft_plan.h"
+#include "fir_kernels.h"   // fir_pcm_gain_ok, fir_pcm_gain_scale: the PCM output rule is the FIR path's
 
 using rsmp::DeviceBuffer;
 using rsmp::DeviceGuard;
@@ -160,6 +161,8 @@ struct rsmp_fft {
     uint64_t abs_out = 0;
     int pcm_dither = RSMP_DITHER_NONE;
     uint64_t pcm_dither_seed = 0;
+    // The output gain of the PCM-output entries (rsmp_fft_set_pcm_gain): a setting like the dither, per stream; the f32 entries ignore it
+    float pcm_gain = 1.0f;
     // Statistics of the PCM the pair kernel stores for this handle (rsmp_fft_set_pcm_stats): a setting like the dither.  The totals
     // are one rsmp_pcm_stats in device memory, allocated and zeroed when the setting is first turned on; the counting builds
     // (fft_pair_pcm_stats.hip) merge into it.  A clear sets pcm_stats_cleared and nothing else: the handle's next counting launch
@@ -287,7 +290,8 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
     }
     FftPcmOutDesc* h_pcm = out_bits != 0 ? reinterpret_cast<FftPcmOutDesc*>(h + n) : nullptr;
     for (size_t i = 0; h_pcm && i < n; ++i)
-        h_pcm[i] = FftPcmOutDesc{jobs[i].r->pcm_dither_seed, jobs[i].r->abs_out, static_cast<uint32_t>(jobs[i].r->pcm_dither), 0};
+        h_pcm[i] = FftPcmOutDesc{jobs[i].r->pcm_dither_seed, jobs[i].r->abs_out, static_cast<uint32_t>(jobs[i].r->pcm_dither),
+                                 rsmp::fir_pcm_gain_scale(jobs[i].r->pcm_gain, out_bits)};
     rsmp_pcm_stats** h_acc = stats ? reinterpret_cast<rsmp_pcm_stats**>(reinterpret_cast<char*>(h) + acc_off) : nullptr;
     for (size_t i = 0; h_acc && i < n; ++i) h_acc[i] = jobs[i].r->d_pcm_stats;
     const FftStreamDesc* d_descs = h;   // (mapped host memory: the same address on the device)
@@ -581,6 +585,21 @@ extern "C" int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* see
     if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_dither: null handle");
     if (dither) *dither = r->pcm_dither;
     if (seed) *seed = r->pcm_dither_seed;
+    return RSMP_OK;
+}
+
+// PCM output's gain: a setting like the dither, per stream -- the streams of a batch may differ in it.  Read where a PCM-output launch
+// writes its FftPcmOutDesc table, at every launch: a change holds from the next one.
+extern "C" int rsmp_fft_set_pcm_gain(rsmp_fft* r, float gain) {
+    if (!r || !rsmp::fir_pcm_gain_ok(gain))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_set_pcm_gain: null handle, or gain not finite with 2^-32 <= |gain| <= 2^32");
+    r->pcm_gain = gain;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fft_pcm_gain(const rsmp_fft* r, float* gain) {
+    if (!r || !gain) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_gain: null argument");
+    *gain = r->pcm_gain;
     return RSMP_OK;
 }
 

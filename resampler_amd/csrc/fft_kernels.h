@@ -49,8 +49,9 @@ struct FftPcmOutDesc {
     uint64_t seed;        // the stream's own
     uint64_t abs_out;     // output frames the handle had produced before this launch
     uint32_t dither;      // RSMP_DITHER_NONE / RSMP_DITHER_TPDF: one mode for all the streams of a launch
-    uint32_t reserved;
+    float pcm_k;          // the factor every store multiplies by: f32(gain) * 2^(out_bits-1), the stream's own gain (fir_pcm_gain_scale)
 };
+static_assert(sizeof(FftPcmOutDesc) == 24, "pcm_k took the reserved word: the size stays");
 
 // pcm_bits != 0: every stream's `in` is PCM of that width (FftStreamDesc::in_bits); hipErrorNotSupported where no kernel
 // that reads PCM serves the plan / channel count.  Which kernel, grid, block and LDS a launch gets: fft_launch.h.

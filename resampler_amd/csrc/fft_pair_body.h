@@ -297,7 +297,8 @@ __device__ __forceinline__ int32_t pair_pcm_code(float v, int32_t bottom, int32_
 // upper two; odd g: L's low two, then L's top byte and R).  A lane writes its frame's own bytes and no others; non-temporal like
 // the f32 frames.  Width and mode are the same for every lane of the wave; the product by the power of two and the sum with the
 // noise are separate operations, as in the converters.
-// RSMP_PAIR_PCM_OUT 2: `st` also takes what was done to the two values, by fir_pcm_stat's rule, from the x, the scaled value and the
+// The factor is the stream's own, FftPcmOutDesc::pcm_k = gain * 2^(bits-1) (rsmp_fft_set_pcm_gain; fir_pcm_quantise_gain's rule).
+// RSMP_PAIR_PCM_OUT 2: `st` also takes what was done to the two values, by fir_pcm_quantise_gain_stat's rule, from the scaled value p and the
 // rounded value that the store uses (its `values` is not used: the wave knows how many frames it emitted).
 #if RSMP_PAIR_PCM_OUT == 2
 __device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const FftPcmOutDesc& po, size_t frame0, uint32_t n, cf v, FirPcmStat& st) {
@@ -311,9 +312,10 @@ __device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const Fft
     typedef uint32_t u2o __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(1))) u2o GU2o;
     const uint32_t bits = d.out_bits;
-    const float scale = fir_pcm_scale(bits);
+    const float scale = po.pcm_k;   // the stream's factor, gain * 2^(bits-1) (fir_pcm_quantise_gain's k)
     const int32_t top = bits == 16 ? 32767 : bits == 24 ? 8388607 : INT32_MAX, bottom = -top - 1;
-    float sl = v.x * scale, sr = v.y * scale;
+    const float pl = v.x * scale, pr = v.y * scale;   // p of the gain rule: one rounding each
+    float sl = pl, sr = pr;
     if (po.dither == RSMP_DITHER_TPDF) {
         const uint64_t w = fir_dither_word(po.seed, po.abs_out + frame0 + n);
         sl += fir_dither_value(static_cast<uint32_t>(w));
@@ -321,8 +323,8 @@ __device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const Fft
     }
 #if RSMP_PAIR_PCM_OUT == 2
     const float vl = rintf(sl), vr = rintf(sr);
-    fir_pcm_stat(v.x, vl, bits, st);
-    fir_pcm_stat(v.y, vr, bits, st);
+    fir_pcm_stat(pl * fir_pcm_unscale(bits), vl, bits, st);
+    fir_pcm_stat(pr * fir_pcm_unscale(bits), vr, bits, st);
     const uint32_t l = static_cast<uint32_t>(pair_pcm_code(vl, bottom, top)), r = static_cast<uint32_t>(pair_pcm_code(vr, bottom, top));
 #else
     const uint32_t l = static_cast<uint32_t>(pair_pcm_code(rintf(sl), bottom, top)), r = static_cast<uint32_t>(pair_pcm_code(rintf(sr), bottom, top));

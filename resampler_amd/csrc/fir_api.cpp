@@ -450,6 +450,21 @@ extern "C" int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed) {
     return RSMP_OK;
 }
 
+// PCM output's gain: a setting like the dither (reset and seek leave it alone), per stream -- the streams of a batch may differ.
+// fill_descriptors reads it at every PCM-output launch.
+extern "C" int rsmp_fir_set_pcm_gain(rsmp_fir* r, float gain) {
+    if (!r || !rsmp::fir_pcm_gain_ok(gain))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_set_pcm_gain: null handle, or gain not finite with 2^-32 <= |gain| <= 2^32");
+    r->pcm_gain = gain;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fir_pcm_gain(const rsmp_fir* r, float* gain) {
+    if (!r || !gain) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_gain: null argument");
+    *gain = r->pcm_gain;
+    return RSMP_OK;
+}
+
 extern "C" int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* seed) {
     if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_dither: null handle");
     if (dither) *dither = r->pcm_dither;
@@ -698,7 +713,7 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
 }
 
 // The same with the output as a WAV file stores it: d_out_pcm[i] receives little-endian PCM of `out_bits` (16 / 24 / 32; 24-bit
-// packed), every sum quantised where the kernels store it (fir_pcm_quantise, fir_kernels.h) -- the split kernel's pending, full and
+// packed), every sum quantised where the kernels store it (fir_pcm_quantise_gain with the stream's own gain -- rsmp_fir_set_pcm_gain, 1 by default --, fir_kernels.h) -- the split kernel's pending, full and
 // per-frame stores, the generic kernels, the repair pass.  Input: interleaved f32 (in_bits = 0) or PCM as above.  Counts, end states
 // and buffered frames (f32) are those of rsmp_fir_batch_resample_bulk_device; the bytes are rsmp_f32_to_pcm_device's of that
 // entry's output, without the f32 ever reaching HBM (f32 written, f32 read, PCM written: two passes less).

@@ -64,6 +64,8 @@ struct rsmp_fir {
     // A setting, not state: reset and seek leave it alone; the noise counter is the mirror's abs_out.
     int pcm_dither = RSMP_DITHER_NONE;
     uint64_t pcm_dither_seed = 0;
+    // ... and the stream's output gain (rsmp_fir_set_pcm_gain): only the PCM-output entry reads it
+    float pcm_gain = 1.0f;
     // ... and its statistics (rsmp_fir_set_pcm_stats): the setting -- reset and seek leave it -- and the handle's totals, one
     // rsmp_pcm_stats in device memory that the fold kernel behind every counting launch merges into.  pcm_stats_cleared: the totals
     // are zero whatever the memory holds (a new handle, reset, rsmp_fir_pcm_stats_clear): the next counting launch replaces them.

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/resampler_amd.h"
@@ -56,8 +57,13 @@ struct FirStreamDesc {
     // dithered builds by it --, and the stream's own seed.  Value (frame n of the launch, channel c) takes the noise of index
     // (abs_out + n) * channels + c (fir_pcm_dither below).  No build without PCM output reads either field, no undithered one the seed.
     uint32_t dither;
+    // PCM output only: the factor every store multiplies by, k = f32(gain) * 2^(out_bits-1) with the stream's own gain (fir_pcm_gain_scale
+    // below; gain 1: fir_pcm_scale(out_bits)).  The host writes it for every PCM-output launch; no build without PCM output reads it.
+    float pcm_k;
     uint64_t dither_seed;
 };
+static_assert(offsetof(FirStreamDesc, pcm_k) == 188 && offsetof(FirStreamDesc, dither_seed) == 192 && sizeof(FirStreamDesc) == 200,
+              "pcm_k fills the hole in front of dither_seed: the descriptor keeps its size and every other field its place");
 
 // One sample of a stream's `in`, index `i` in values (frame * channels + channel).
 // main.rs:131: `sample as f32 / (1 << (bits - 1)) as f32`; the literal is an i32, so 32-bit files divide by -2^31.
@@ -116,6 +122,25 @@ __host__ __device__ __forceinline__ float fir_pcm_dither(uint64_t seed, uint64_t
 __host__ __device__ __forceinline__ int32_t fir_pcm_quantise_dither(float x, uint32_t bits, float d) {
     return fir_pcm_code(rintf(x * fir_pcm_scale(bits) + d), bits);
 }
+// Output gain (rsmp_fir_set_pcm_gain, rsmp_fft_set_pcm_gain, rsmp_f32_to_pcm_gain): THE definition of PCM output under a gain, every
+// store site of the fused paths calls it.  Value `i` of a stream is quantised as
+//   k = f32(gain) * 2^(bits-1)              (exact: a power-of-two multiple of an f32; a normal f32 for every accepted gain)
+//   p = f32(x * k)                          (one rounding)
+//   q = saturate(round_half_to_even(f32(p + d(seed, i)))),  p NaN -> 0
+// with d = 0 without dither (p + 0 rounds as p does: the undithered form has no addition); i, saturation and the 32-bit top code
+// as above.  The product and the sum are separate operations: an fma would round x * k + d once and give other bytes for a gain
+// that is no power of two (the library is compiled with -ffp-contract=off).  With gain == 1, k is fir_pcm_scale(bits) and the
+// bytes are fir_pcm_quantise[_dither]'s for every input.  Accepted gains: finite, 2^-32 <= |gain| <= 2^32 (negative: polarity).
+// Consequence: for a power-of-two gain the bytes are the plain quantiser's of x * gain; for any gain they are its bytes of
+// f32(x * gain) wherever |x * gain| >= 2^-126 (x * gain and x * k then round at the same bit), and below that both give code 0
+// without dither.
+__host__ __device__ __forceinline__ bool fir_pcm_gain_ok(float gain) {
+    const float a = gain < 0.0f ? -gain : gain;
+    return a >= 0x1p-32f && a <= 0x1p32f;   // (NaN fails both comparisons, 0 the first, inf the second)
+}
+__host__ __device__ __forceinline__ float fir_pcm_gain_scale(float gain, uint32_t bits) { return gain * fir_pcm_scale(bits); }
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise_gain(float x, float k, uint32_t bits) { return fir_pcm_code(rintf(x * k), bits); }
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise_gain(float x, float k, uint32_t bits, float d) { return fir_pcm_code(rintf(x * k + d), bits); }
 // What the quantiser did to the values it was given (rsmp_pcm_stats, include/resampler_amd.h): THE definition, every site that
 // counts calls fir_pcm_stat.  x: the value before scaling; v: the quantiser's own rounded value, rintf(x * 2^(bits-1) + d).
 //   values  every value;   nans  x is NaN (stored as 0, not clipped);
@@ -153,6 +178,17 @@ __host__ __device__ __forceinline__ void fir_pcm_stat_merge(FirPcmStat& s, const
 __host__ __device__ __forceinline__ int32_t fir_pcm_quantise_stat(float x, uint32_t bits, float d, FirPcmStat& s) {
     const float v = rintf(x * fir_pcm_scale(bits) + d);
     fir_pcm_stat(x, v, bits, s);
+    return fir_pcm_code(v, bits);
+}
+// The statistics under a gain describe what was quantised, p = f32(x * k): nans: p is NaN; clipped: by v, as above; peak: the
+// largest |p| * 2^-(bits-1), in f32 -- the peak of the gained signal (exact: a power of two; with gain 1 it is |x|, except where
+// x * 2^(bits-1) overflows f32 -- |x| >= 2^(129-bits) --, which gives +inf).  THE definition for the fused paths' counting builds and
+// for rsmp_f32_to_pcm_gain.
+__host__ __device__ __forceinline__ float fir_pcm_unscale(uint32_t bits) { return bits == 16 ? 0x1p-15f : bits == 24 ? 0x1p-23f : 0x1p-31f; }
+__host__ __device__ __forceinline__ int32_t fir_pcm_quantise_gain_stat(float x, float k, uint32_t bits, float d, FirPcmStat& s) {
+    const float p = x * k;
+    const float v = rintf(p + d);
+    fir_pcm_stat(p * fir_pcm_unscale(bits), v, bits, s);
     return fir_pcm_code(v, bits);
 }
 // Where a counting launch keeps its statistics: four words {values, clipped, nans, peak bits} per stream and 1024-output-frame
@@ -206,18 +242,20 @@ __device__ __forceinline__ void fir_pcm_store_code(void* out, uint32_t bits, siz
     }
 }
 __device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y) { fir_pcm_store_code(out, bits, i, fir_pcm_quantise(y, bits)); }
+// ... and by the factor `k` of a stream's descriptor (fir_pcm_quantise_gain)
+__device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y, float k) { fir_pcm_store_code(out, bits, i, fir_pcm_quantise_gain(y, k, bits)); }
 // A counting build's store of value `i` (as fir_out_store below): the bytes of the plain / dithered builds, and `s` says what was done.
 __device__ __forceinline__ void fir_out_store_stat(const FirStreamDesc& d, size_t i, float y, FirPcmStat& s) {
     const float noise = d.dither == RSMP_DITHER_TPDF ? fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i) : 0.0f;
-    fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_stat(y, d.out_bits, noise, s));
+    fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_gain_stat(y, d.pcm_k, d.out_bits, noise, s));
 }
 // Value `i` of a stream's output in this launch.  OUT: the PCM-output builds of the generic kernels and of the repair pass (out_bits
 // != 0), with and without dither; the f32 builds do not read the fields.
 template <int OUT>
 __device__ __forceinline__ void fir_out_store(const FirStreamDesc& d, size_t i, float y) {
     if constexpr (OUT == kFirOutPcmTpdf)
-        fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_dither(y, d.out_bits, fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i)));
-    else if constexpr (OUT == kFirOutPcm) fir_pcm_store(d.out, d.out_bits, i, y);
+        fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_gain(y, d.pcm_k, d.out_bits, fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i)));
+    else if constexpr (OUT == kFirOutPcm) fir_pcm_store(d.out, d.out_bits, i, y, d.pcm_k);
     else d.out[i] = y;
 }
 

@@ -257,6 +257,8 @@ int fill_descriptors(Launch& L) {
         ds.out_bits = L.format.out_bits;
         ds.dither = L.format.dither;
         ds.dither_seed = L.format.out_bits != 0 ? r->pcm_dither_seed : 0;
+        // (written for every PCM-output launch, whatever was cached: the descriptors are this launch's own, and publish() compares the image)
+        ds.pcm_k = L.format.out_bits != 0 ? fir_pcm_gain_scale(r->pcm_gain, L.format.out_bits) : 0.0f;
         if (ds.tail_frames * ch > L.max_tail_values) L.max_tail_values = ds.tail_frames * ch;
         if (!pl.periodic) {
             ds.segs = reinterpret_cast<const rsmp_fir_segment*>(L.d + pp.seg_off);

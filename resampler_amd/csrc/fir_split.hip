@@ -481,8 +481,9 @@ __device__ __forceinline__ uint32_t consumer_index(uint32_t w) { return w < 6 ? 
 // ROUNDS: lane tasks per stager lane and item -- 2 for periods of 161 .. 320 frames (96 -> 44.1 kHz, 96 -> 48 kHz): both
 // rounds' loads are in flight together, one item ahead, like the single round's.
 // OUT: the streams' `out` is PCM (FirStreamDesc::out_bits: 16 / 24 / 32, one width per launch, read from the descriptor by
-// these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise) -- OUT is a FirOut; the
-// kFirOutPcmTpdf builds add TPDF dither there (fir_pcm_quantise_dither; the stream's seed from the descriptor, one 64-bit mix per frame).
+// these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise_gain, by the stream's own
+// factor FirStreamDesc::pcm_k = gain * 2^(out_bits-1): a pending store carries its stream's) -- OUT is a FirOut; the
+// kFirOutPcmTpdf builds add TPDF dither there (the stream's seed from the descriptor, one 64-bit mix per frame).
 // The kFirOutPcmStats builds also count every value they store into its chunk's entry of g.stat (fir_pcm_stat), where the wave
 // decides what it stores -- a deferred store is counted once, there --; they serve both dither modes (a wave-uniform branch).
 template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0, int OUT = kFirOutF32>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
@@ -1359,6 +1360,26 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     constexpr bool kKeyed = OUT == kFirOutPcmTpdf || OUT == kFirOutPcmStats;
     typedef typename std::conditional<kKeyed, uint64_t, NoKey>::type dkey_t;
     dkey_t pend_k{};
+    // PCM output: a stream's store factor (FirStreamDesc::pcm_k = gain * 2^(out_bits-1); the streams of a launch may differ in gain,
+    // so a pending store carries its own); nothing in the f32 builds, as the key above.  Fetched through the scalar cache when
+    // the wave's items change stream (StreamCtx stays what the f32 builds know: their code does not change by a byte).
+    struct NoScale {
+        __device__ operator float() const { return 0.0f; }
+    };
+    typedef typename std::conditional<OUT != kFirOutF32, float, NoScale>::type pks_t;
+    pks_t pend_ks{};
+    pks_t cur_ks{};
+    uint32_t ks_stream = 0xFFFFFFFFu;
+    auto stream_ks = [&](const StreamCtx& c) -> pks_t {   // (wave-uniform)
+        if constexpr (OUT != kFirOutF32) {
+            if (c.sidx != ks_stream) {
+                typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
+                ks_stream = c.sidx;
+                cur_ks = __uint_as_float(__builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[c.sidx].pcm_k)));
+            }
+            return cur_ks;
+        } else return NoScale{};
+    };
     typedef v2f __attribute__((address_space(1)))* g_f2_ptr;
     // PCM output: the launch's width (wave-uniform, in a scalar register) and the bytes of a two-channel frame
     uint32_t out_bits = 0, out_fb = 0;
@@ -1391,20 +1412,20 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         else return d.dither_seed + (d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n)) + 1u) * kFirDitherStep;
     };
     // a frame's two dithered codes (the undithered builds quantise below, in the statements they always had: their code is unchanged)
-    auto dither_frame = [&](float y0, float y1, dkey_t k, uint32_t& q0, uint32_t& q1) {
+    auto dither_frame = [&](float y0, float y1, dkey_t k, pks_t ks, uint32_t& q0, uint32_t& q1) {
         if constexpr (OUT == kFirOutPcmTpdf) {
             const uint64_t w = fir_dither_mix(k);
-            q0 = static_cast<uint32_t>(fir_pcm_quantise_dither(y0, out_bits, fir_dither_value(static_cast<uint32_t>(w))));
-            q1 = static_cast<uint32_t>(fir_pcm_quantise_dither(y1, out_bits, fir_dither_value(static_cast<uint32_t>(w >> 32))));
+            q0 = static_cast<uint32_t>(fir_pcm_quantise_gain(y0, ks, out_bits, fir_dither_value(static_cast<uint32_t>(w))));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise_gain(y1, ks, out_bits, fir_dither_value(static_cast<uint32_t>(w >> 32))));
         } else if constexpr (OUT == kFirOutPcmStats) {
-            float d0 = 0.0f, d1 = 0.0f;   // (no dither: x * scale + 0 rounds to fir_pcm_quantise's code)
+            float d0 = 0.0f, d1 = 0.0f;   // (no dither: x * k + 0 rounds to the undithered form's code)
             if (dith) {
                 const uint64_t w = fir_dither_mix(k);
                 d0 = fir_dither_value(static_cast<uint32_t>(w));
                 d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
             }
-            q0 = static_cast<uint32_t>(fir_pcm_quantise_dither(y0, out_bits, d0));
-            q1 = static_cast<uint32_t>(fir_pcm_quantise_dither(y1, out_bits, d1));
+            q0 = static_cast<uint32_t>(fir_pcm_quantise_gain(y0, ks, out_bits, d0));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise_gain(y1, ks, out_bits, d1));
         }
     };
     // Counting builds: the frames n0 + r this lane is about to store (or to defer) -- all four where `full`, else those inside the
@@ -1412,7 +1433,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     // sixteen periods of four classes each: its frames lie in a few chunks (one to three at 44.1 -> 48 kHz), a lane's four frames in
     // one or, across a chunk boundary, two.  Per chunk present in the wave: a sum over the wave of the frames that lie in it, and one
     // lane's atomics.
-    auto count_frames = [&](const StreamCtx& d, int32_t n0, int32_t n_limit, uint32_t j0, bool full, const v4f& lo, const v4f& hi) {
+    auto count_frames = [&](const StreamCtx& d, int32_t n0, int32_t n_limit, uint32_t j0, bool full, const v4f& lo, const v4f& hi, pks_t ks) {
         if constexpr (OUT == kFirOutPcmStats) {
             const float y[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
             FirPcmStat fr[4];
@@ -1428,8 +1449,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                         d0 = fir_dither_value(static_cast<uint32_t>(w));
                         d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
                     }
-                    (void)fir_pcm_quantise_stat(y[2 * r], out_bits, d0, fr[r]);
-                    (void)fir_pcm_quantise_stat(y[2 * r + 1], out_bits, d1, fr[r]);
+                    (void)fir_pcm_quantise_gain_stat(y[2 * r], ks, out_bits, d0, fr[r]);
+                    (void)fir_pcm_quantise_gain_stat(y[2 * r + 1], ks, out_bits, d1, fr[r]);
                     c_last = n >> kNfChunkShift;
                     if (c_next < 0) c_next = c_last;
                 }
@@ -1451,13 +1472,13 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
             }
         }
     };
-    auto store_frame_pcm = [&](g_f32_ptr o, float y0, float y1, dkey_t k) {
+    auto store_frame_pcm = [&](g_f32_ptr o, float y0, float y1, dkey_t k, pks_t ks) {
         uint32_t q0, q1;
         if constexpr (kKeyed) {
-            dither_frame(y0, y1, k, q0, q1);
+            dither_frame(y0, y1, k, ks, q0, q1);
         } else {
-            q0 = static_cast<uint32_t>(fir_pcm_quantise(y0, out_bits));
-            q1 = static_cast<uint32_t>(fir_pcm_quantise(y1, out_bits));
+            q0 = static_cast<uint32_t>(fir_pcm_quantise_gain(y0, ks, out_bits));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise_gain(y1, ks, out_bits));
         }
         if (out_bits == 16) {
             *(g_u32_ptr)o = (q0 & 0xFFFFu) | (q1 << 16);
@@ -1472,15 +1493,15 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     };
     // PCM output, a lane's four frames x two channels at `o`: 16 bytes (4-byte aligned), 24 bytes (2-byte aligned) or 32 bytes
     // (4-byte aligned).  No store is wider than the alignment of its address, every byte is written once, none beside the 4 frames.
-    auto store_frames_pcm = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, dkey_t k) {
+    auto store_frames_pcm = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, dkey_t k, pks_t ks) {
         const float y[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
         uint32_t q[8];
         if constexpr (kKeyed) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dither_frame(y[2 * i], y[2 * i + 1], k + static_cast<uint64_t>(i) * kFirDitherStep, q[2 * i], q[2 * i + 1]);
+            for (int i = 0; i < 4; ++i) dither_frame(y[2 * i], y[2 * i + 1], k + static_cast<uint64_t>(i) * kFirDitherStep, ks, q[2 * i], q[2 * i + 1]);
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) q[i] = static_cast<uint32_t>(fir_pcm_quantise(y[i], out_bits));
+            for (int i = 0; i < 8; ++i) q[i] = static_cast<uint32_t>(fir_pcm_quantise_gain(y[i], ks, out_bits));
         }
         if (out_bits == 16) {
             typedef v4u __attribute__((address_space(1), aligned(4)))* g_u4a4_ptr;
@@ -1516,17 +1537,17 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         }
     };
     // a lane's four frames x two channels: 32 contiguous bytes, or (WIDE) 8 bytes in each of four frames
-    auto store_frames = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, bool ph, dkey_t k) {   // (k: dithered builds, the first frame's key)
+    auto store_frames = [&](g_f32_ptr o, const v4f& lo, const v4f& hi, bool ph, dkey_t k, pks_t ks) {   // (k: dithered builds, the first frame's key; ks: PCM output, the stream's factor)
         if constexpr (OUT && WIDE) {
             // a frame of the pair is the unit: 4 bytes (4-byte aligned: the channel count is even), 6 bytes (2-byte aligned) or
             // 8 bytes (4-byte aligned), one frame stride apart; from one frame to the next the key moves on by the frame's pairs
             const uint64_t kstep = static_cast<uint64_t>(g.pairs) * kFirDitherStep;
-            store_frame_pcm(o, lo.x, lo.y, k);
-            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + out_stride), lo.z, lo.w, k + kstep);
-            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + 2 * out_stride), hi.x, hi.y, k + 2 * kstep);
-            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + 3 * out_stride), hi.z, hi.w, k + 3 * kstep);
+            store_frame_pcm(o, lo.x, lo.y, k, ks);
+            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + out_stride), lo.z, lo.w, k + kstep, ks);
+            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + 2 * out_stride), hi.x, hi.y, k + 2 * kstep, ks);
+            store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + 3 * out_stride), hi.z, hi.w, k + 3 * kstep, ks);
         } else if constexpr (OUT) {
-            store_frames_pcm(o, lo, hi, k);
+            store_frames_pcm(o, lo, hi, k, ks);
         } else if constexpr (WIDE) {
             if (kOdd && ph) {   // the last channel alone: one value per frame
                 o[0] = lo.x;
@@ -1555,7 +1576,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     };
     auto flush_pending = [&]() {
         if (pend) {   // wave-uniform
-            store_frames(pend_o, pend_lo, pend_hi, pend_ph, pend_k);
+            store_frames(pend_o, pend_lo, pend_hi, pend_ph, pend_k, pend_ks);
             pend = false;
         }
     };
@@ -1704,7 +1725,8 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         const v4f hi = v4f{acc0.z, acc1.z, acc0.w, acc1.w};
         if (!(dbg & 16)) {
             const bool full = j0 + 4 <= g.b && n0 >= 0 && n0 + 4 <= n_limit;
-            count_frames(d, n0, n_limit, j0, full, lo, hi);
+            const pks_t ks_d = stream_ks(d);   // (here: the whole wave is active)
+            count_frames(d, n0, n_limit, j0, full, lo, hi, ks_d);
             bool combined = false;
             if constexpr (WIDE && !OUT) {   // (PCM output: pairs are not merged, and nothing is pending here -- flushed above, before every item's stores)
                 // the odd pair of a block whose even pair is pending: four channels of a frame side by side, 16-byte stores
@@ -1729,17 +1751,18 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                 pend_o = o;
                 pend_ph = phantom(cu.cur_pair);
                 pend_k = dither_key(d, n0);
+                pend_ks = ks_d;
                 pend = true;
             } else if (full) {
-                store_frames(o, lo, hi, phantom(cu.cur_pair), dither_key(d, n0));
+                store_frames(o, lo, hi, phantom(cu.cur_pair), dither_key(d, n0), ks_d);
             } else {
                 const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int32_t n = n0 + r;
                     if (j0 + r < g.b && n >= 0 && n < n_limit) {
-                        if constexpr (OUT && WIDE) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_stride), v[2 * r], v[2 * r + 1], dither_key(d, n));
-                        else if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1], dither_key(d, n));
+                        if constexpr (OUT && WIDE) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_stride), v[2 * r], v[2 * r + 1], dither_key(d, n), ks_d);
+                        else if constexpr (OUT) store_frame_pcm((g_f32_ptr)((g_u8_ptr)o + r * out_fb), v[2 * r], v[2 * r + 1], dither_key(d, n), ks_d);
                         else if (mono) o[r] = v[2 * r];
                         else if (phantom(cu.cur_pair)) o[fs * r] = v[2 * r];
                         else if constexpr (kOdd) *((g_f2u_ptr)(o + fs * r)) = v2f{v[2 * r], v[2 * r + 1]};

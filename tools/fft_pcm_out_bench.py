@@ -11,6 +11,9 @@ and `f32` = the f32-output launch alone.  A step is bracketed by events on the s
 back and counts as their mean; the rows are measured one after the other, --reps repetitions each, and the whole table --rounds times
 in the one process: a row is the median over all its repetitions, with every round's median beside it.  Prints one JSON object.
 
+--gain G (default 1: the setting is left alone, so that a library from before it can be measured): every handle's output gain
+(ResamplerFft.set_pcm_gain); the conversion passes of the two_pass rows take the same gain.
+
 --stats adds rows (the default output is unchanged): what the statistics of the store cost (rsmp_fft_set_pcm_stats).  Per width, input
 and dither, four routes alternating in the one process:
   fused_off   rsmp_fft_batch_resample_bulk_pcm_out_device with the setting off (the `fused` row's launch, on handles of their own)
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--burst", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--gain", type=float, default=1.0)
     ap.add_argument("--stats", action="store_true", help="add the rows of the store's statistics: setting off / on, two-pass counted, parent")
     ap.add_argument("--parent-lib", default=None, help="--stats: a libresampler_amd.so of the parent commit, for the `parent` rows")
     a = ap.parse_args()
@@ -54,6 +58,10 @@ def main():
     S, blocks = a.streams, a.blocks
     hs = [ra.ResamplerFft.new(2, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000) for _ in range(S)]
     n_in, n_out = hs[0].chunk_size_input(), hs[0].chunk_size_output()
+    gain_kw = {"gain": a.gain} if a.gain != 1.0 else {}
+    for h in hs:
+        if gain_kw:
+            h.set_pcm_gain(a.gain)
     base = torch.from_numpy(synth.sweep(blocks * n_in // 2, 2, 44100.0)).to(dev)
     gains = torch.linspace(0.5, 1.0, S, device=dev)
     d_f32 = [(base * gains[i]).contiguous() for i in range(S)]
@@ -88,10 +96,10 @@ def main():
                 def two_pass(in_bits=in_bits, bits=bits, dither=dither, pcm_all=pcm_all, d_pcm_out=d_pcm_out):
                     launch_f32(in_bits)
                     if not dither:
-                        ra.f32_to_pcm_device(out_all, bits, pcm_all, stream)
+                        ra.f32_to_pcm_device(out_all, bits, pcm_all, stream, **gain_kw)
                     else:   # (first_index 0: the noise of a fresh stream; which index it starts at costs nothing)
                         for i in range(S):
-                            ra.f32_to_pcm_device(d_out[i], bits, d_pcm_out[i], stream, dither=dither, seed=a.seed + i, first_index=0)
+                            ra.f32_to_pcm_device(d_out[i], bits, d_pcm_out[i], stream, dither=dither, seed=a.seed + i, first_index=0, **gain_kw)
 
                 def fused(in_bits=in_bits, bits=bits, dither=dither, d_pcm_out=d_pcm_out):
                     if hs[0].pcm_dither()[0] != int(dither):
@@ -128,6 +136,8 @@ def main():
             all_t[k] += t
             med[k].append(round(float(np.median(t)), 4))
     result = {"streams": S, "blocks": blocks, "reps": a.reps, "burst": a.burst, "rounds": a.rounds, "lib": os.path.basename(ra.LIB_PATH), "rows": {}}
+    if gain_kw:
+        result.update(gain=a.gain)
     for k in rows:
         v = np.asarray(all_t[k])
         result["rows"][k] = {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(v.min()), 4), "max_ms": round(float(v.max()), 4),

@@ -27,6 +27,8 @@ input alone: row (d) and the PCM-input rows of --stats are left out.  (128 chann
 --rounds R (default 1): rows (b) and (c) are measured R times in alternation, b c b c ..., --reps repetitions each, in the one
 process; the rows are then over all their repetitions and carry every round's median (round_medians_ms), so that the two-pass
 route's own spread from round to round stands beside the gain.
+--gain G (default 1: the setting is left alone, so that a library from before it can be measured): every handle's output gain
+(ResamplerFir.set_pcm_gain); the conversion passes of the two-pass rows take the same gain.
 --convert: instead of the table, the stand-alone conversion alone -- rsmp_f32_to_pcm_device without and with dither over
 --convert-values values, and rsmp_device_stream_copy moving the same number of bytes (the conversion reads 4 and writes bits / 8
 bytes a value, the copy reads and writes 4 bytes a float) -- each bracketed by events, median of --reps bursts, with GB/s.
@@ -101,6 +103,7 @@ def main():
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--gain", type=float, default=1.0)
     ap.add_argument("--convert", action="store_true")
     ap.add_argument("--convert-values", type=int, default=1 << 27)
     a = ap.parse_args()
@@ -118,6 +121,8 @@ def main():
     hs = [ra.ResamplerFir.new(C, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000, ra.Latency.Sample64, ra.Attenuation.Db90) for _ in range(S)]
     for i, h in enumerate(hs):
         h.set_pcm_dither(dither, a.seed + i)
+        if a.gain != 1.0:
+            h.set_pcm_gain(a.gain)
     batch = ra.FirBatch(hs)
     batch.device_planner = False   # (the fused entry is planned on the host: the same planner for every row of the table)
     base = torch.from_numpy(synth.sweep(N, C, 44100.0)).to(dev)
@@ -155,6 +160,9 @@ def main():
         return times
 
     result = {"streams": S, "frames": N, "reps": a.reps, "dither": a.dither, "rows": {}}
+    gain_kw = {"gain": a.gain} if a.gain != 1.0 else {}
+    if gain_kw:
+        result.update(gain=a.gain)
     if C != 2 or a.rounds != 1:
         result.update(channels=C, rounds=a.rounds)
     produced = [0]
@@ -177,7 +185,7 @@ def main():
             f32_launch()
             e0.record()
             for i, (o, q, n) in enumerate(zip(d_out, d_pcm_out, produced[0])):
-                ra.f32_to_pcm_device(o[:n], bits, q, stream, dither=dither, seed=a.seed + i)
+                ra.f32_to_pcm_device(o[:n], bits, q, stream, dither=dither, seed=a.seed + i, **gain_kw)
             e1.record()
             return True
 
@@ -219,7 +227,7 @@ def main():
                 d_acc.zero_()   # (the caller zeroes its accumulators: part of the route)
                 f32_launch()
                 for i, (o, q, n) in enumerate(zip(d_out, d_pcm_out, produced[0])):
-                    ra.f32_to_pcm_stats_device(o[:n], bits, q, d_acc[i], stream, dither=dither, seed=a.seed + i)
+                    ra.f32_to_pcm_stats_device(o[:n], bits, q, d_acc[i], stream, dither=dither, seed=a.seed + i, **gain_kw)
 
             on_f32 = None
             for name, step in (("f32", fused_f32), (f"pcm_{bits}", fused_pcm))[:2 if C == 2 else 1]:
