@@ -214,7 +214,7 @@ M_RMS_CAP = 3.0
 M_MAX_CAP = 4.0
 # (M_RMS, M_MAX) per kernel family: 1.25 x the worst ratio over the family's cases in tests/test_accuracy_f64_gpu.py
 # ("fft_pair_io": tests/test_fft_pair_builds_gpu.py, "fft_wave_builds": tests/test_fft_wave_builds_gpu.py, "fft_workgroup":
-# tests/test_fft_workgroup_builds_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
+# tests/test_fft_workgroup_builds_gpu.py, "lockstep_step_*": tests/test_fir_lockstep_paths_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
 MARGINS = {
     "fir_bulk": (1.5, 1.6),    # worst x1.191 / x1.256: the f32 periodic kernels (pre-mixed rows); the split kernel x0.78 / x0.92
     "lockstep": (1.0, 1.1),    # worst x0.784 / x0.867
@@ -228,6 +228,16 @@ MARGINS = {
     # tests/test_fft_workgroup_builds_gpu.py: every build of the workgroup kernels on every plan, mixed-channel batches included, 22
     # blocks each (three per-call): worst x1.000 / x1.000 -- all 126 cases are bit-equal to the scalar spec, so the ratio is exactly 1
     "fft_workgroup": (1.3, 1.3),
+    # tests/test_fir_lockstep_paths_gpu.py: every path of the lock-step step kernel, six steps or more per case, mostly of 64 frames
+    # (as few as 2068 values: the max ratio is noisier than "lockstep"'s).  The split image, 160-byte rows x NK 1..6 and 128-byte
+    # rows x NK 2..6: worst x1.120 (16 -> 192 kHz, 16 taps: one 32-tap step, 160-byte rows) / x0.835 (22.05 -> 16 kHz, 16 taps,
+    # 128-byte rows)
+    "lockstep_step_split": (1.5, 1.1),
+    # ... the exact-f32 spans, even and odd channel counts x nblk 2..12, and the two-channel streams whose image was given up:
+    # worst x1.201 (8 channels 32 -> 22.05 kHz, 128 taps, nblk 10) / x1.942 (4 channels 44.1 -> 16 kHz, 128 taps, nblk 11)
+    "lockstep_step_f32": (1.6, 2.5),
+    # ... the reference form: worst x0.735 (2 channels 44100 -> 44101 Hz, 32 taps) / x0.670 (2 channels 192 -> 16 kHz, 16 taps)
+    "lockstep_step_ref": (1.0, 0.9),
 }
 # The (family, block) builds of fft_kernels.hip whose every case in profiles/accuracy_f64.txt (the rows of "fft_workgroup", their last
 # column) was bit-equal to the scalar spec, OracleFft(1, .., simd=False) per channel: tests/test_fft_workgroup_builds_gpu.py asserts

@@ -60,22 +60,26 @@ def gate(family, label, y, ref, yard):
 
 
 def test_margins_respect_their_conditions():
-    assert set(R.MARGINS) == {"fir_bulk", "lockstep", "fft", "fft_pair_io", "fft_wave_builds", "fft_workgroup"}   # (every family in use is held under the caps)
+    assert set(R.MARGINS) == {"fir_bulk", "lockstep", "fft", "fft_pair_io", "fft_wave_builds", "fft_workgroup", "lockstep_step_split",
+                              "lockstep_step_f32", "lockstep_step_ref"}   # (every family in use is held under the caps)
     for family, (m_rms, m_max) in R.MARGINS.items():
         assert 0.0 < m_rms <= R.M_RMS_CAP and 0.0 < m_max <= R.M_MAX_CAP, family
 
 
+ATTENUATION = {60: ra.Attenuation.Db60, 90: ra.Attenuation.Db90, 120: ra.Attenuation.Db120}
+
+
 @functools.lru_cache(maxsize=None)
-def table(in_hz, out_hz, lat):
+def table(in_hz, out_hz, lat, att=ATT):
     """The reference's f32 coefficient table, three ways: the oracle's design, the oracle handle's, the library's."""
-    t = R.fir_table(in_hz, out_hz, lat.taps(), ATT)
-    assert np.array_equal(t, o.OracleFir(1, in_hz, out_hz, lat.taps(), ATT).coeffs())
-    assert np.array_equal(t, ra.design_fir_coeffs(in_hz, out_hz, lat, ra.Attenuation.Db90).reshape(t.shape))
+    t = R.fir_table(in_hz, out_hz, lat.taps(), att)
+    assert np.array_equal(t, o.OracleFir(1, in_hz, out_hz, lat.taps(), att).coeffs())
+    assert np.array_equal(t, ra.design_fir_coeffs(in_hz, out_hz, lat, ATTENUATION[att]).reshape(t.shape))
     return t
 
 
-def scalar_spec(ch, in_hz, out_hz, lat):
-    return o.OracleFir(ch, in_hz, out_hz, lat.taps(), ATT, o.CONVOLVE_SCALAR)
+def scalar_spec(ch, in_hz, out_hz, lat, att=ATT):
+    return o.OracleFir(ch, in_hz, out_hz, lat.taps(), att, o.CONVOLVE_SCALAR)
 
 
 # ---- FIR bulk -----------------------------------------------------------------------------------------------------

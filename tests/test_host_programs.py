@@ -499,3 +499,77 @@ def test_fft_workgroup_builds_fixture_names_every_build(tmp_path):
     # (check c: the list next to the margins names builds of these kernels, by family and block)
     from oracle import reference_f64 as R
     assert set(R.FFT_WORKGROUP_BIT_EQUAL) <= {(b[0], b[2]) for b in names["default"] | names["switched"]}
+
+
+# ---- the paths of the lock-step step kernel that tests/test_fir_lockstep_paths_gpu.py runs ----------------------------------------
+def test_fir_lockstep_paths_fixture_names_every_path(tmp_path):
+    """tests/host/fir_lockstep_paths_dump.cpp (plain C++, g++ with ASan + UBSan, linked with fir_lockstep_geometry.cpp): what
+    lockstep_geometry answers to every request of tests/test_fir_lockstep_paths_gpu.py -- its CASES, then the request it expects to
+    be refused -- byte for byte tests/golden/fir_lockstep_paths.json, which so cannot go stale.  From the fixture and the GPU
+    module's own lists:
+      - the cases name every (layout, row pitch / channel parity, NK or nblk) path of PATHS: 160-byte rows x NK 1..6, 128-byte rows
+        x NK 2..6, exact f32 x even / odd channel counts x nblk 2..12, the reference form;
+      - they name all ten (outcome, slots = 1 / slots > 1) rows of the decision tree;
+      - an exact-f32 case has more than 16 columns in a workgroup (chunk > 0 in the kernel's unit loop), with an even and with an
+        odd channel count; the even f32 paths cycle through 4, 6 and 8 channels, the odd ones alternate 1 and 3; split cases
+        have two channels; the rates are the ten of RATES but for 44100 -> 44101; Db60 and Db120 occur twice or more;
+      - the refused request does not fit, and the three cases that run twice are one per arithmetic.
+    From the 28 800-row walk of tests/host/fir_lockstep_dump.cpp (held to tests/golden/fir_lockstep.json by
+    test_lockstep_rules_as_before_the_move): no row has a path outside PATHS, and every path of PATHS occurs in it."""
+    import test_fir_lockstep_paths_gpu as p   # (its lists of cases: nothing of them needs a GPU)
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fir_lockstep_paths_dump.cpp"
+    geo = os.path.join(CSRC, "fir_lockstep_geometry.cpp")
+    exe, walk_exe = str(tmp_path / "fir_lockstep_paths_dump"), str(tmp_path / "fir_lockstep_dump")
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_lockstep_paths_dump.cpp"), geo, "-o", exe], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}
+    run = subprocess.run([exe], input=p.requests(), env=env, capture_output=True, text=True, timeout=300)
+    _clean(run)
+    with open(os.path.join(ROOT, "tests", "golden", "fir_lockstep_paths.json")) as fh:
+        text = fh.read()
+    assert run.stdout == text, "tests/golden/fir_lockstep_paths.json is not what tests/host/fir_lockstep_paths_dump.cpp prints"
+    rows = json.loads(text)["rows"]
+    assert rows == p.fixture() and len(rows) == len(p.CASES) + 1
+    w = p.rows_of_the_walk
+
+    # ---- the GPU module's cases
+    named = [p.path_of(r) for r in rows[:-1]]
+    assert set(named) == set(p.PATHS) and len(set(p.PATHS)) == len(p.PATHS) == 11 + 22 + 1
+    outcomes = {w.outcome(r) for r in rows[:-1]}
+    assert outcomes == {o + s for o in ("split, 160-byte rows", "split, packed 128-byte rows", "split given up for exact f32", "exact f32",
+                                        "reference form") for s in (" (slots = 1)", " (slots > 1)")}
+    wide = {path[1] for path, r in zip(named, rows) if path[0] == "f32" and w.geometry_of(r)["max_cols"] > 16}
+    assert wide == {"even", "odd"}
+    given_up = [w.geometry_of(r) for r in rows[:-1] if w.outcome(r).startswith("split given up")]
+    assert len(given_up) >= 2 and any(g["max_cols"] > 16 for g in given_up) and any(g["slots"] > 1 for g in given_up)
+    even = [c[2] for c, path, r in zip(p.CASES, named, rows) if path[:2] == ("f32", "even") and w.outcome(r).startswith("exact")]
+    odd = [c[2] for c, path in zip(p.CASES, named) if path[:2] == ("f32", "odd")]
+    assert even == [(4, 6, 8)[i % 3] for i in range(11)] and odd == [(1, 3)[i % 2] for i in range(11)]
+    assert [path[2] for path in named if path[:2] == ("f32", "odd")] == list(range(2, 13))
+    assert all(c[2] == 2 for c, path in zip(p.CASES, named) if path[0] == "split")
+    assert all(c[3] in p.RATES and (c[4] in p.RATES or c[3:5] == (44100, 44101)) for c in p.CASES)
+    assert (44100, 44101) in [c[3:5] for c in p.CASES]
+    assert any(path[0] == "reference" and c[2] == 1 for c, path in zip(p.CASES, named))
+    assert any(path[0] == "reference" and c[0].taps() + 15 * 12 > 192 and c[3] == 12 * c[4] for c, path in zip(p.CASES, named))
+    for att in (60, 120):
+        assert sum(c[1] == att for c in p.CASES) >= 2, att
+    assert all(c[5] == 64 for c, r in zip(p.CASES, rows) if w.outcome(r) not in ("split, packed 128-byte rows (slots = 1)", "reference form (slots = 1)"))
+    for c, r in zip(p.CASES, rows):   # (workgroups of several streams: full ones and a partial one)
+        slots = w.geometry_of(r)["slots"]
+        assert p.n_streams(slots) == min(2 * slots + 1, 17) and (slots == 1 or p.n_streams(slots) % slots != 0 or slots == 16)
+    assert w.geometry_of(rows[-1])["lds_bytes"] == 0 and w.outcome(rows[-1]) == "does not fit" and p.path_of(rows[-1]) is None
+    assert [named[i][0] for i in p.REPEATED] == ["split", "f32", "reference"]
+    assert len(p.BEYOND_CAPS) <= 2 and all(b[0] in p.PATHS for b in p.BEYOND_CAPS)
+
+    # ---- the walk: nothing outside PATHS
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_lockstep_dump.cpp"), geo, "-o", walk_exe], check=True)
+    run = subprocess.run([walk_exe, "geometry"], env=env, capture_output=True, text=True, timeout=300)
+    _clean(run)
+    walk = [r for r in run.stdout.splitlines() if r.startswith("walk ")]
+    assert len(walk) == 28800
+    reached = {}
+    for r in walk:
+        path = p.path_of(r)
+        reached[path] = reached.get(path, 0) + 1
+    assert reached.pop(None) == 1440   # ("does not fit")
+    assert set(reached) == set(p.PATHS), (sorted(set(reached) - set(p.PATHS), key=str), sorted(set(p.PATHS) - set(reached), key=str))

@@ -429,3 +429,120 @@ def test_a_mixed_batch_defect_fails_the_workgroup_builds_gate(name, stream, forg
     assert r_rms > m_rms and r_max > m_max, (r_rms, r_max)
     clean = R.budget(ref.astype(np.float32), ref, yard)
     assert clean[0] <= 1.0 and clean[1] <= 1.0
+
+
+# ---- the gate of tests/test_fir_lockstep_paths_gpu.py can fail -------------------------------------------------------------------
+LOCKSTEP_STEP_FAMILIES = ["lockstep_step_split", "lockstep_step_f32", "lockstep_step_ref"]
+DEFECT_CLASS = 5        # the class j whose outputs n = j (mod b) carry the defect
+DEFECT_STEP = 4         # the step in front of which a history frame is the wrong one
+
+
+def smallest_lockstep_case(family):
+    """The case of the family with the fewest pooled values, its fixture geometry and its CPU data."""
+    import test_fir_lockstep_paths_gpu as p
+    cases = [c for c, row in zip(p.CASES, p.fixture()) if p.FAMILY[p.path_of(row)[0]] == family]
+    case = min(cases, key=lambda c: sum(s["ref"].size for s in p.case_data(c)["streams"]))
+    return p, case, p.geometry_of(case), p.case_data(case)
+
+
+def class_period(geo):
+    """b, the outputs of a super period: the classes of the class tables; the reference form has none, 16 stands in."""
+    return geo["b"] if geo["periodic"] else 16
+
+
+def lockstep_defect(p, case, geo, data, name):
+    """The f64 evaluation of every stream of the case with one defect, pooled as the GPU test pools."""
+    lat, att, ch, in_hz, out_hz, step = case
+    taps, coeffs, b = lat.taps(), data["coeffs"], class_period(geo)
+    out = []
+    for s in data["streams"]:
+        pos, x = s["pos"], s["seen"]
+        k = np.arange(DEFECT_CLASS, len(pos), b)
+        assert k.size >= 1
+        if name == "one class uses its neighbour's pre-mixed row":
+            # class j + 1 lies num / den of a frame later: that many of the table's 1024 rows.  Where every class has the same
+            # phase (an integer ratio) the neighbour's row IS the class's own, and a wrong row there is the table's next one.
+            g = np.gcd(in_hz, out_hz)
+            rows = int(round(1024.0 * ((in_hz // g) % (out_hz // g)) / (out_hz // g))) % 1024 or 1
+            q = copy.copy(pos)
+            q.phase1 = pos.phase1.copy()
+            q.phase1[k] = (q.phase1[k] + rows) % 1024
+            q.phase2 = np.minimum(q.phase1 + 1, 1023)
+            y = R.fir_f64(x, ch, coeffs, q)
+        elif name == "the last tap is dropped at every output of one class":
+            y = s["ref"].reshape(-1, ch).copy()
+            f = pos.frac[k]
+            w = (np.float32(1.0) - f).astype(np.float64) * coeffs[pos.phase1[k], -1] + f.astype(np.float64) * coeffs[pos.phase2[k], -1]
+            y[k] -= w[:, None] * x.reshape(-1, ch).astype(np.float64)[pos.index[k] + taps - 1]
+            y = y.reshape(-1)
+        else:
+            assert name == "one frame at a step boundary comes from the other history buffer"
+            calls = s["calls"]
+            first_call = DEFECT_STEP + (1 if s["pre"] else 0)
+            t = sum(c[0] for c in calls[:first_call]) // ch - 1          # the newest frame the earlier calls left behind
+            o = sum(c[1] for c in calls[:first_call])                    # values produced before
+            if t - step < 0 or int(pos.index[o // ch]) > t:              # (a stream whose step does not read it: left clean)
+                out.append(s["ref"])
+                continue
+            x2 = x.copy().reshape(-1, ch)
+            x2[t] = x2[t - step]
+            y = np.concatenate([s["ref"][:o], R.fir_f64(x2.reshape(-1), ch, coeffs, pos)[o:]])
+        out.append(y)
+    return np.concatenate(out)
+
+
+LOCKSTEP_DEFECTS = ["one class uses its neighbour's pre-mixed row", "the last tap is dropped at every output of one class",
+                    "one frame at a step boundary comes from the other history buffer"]
+
+
+@pytest.mark.parametrize("family", LOCKSTEP_STEP_FAMILIES)
+def test_a_clean_f32_result_passes_the_lockstep_step_gates(family):
+    """The f64 sums of the family's smallest case rounded to f32 -- the best an f32 kernel can return -- pass at the family's
+    margins (the reference form's max margin is below 1: the yardstick itself, x1 by definition, would not)."""
+    p, case, geo, data = smallest_lockstep_case(family)
+    ref = np.concatenate([s["ref"] for s in data["streams"]])
+    yard = np.concatenate([s["yard"] for s in data["streams"]])
+    m_rms, m_max = R.MARGINS[family]
+    r_rms, r_max = R.budget(ref.astype(np.float32), ref, yard)
+    print(f"{family} {p.label_of(case)}: the f64 sums as f32 x{r_rms:.3f} rms, x{r_max:.3f} max")
+    assert r_rms <= min(1.0, m_rms) and r_max <= min(1.0, m_max), (family, r_rms, r_max)
+    assert R.budget(yard, ref, yard) == (1.0, 1.0)
+
+
+@pytest.mark.parametrize("name", LOCKSTEP_DEFECTS)
+@pytest.mark.parametrize("family", LOCKSTEP_STEP_FAMILIES)
+def test_a_lockstep_step_defect_fails_the_gate_of_its_family(family, name):
+    """The smallest case of each family of tests/test_fir_lockstep_paths_gpu.py -- the fewest pooled values: the max ratio is the
+    noisiest there and a defect in a few outputs weighs the least in the RMS --, each defect applied to the f64 evaluation of
+    every stream and the result rounded to f32: a kernel whose ONLY fault is the defect, pooled and gated as the GPU test does.
+    The class is n = 5 (mod b), b the outputs of the geometry's super period (16 for the reference form, which has no classes); the
+    history frame is the newest one the calls before step 4 left behind, read `step_frames` earlier by step 4 and later.
+    Measured (values changed; RMS against the scalar oracle; then RMS and max against f64 in multiples of the oracle's distance):
+      split, 2 ch 88.2 -> 22.05 kHz, 64 taps, 11 streams, 2100 values (4/1: every class has phase row 0, the wrong row is row 1)
+        neighbour's pre-mixed row           30    1.08e-5     x279      x716
+        last tap dropped                    29    1.65e-7     x4.13     x7.67
+        frame from the other buffer        346    1.63e-2     x4.2e5    x1.5e6
+      exact f32, 1 ch 176.4 -> 48 kHz, 64 taps, 17 streams, 2074 values (147/40: the neighbour's row lies 691 rows on)
+        neighbour's pre-mixed row           24    3.33e-3     x9.4e4    x2.3e5
+        last tap dropped                    24    2.70e-7     x7.59     x13.5
+        frame from the other buffer        289    1.75e-2     x4.9e5    x1.1e6
+      reference form, 2 ch 192 -> 16 kHz, 16 taps, 9 streams, 2068 values (12/1, as the split case: row 1 for row 0)
+        neighbour's row                    132    1.48e-5     x900      x1770
+        last tap dropped                   132    5.94e-6     x361      x497
+        frame from the other buffer         24    2.91e-3     x1.8e5    x7.6e5
+    The dropped tap of the split and the f32 case passes "1e-6 RMS of the oracle"; every defect fails both bounds here, and both
+    caps (M_RMS_CAP, M_MAX_CAP), so a path listed in the GPU module's BEYOND_CAPS is not let through with one either."""
+    p, case, geo, data = smallest_lockstep_case(family)
+    ref = np.concatenate([s["ref"] for s in data["streams"]])
+    yard = np.concatenate([s["yard"] for s in data["streams"]])
+    y = lockstep_defect(p, case, geo, data, name).astype(np.float32)
+    changed = int(np.count_nonzero(y != ref.astype(np.float32)))
+    old_rms, old_max = R.errors(y, yard)
+    r_rms, r_max = R.budget(y, ref, yard)
+    print(f"{family} {p.label_of(case)} ({ref.size} values) {name}: {changed} values changed; against the oracle {old_rms:.3e} (max {old_max:.3e}); "
+          f"against f64 x{r_rms:.3g} rms, x{r_max:.3g} max")
+    assert changed > 0
+    m_rms, m_max = R.MARGINS[family]
+    if name.startswith("the last tap") and family != "lockstep_step_ref":
+        assert old_rms <= OLD_RMS_GATE
+    assert r_rms > max(m_rms, R.M_RMS_CAP) and r_max > max(m_max, R.M_MAX_CAP), (r_rms, r_max, R.MARGINS[family])
