@@ -214,7 +214,7 @@ M_RMS_CAP = 3.0
 M_MAX_CAP = 4.0
 # (M_RMS, M_MAX) per kernel family: 1.25 x the worst ratio over the family's cases in tests/test_accuracy_f64_gpu.py
 # ("fft_pair_io": tests/test_fft_pair_builds_gpu.py, "fft_wave_builds": tests/test_fft_wave_builds_gpu.py, "fft_workgroup":
-# tests/test_fft_workgroup_builds_gpu.py, "lockstep_step_*": tests/test_fir_lockstep_paths_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
+# tests/test_fft_workgroup_builds_gpu.py, "lockstep_step_*": tests/test_fir_lockstep_paths_gpu.py, "fir_generic": tests/test_fir_generic_builds_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
 MARGINS = {
     "fir_bulk": (1.5, 1.6),    # worst x1.191 / x1.256: the f32 periodic kernels (pre-mixed rows); the split kernel x0.78 / x0.92
     "lockstep": (1.0, 1.1),    # worst x0.784 / x0.867
@@ -238,6 +238,12 @@ MARGINS = {
     "lockstep_step_f32": (1.6, 2.5),
     # ... the reference form: worst x0.735 (2 channels 44100 -> 44101 Hz, 32 taps) / x0.670 (2 channels 192 -> 16 kHz, 16 taps)
     "lockstep_step_ref": (1.0, 0.9),
+    # tests/test_fir_generic_builds_gpu.py: every build of the reference-form FIR kernels (latency, tiled <0 | 1 | 2, false | true>, PCM-input
+    # staging, repair), every launch of every stream gated on its own (as few as 701 values): worst x0.892 (2 channels 44100 -> 48001 Hz,
+    # 16 taps, the 701-frame launch on the latency kernel) / x0.793 (5 channels 47999 -> 44100 Hz, 16 taps, the 701-frame launch).  The 16-tap
+    # rows lie at x0.82-0.89 RMS, the 128-tap rows at x0.43-0.53: four lanes of a group carry four taps each at 16 taps, so the
+    # eight-partial-sum form gains less over the scalar sum ("2ch-44100-48001-Sample8-Auto" under fir_bulk: x0.84)
+    "fir_generic": (1.2, 1.0),
 }
 # The (family, block) builds of fft_kernels.hip whose every case in profiles/accuracy_f64.txt (the rows of "fft_workgroup", their last
 # column) was bit-equal to the scalar spec, OracleFft(1, .., simd=False) per channel: tests/test_fft_workgroup_builds_gpu.py asserts

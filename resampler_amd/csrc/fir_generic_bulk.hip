@@ -29,16 +29,15 @@ namespace rsmp {
 namespace {
 
 constexpr int kBulkBlock = 1024;                     // sixteen waves
-constexpr uint32_t kBulkTileMax = 4096;              // output frames per workgroup
-constexpr uint32_t kBulkWindowBytes = 64u * 1024u;   // LDS for the input window
-constexpr uint32_t kRows = 1024;                     // phases (resampler_fir.rs:17)
+constexpr uint32_t kRows = kBulkRows;                // phases (resampler_fir.rs:17); the tile and the LDS regions' sizes: fir_generic_plan.h
 
 struct BulkMeta {      // one output frame of the tile
     uint16_t rel;      // its window's first frame, relative to the tile's
     uint16_t phase;    // phase1 (:563)
     float frac;        // (:565)
 };
-static_assert(sizeof(BulkMeta) == 8, "BulkMeta layout");
+static_assert(sizeof(BulkMeta) == kBulkMetaBytes && sizeof(uint16_t) == kBulkSortedBytes && kBulkScanWords >= kBulkBlock / 64,
+              "the LDS regions are the sizes generic_launch_choice adds up");
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -61,7 +60,6 @@ __device__ __forceinline__ void bulk_position(const rsmp_fir_segment& sg, uint32
     *frac = static_cast<float>(phase_f - static_cast<double>(ph));  // :565
     *v0 = sg.in_base + static_cast<int64_t>(fl);
 }
-constexpr uint32_t kBulkSegs = 256;   // run descriptors of a tile kept in LDS (a 512-frame call is ~10 runs: a tile of 4096 outputs ~80)
 
 // Descriptor pointers come out of a struct in memory: without a named address space the compiler emits FLAT loads for them
 // (which also count on the LDS counter and wait with it).
@@ -248,7 +246,7 @@ __device__ __forceinline__ void fir_generic_bulk_body(const FirStreamDesc* __res
     uint32_t* counts = reinterpret_cast<uint32_t*>(lds);                    // [1024]: outputs per phase row, then the scatter's cursors
     uint32_t* offsets = counts + kRows;                                     // [1024]: first slot of a row's outputs in `sorted`
     uint32_t* wsum = offsets + kRows;                                       // [16]: the scan's wave totals
-    rsmp_fir_segment* segs = reinterpret_cast<rsmp_fir_segment*>(wsum + 32);   // [kBulkSegs]: the tile's run descriptors
+    rsmp_fir_segment* segs = reinterpret_cast<rsmp_fir_segment*>(wsum + kBulkScanWords);   // [kBulkSegs]: the tile's run descriptors
     BulkMeta* meta = reinterpret_cast<BulkMeta*>(segs + kBulkSegs);         // [tile_frames]
     uint16_t* sorted = reinterpret_cast<uint16_t*>(meta + tile_frames);     // [tile_frames]: the tile's outputs by phase row
     float* win = reinterpret_cast<float*>(lds + ((reinterpret_cast<char*>(sorted + tile_frames) - lds + 15) & ~15));   // [window][ch]
@@ -384,31 +382,14 @@ __global__ __launch_bounds__(kBulkBlock) void fir_generic_bulk_pcm_stats_kernel(
 
 }  // namespace
 
-// Tiles of `tile` output frames whose windows fit the LDS for every stream of the launch: the largest multiple of 64 up to
-// kBulkTileMax with ceil(tile * max_ratio) + taps + 2 frames of max_channels channels inside kBulkWindowBytes; 0 = none (many
-// channels at a high ratio: the caller keeps fir_generic_kernel).
-uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double max_ratio) {
-    if (max_channels == 0 || max_ratio <= 0.0) return 0;
-    const uint32_t cap = kBulkWindowBytes / (4u * max_channels);
-    if (cap < max_taps + 8u) return 0;
-    double t = (static_cast<double>(cap) - max_taps - 4.0) / max_ratio;
-    if (t > kBulkTileMax) t = kBulkTileMax;
-    const uint32_t tile = static_cast<uint32_t>(t) / 64u * 64u;
-    return tile >= 512u ? tile : 0u;
-}
-
-hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
-                                   uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels, uint32_t uniform_taps,
+// The launch generic_launch_choice (fir_geometry.cpp) decided on: the build <ch_build, full> or its PCM-output twin, the tile, the
+// grid and the LDS are the choice's.
+hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, const GenericLaunchChoice& choice, hipStream_t stream,
                                    const FirFormat& format, const FirStatArgs& st) {
-    if (n_streams == 0 || max_out == 0) return hipSuccess;
-    if (!generic_tiled_ok(format, uniform_channels, uniform_channels)) return hipErrorNotSupported;
-    const uint32_t tile = fir_generic_bulk_tile(max_channels, max_taps, max_ratio);
-    if (tile == 0) return hipErrorNotSupported;
-    const uint32_t cap = kBulkWindowBytes / (4u * max_channels);
-    const size_t lds = (2 * kRows + 32) * sizeof(uint32_t) + kBulkSegs * sizeof(rsmp_fir_segment) + static_cast<size_t>(tile) * (sizeof(BulkMeta) + sizeof(uint16_t)) + 16 +
-                       static_cast<size_t>(cap) * max_channels * sizeof(float);
-    const bool full = uniform_taps == 128;
-    const int ci = uniform_channels == 2 ? 2 : uniform_channels == 1 ? 1 : 0;
+    if (n_streams == 0 || choice.grid_x == 0) return hipSuccess;
+    if (choice.kernel != GenericKernel::kTiled || choice.tile == 0 || choice.ch_build < 0 || choice.ch_build > 2) return hipErrorInvalidValue;
+    const bool full = choice.full;
+    const int ci = choice.ch_build;
     static const void* const fns[3][2] = {
         {reinterpret_cast<const void*>(fir_generic_bulk_kernel<0, false>), reinterpret_cast<const void*>(fir_generic_bulk_kernel<0, true>)},
         {reinterpret_cast<const void*>(fir_generic_bulk_kernel<1, false>), reinterpret_cast<const void*>(fir_generic_bulk_kernel<1, true>)},
@@ -426,12 +407,13 @@ hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_stre
     static bool granted[6][2] = {};   // (the attribute is per function and process: set once)
     bool& have = granted[mode == kFirOutPcmStats ? 5 : mode == kFirOutPcmTpdf ? 4 : mode == kFirOutPcm ? 3 : ci][full ? 1 : 0];
     if (!have) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kBulkLdsOptIn));
         if (e != hipSuccess) return e;
         have = true;
     }
-    const dim3 grid((max_out + tile - 1) / tile, n_streams);
-    uint32_t tile_arg = tile, cap_arg = cap;
+    const dim3 grid(choice.grid_x, n_streams);
+    const size_t lds = choice.lds_bytes;
+    uint32_t tile_arg = choice.tile, cap_arg = choice.window_cap_frames;
     FirStatArgs st_arg = mode == kFirOutPcmStats ? st : FirStatArgs{nullptr, 0};
     void* kargs[4] = {&d_descs, &tile_arg, &cap_arg, &st_arg};   // (the counting builds alone take the fourth)
     if (hipError_t e = hipLaunchKernel(fn, grid, dim3(kBulkBlock), kargs, lds, stream); e != hipSuccess) return e;

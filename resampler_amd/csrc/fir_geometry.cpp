@@ -1,12 +1,14 @@
 // fir_geometry.cpp -- the geometry of a periodic FIR launch for a rate pair (which kernel family, how its LDS is laid
 // out), the rules the host planner asks about, and which build of a kernel runs a geometry.  Pure functions of their
 // arguments and of debug switches read once.  Plain C++: includes no HIP header and is compiled by a host compiler for
-// the stand-alone tests (tests/host); the numbers it shares with the kernels come from the two *_consts.h headers.
+// the stand-alone tests (tests/host); the numbers it shares with the kernels come from the two *_consts.h headers and
+// fir_generic_plan.h.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "errors.h"
+#include "fir_generic_plan.h"
 #include "fir_periodic_consts.h"
 #include "fir_periodic_plan.h"
 #include "fir_split_consts.h"
@@ -353,6 +355,44 @@ const char* format_fault_text(FormatFault fault) {
 }
 bool generic_tiled_ok(const FirFormat& format, uint32_t min_channels, uint32_t max_channels) { return format.out_bits == 0 || (min_channels == 2 && max_channels == 2); }
 bool split_groups_may_share(const FirFormat& format) { return !format.pcm(); }
+
+// ---- the generic streams' kernel: latency or tiled (fir_generic_plan.h) ---------------------------------------------------------
+uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double max_ratio) {
+    if (max_channels == 0 || max_ratio <= 0.0) return 0;
+    const uint32_t cap = generic_bulk_window_cap(max_channels);
+    if (cap < max_taps + 8u) return 0;
+    double t = (static_cast<double>(cap) - max_taps - 4.0) / max_ratio;
+    if (t > kBulkTileMax) t = kBulkTileMax;
+    const uint32_t tile = static_cast<uint32_t>(t) / 64u * 64u;
+    return tile >= kBulkTileMin ? tile : 0u;
+}
+
+// Long launches of streams without a short period (arbitrary rates, src/resampler_fir.rs:295-301) take the tiled kernel, whose
+// workgroups sort a tile's outputs by phase row and stage its window in LDS; streaming calls keep the one-launch latency path.
+// PCM output: the tiled kernel's builds are two-channel; a generic stream of more channels -- a launch too short for the periodic
+// kernels, a rate pair without a short period -- keeps the batch's generic streams on the latency kernel, which stores by value
+// index for any count, at any length.
+GenericLaunchChoice generic_launch_choice(const GenericLaunchRequest& rq, bool bulk_on) {
+    GenericLaunchChoice c;
+    c.grid_x = (rq.max_out + kFirTile - 1) / kFirTile;
+    if (!bulk_on) { c.reason = GenericLatencyReason::kSwitchedOff; return c; }
+    if (rq.max_out < kFirBulkMinOut) { c.reason = GenericLatencyReason::kShort; return c; }
+    const uint32_t tile = fir_generic_bulk_tile(rq.max_channels, rq.max_taps, rq.max_ratio);
+    if (tile == 0) { c.reason = GenericLatencyReason::kNoTile; return c; }
+    if (!generic_tiled_ok(rq.format, rq.min_channels, rq.max_channels)) { c.reason = GenericLatencyReason::kFormat; return c; }
+    const uint32_t uniform_channels = rq.min_channels == rq.max_channels ? rq.max_channels : 0u;
+    c.kernel = GenericKernel::kTiled;
+    c.reason = GenericLatencyReason::kNone;
+    c.ch_build = rq.format.out_bits != 0 ? 2 : uniform_channels == 2 ? 2 : uniform_channels == 1 ? 1 : 0;
+    c.full = rq.min_taps == 128 && rq.max_taps == 128;
+    c.tile = tile;
+    c.window_cap_frames = generic_bulk_window_cap(rq.max_channels);
+    c.grid_x = (rq.max_out + tile - 1) / tile;
+    c.lds_bytes = static_cast<uint32_t>((2 * kBulkRows + kBulkScanWords) * sizeof(uint32_t) + kBulkSegs * sizeof(rsmp_fir_segment) +
+                                        static_cast<size_t>(tile) * (kBulkMetaBytes + kBulkSortedBytes) + kBulkWindowAlign +
+                                        static_cast<size_t>(c.window_cap_frames) * rq.max_channels * sizeof(float));
+    return c;
+}
 
 // Slots of launch_fir_periodic's kernel table.  0..2 = vector kernel: two channels with one lane per period / CG 2,
 // any even channel count / CG 1.  (4-tap chunks with 16-wave workgroups at 8 waves per SIMD measured

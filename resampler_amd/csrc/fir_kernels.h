@@ -8,6 +8,7 @@
 
 #include "../../include/resampler_amd.h"
 #include "fir_format.h"
+#include "fir_generic_plan.h"
 #include "fir_nonfinite.h"
 
 namespace rsmp {
@@ -259,23 +260,17 @@ __device__ __forceinline__ void fir_out_store(const FirStreamDesc& d, size_t i, 
     else d.out[i] = y;
 }
 
-constexpr uint32_t kFirTile = 32;   // output frames per workgroup tile (generic kernel): one pass of 32 x 8 lanes
-
 // Generic kernel: any ratio, reference-form two-row interpolation; grid = (max tiles, streams).
 // (format, here and below: the launch's FirFormat (fir_format.h) -- format.out_mode() selects the builds that store f32, PCM, dithered
 // PCM or counted PCM; st, for a counting launch: its statistics table, stream s's entries the s-th row; hipErrorInvalidValue without one)
 hipError_t launch_fir_generic(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out,
                               uint32_t max_channels, hipStream_t stream, bool fuse_tail = false, const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
 // The same arithmetic for LONG launches (fir_generic_bulk.hip): tiles of up to 4096 output frames per workgroup, their outputs sorted
-// by phase row, the tile's input window in LDS.  hipErrorNotSupported where no tile fits the LDS (fir_generic_bulk_tile == 0);
-// does not copy the tails (launch_fir_tail_copy).
-uint32_t fir_generic_bulk_tile(uint32_t max_channels, uint32_t max_taps, double max_ratio);
-// (uniform_channels: 1 / 2 = every stream has that many channels -- the builds for them --, anything else = any counts; PCM output: generic_tiled_ok or hipErrorNotSupported)
-hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, uint32_t max_out, uint32_t max_channels,
-                                   uint32_t max_taps, double max_ratio, hipStream_t stream, uint32_t uniform_channels = 0,
-                                   uint32_t uniform_taps = 0,    // (uniform_taps: 128 = every stream has 128 taps)
+// by phase row, the tile's input window in LDS.  Which launches take it, which build, tile, grid and LDS: generic_launch_choice
+// (fir_generic_plan.h); `choice` is its answer for the launch, hipErrorInvalidValue for one that is not tiled.  Does not copy the
+// tails (launch_fir_tail_copy).
+hipError_t launch_fir_generic_bulk(const FirStreamDesc* d_descs, uint32_t n_streams, const GenericLaunchChoice& choice, hipStream_t stream,
                                    const FirFormat& format = FirFormat{}, const FirStatArgs& st = {});
-constexpr uint32_t kFirBulkMinOut = 8192;   // launches whose longest generic stream produces fewer frames keep fir_generic_kernel
 // Re-evaluates, in the reference's two-row form, the output chunks a periodic launch marked as non-finite
 // (fir_nonfinite.h); exits at once when the launch marked nothing.
 // (done / done_attached, here and in launch_fir_tail_copy: as in launch_fir_repair_multi below -- the launch completes `done`

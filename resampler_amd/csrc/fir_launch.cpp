@@ -325,23 +325,24 @@ int launch_generic(Launch& L) {
     // a launch made of generic-kernel streams only (a streaming call, a batch of them) lets that kernel copy
     // the tails as well: one launch per call instead of two
     L.tail_fused = L.n_generic == L.n && L.max_out_generic != 0;
-    // Long launches of streams without a short period (arbitrary rates, src/resampler_fir.rs:295-301) take the tiled kernel,
-    // whose workgroups sort a tile's outputs by phase row and stage its window in LDS (fir_generic_bulk.hip); streaming calls
-    // keep the one-launch latency path.  (RSMP_FIR_GENERIC_BULK=0, debug: the latency kernel for everything.)
+    // Latency kernel or tiled kernel, and which build of it: generic_launch_choice (fir_generic_plan.h, fir_geometry.cpp).
+    // (RSMP_FIR_GENERIC_BULK=0, debug: the latency kernel for everything.)
     static const bool bulk_on = [] { const char* e = knob("RSMP_FIR_GENERIC_BULK"); return !e || atoi(e) != 0; }();
-    const bool generic_bulk = bulk_on && L.n_generic != 0 && L.max_out_generic >= kFirBulkMinOut &&
-                              fir_generic_bulk_tile(L.max_ch_generic, L.max_taps_generic, L.max_ratio_generic) != 0 &&
-                              // (PCM output: the tiled kernel's builds are two-channel; a generic stream of more channels -- a launch too short for the periodic kernels, a rate
-                              // pair without a short period -- keeps the batch's generic streams on the latency kernel, which stores by value index for any count, at any length)
-                              generic_tiled_ok(L.format, L.min_ch_generic, L.max_ch_generic);
+    if (L.n_generic == 0) return RSMP_OK;
+    GenericLaunchRequest rq;
+    rq.format = L.format;
+    rq.max_out = L.max_out_generic;
+    rq.min_channels = L.min_ch_generic;
+    rq.max_channels = L.max_ch_generic;
+    rq.min_taps = L.min_taps_generic;
+    rq.max_taps = L.max_taps_generic;
+    rq.max_ratio = L.max_ratio_generic;
+    const GenericLaunchChoice choice = generic_launch_choice(rq, bulk_on);
     const FirStatArgs st = L.stat_rows(0);   // (the generic streams are the launch's first)
-    if (generic_bulk) {
+    if (choice.kernel == GenericKernel::kTiled) {
         L.tail_fused = false;
-        RSMP_HIP_CHECK(launch_fir_generic_bulk(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic,
-                                               L.max_taps_generic, L.max_ratio_generic, L.stream,
-                                               L.min_ch_generic == L.max_ch_generic ? L.max_ch_generic : 0u,
-                                               L.min_taps_generic == L.max_taps_generic ? L.max_taps_generic : 0u, L.format, st));
-    } else if (L.n_generic)
+        RSMP_HIP_CHECK(launch_fir_generic_bulk(L.d_descs, static_cast<uint32_t>(L.n_generic), choice, L.stream, L.format, st));
+    } else
         RSMP_HIP_CHECK(launch_fir_generic(L.d_descs, static_cast<uint32_t>(L.n_generic), L.max_out_generic, L.max_ch_generic, L.stream,
                                           L.tail_fused, L.format, st));
     return RSMP_OK;

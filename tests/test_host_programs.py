@@ -573,3 +573,96 @@ def test_fir_lockstep_paths_fixture_names_every_path(tmp_path):
         reached[path] = reached.get(path, 0) + 1
     assert reached.pop(None) == 1440   # ("does not fit")
     assert set(reached) == set(p.PATHS), (sorted(set(reached) - set(p.PATHS), key=str), sorted(set(p.PATHS) - set(reached), key=str))
+
+
+# ---- the builds of the reference-form FIR kernels that tests/test_fir_generic_builds_gpu.py launches -----------------------------
+def test_fir_generic_builds_fixture_names_every_build(tmp_path):
+    """tests/host/fir_generic_builds_dump.cpp (plain C++, g++ with ASan + UBSan, linked with fir_geometry.cpp alone): what
+    generic_launch_choice answers to every launch of tests/test_fir_generic_builds_gpu.py -- its cases' launches, a batch's streams
+    alone, the two cases with RSMP_FIR_GENERIC_BULK=0, the f32 twins of the PCM cases -- byte for byte
+    tests/golden/fir_generic_builds.json, which so cannot go stale; the program also checks, for these requests and for a sweep of
+    1 .. 16 channels x 16 / 32 / 64 / 128 taps x the ten sample rates against the ten +- 1 Hz, that ceil(tile * ratio) + taps + 2 <= cap
+    wherever a tile is returned: the window clamp of the tiled kernel cannot bite.  From the fixture and the GPU module's own lists:
+      - every TILED case's first and third launch is the tiled kernel in the build and tile the module expects, its second the
+        latency kernel ("short"): together all six f32 builds <0 | 1 | 2, false | true>, tiles of 4096 and of 512 (the smallest
+        there is) and four sizes in between;
+      - no answer is a build or an outcome outside those the module has a case for: a seventh build, a new reason to stay on the
+        latency kernel or a PCM-output request here fails until it has one;
+      - the {2, 1, 3}-channel batch is <0, true> at the widest stream's tile, the 128 + 32-tap batch <2, false>; a stream of the
+        third batch has fewer tiles than grid.x and one has no output in the long launches; among the streams run alone some
+        take the batch's build and tile (compared bit for bit) and some do not (gated);
+      - the PCM cases are two-channel PCM-input launches of the tiled kernel, the same build and tile as their f32 twins;
+      - both "no tile fits" requests answer latency / no_tile at more than 8192 outputs, the SHORT cases latency / short, the
+        switched cases latency / switched_off;
+      - the 8-frame-call case is tiled at 4096."""
+    import test_fir_generic_builds_gpu as g   # (its lists of cases: nothing of them needs a GPU)
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fir_generic_builds_dump.cpp"
+    exe = str(tmp_path / "fir_generic_builds_dump")
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_generic_builds_dump.cpp"), os.path.join(CSRC, "fir_geometry.cpp"),
+                                       "-o", exe], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}
+    run = subprocess.run([exe], input=g.requests(), env=env, capture_output=True, text=True, timeout=300)
+    _clean(run)
+    with open(os.path.join(ROOT, "tests", "golden", "fir_generic_builds.json")) as fh:
+        text = fh.read()
+    assert run.stdout == text, "tests/golden/fir_generic_builds.json is not what tests/host/fir_generic_builds_dump.cpp prints"
+    assert "tiled answers above and in" in json.loads(text)["window_bound"]
+    g.fixture.cache_clear()
+    fx = g.fixture()
+
+    def build(d):
+        return (d["ch"], d["full"], d["tile"])
+
+    # ---- TILED: the six builds, the tiles
+    assert len(g.TILED) == len(g.TILED_BUILDS)
+    for case, want in zip(g.TILED, g.TILED_BUILDS):
+        first, second, third = (fx[case.name, k, None] for k in range(3))
+        assert first["kernel"] == third["kernel"] == "tiled" and build(first) == build(third) == want, (case.name, first, third)
+        assert (second["kernel"], second["reason"]) == ("latency", "short"), case.name
+        assert 8192 <= int(first["request"].split()[2]) < 8192 + min(512, first["tile"]), case.name   # (the last tile: partial and small)
+        assert case.name.startswith("<%d,%s>" % (want[0], "true" if want[1] else "false")), case.name
+    assert {b[:2] for b in g.TILED_BUILDS} == {(c, f) for c in (0, 1, 2) for f in (0, 1)}
+    tiles = {b[2] for b in g.TILED_BUILDS}
+    assert max(tiles) == 4096 and min(tiles) == 512 and len(tiles) == 6
+    assert {int(c.streams[0][1].taps()) for c, b in zip(g.TILED, g.TILED_BUILDS) if b[:2] == (2, 0)} == {16, 32, 64}
+    # ---- nothing without a case
+    known = {("tiled",) + b for b in g.TILED_BUILDS} | {("latency", r) for r in ("short", "no_tile", "switched_off")}
+    for key, d in fx.items():
+        assert (("tiled",) + build(d) if d["kernel"] == "tiled" else ("latency", d["reason"])) in known, (key, d)
+        assert d["request"].split()[1] == "0", key   # (f32 output everywhere)
+    # ---- BATCHES
+    a, b, c = g.BATCHES
+    assert [s[0] for s in a.streams] == [2, 1, 3] and len({s[1] for s in a.streams}) == 1
+    assert build(fx[a.name, 0, None]) == build(fx[a.name, 2, None]) == (0, 1, 4096) == build(fx[a.name, 0, 2])
+    assert build(fx[a.name, 0, 0]) == (2, 1, 4096) and build(fx[a.name, 0, 1]) == (1, 1, 4096)
+    assert [s[1].taps() for s in b.streams] == [128, 32] and [s[0] for s in b.streams] == [2, 2]
+    assert build(fx[b.name, 0, None]) == (2, 0, 4096) == build(fx[b.name, 0, 1]) and build(fx[b.name, 0, 0]) == (2, 1, 4096)
+    outs = [g.produced_frames(s, ln, g.chunk_frames(c, i)) for i, (s, ln) in enumerate(zip(c.streams, c.lens))]
+    first = fx[c.name, 0, None]
+    assert first["kernel"] == "tiled" and first["grid_x"] == 3 and 0 < -(-outs[1][0] // first["tile"]) < first["grid_x"]
+    assert outs[2][0] == outs[2][2] == 0 and outs[2][1] > 0
+    same = [g.same_launch(fx[case.name, k, None], fx[case.name, k, i]) for case in g.BATCHES for i in range(len(case.streams)) for k in range(3)]
+    assert same.count(True) >= 9 and same.count(False) >= 6
+    # ---- PCM input
+    for case in g.PCM:
+        for k in range(3):
+            d, twin = fx[case.name, k, None], fx[case.name, k, "f32 twin"]
+            assert int(d["request"].split()[0]) == case.bits and case.streams[0][0] == 2 and g.same_launch(d, twin), (case.name, k)
+        assert build(fx[case.name, 0, None]) == (2, 1, 4096)
+    assert [c.bits for c in g.PCM] == [16, 24, 32]
+    # ---- no tile fits, short launches, the switch, the 8-frame calls
+    assert [c.streams[0][0] for c in g.NO_TILE] == [16, 2]
+    for case in g.NO_TILE:
+        for k in range(2):
+            d = fx[case.name, k, None]
+            assert (d["kernel"], d["reason"]) == ("latency", "no_tile") and int(d["request"].split()[2]) >= 8192, (case.name, k)
+    for case in g.SHORT:
+        d = fx[case.name, 0, None]
+        assert (d["kernel"], d["reason"]) == ("latency", "short") and 2000 < int(d["request"].split()[2]) < 8192, case.name
+    assert sorted((c.streams[0][0], c.streams[0][1].taps()) for c in g.SHORT if c.entry == "host") == [(n, t) for n in (1, 2, 3, 16) for t in (16, 128)]
+    assert [(c.bits, c.streams[0][0]) for c in g.SHORT if c.entry == "pcm"] == [(24, 2)]
+    for i in g.SWITCHED:
+        assert [fx[g.TILED[i].name, k, "switched"]["reason"] for k in range(3)] == ["switched_off"] * 3
+    assert [g.TILED_BUILDS[i][:2] for i in g.SWITCHED] == [(2, 1), (0, 1)] and g.TILED[g.SWITCHED[1]].streams[0][0] == 3
+    assert build(fx[g.RUNS.name, 0, None]) == (2, 1, 4096) and g.RUNS.chunk == 8

@@ -546,3 +546,111 @@ def test_a_lockstep_step_defect_fails_the_gate_of_its_family(family, name):
     if name.startswith("the last tap") and family != "lockstep_step_ref":
         assert old_rms <= OLD_RMS_GATE
     assert r_rms > max(m_rms, R.M_RMS_CAP) and r_max > max(m_max, R.M_MAX_CAP), (r_rms, r_max, R.MARGINS[family])
+
+
+# ---- the gate of tests/test_fir_generic_builds_gpu.py can fail -------------------------------------------------------------------
+GENERIC_DEFECTS = ["a tile's last partial pass takes the meta of the tile's first sorted output",
+                   "the last float4 chunk of both rows is dropped at 16 taps on every output of one phase row",
+                   "one tile's window is staged one frame late",
+                   "the one-channel stream of a {2, 1, 3} batch is indexed with the widest stream's channel count"]
+DEFECT_ROW = 5          # the phase row whose outputs lose their last float4 chunk
+
+
+def generic_defect_case(name):
+    """(module, case, stream, launch): the smallest tiled case -- the fewest values in its first launch --, for the 16-tap defect the
+    smallest one at 16 taps, for the batch defect the one-channel stream of the {2, 1, 3} batch; the first launch of each."""
+    import test_fir_generic_builds_gpu as g
+    if name.startswith("the one-channel stream"):
+        return g, g.BATCHES[0], 1, 0
+    cases = [c for c in g.TILED if c.streams[0][1].taps() == 16] if "16 taps" in name else g.TILED
+    return g, min(cases, key=lambda c: g.produced_frames(c.streams[0], c.lens[0], c.chunk)[0] * c.streams[0][0]), 0, 0
+
+
+def generic_defect(g, case, stream, launch, name):
+    """The f64 evaluation of one launch of one stream with one defect of the tiled kernel, as the GPU test gates it."""
+    d = g.case_data(case)[stream]
+    la, x, coeffs = d["launches"][launch], d["x"], d["coeffs"]
+    ch, taps = case.streams[stream][0], case.streams[stream][1].taps()
+    pos, n_out = la.pos, len(la.pos)
+    fx = g.fixture()[case.name, launch, None]
+    assert fx["kernel"] == "tiled"
+    tile = fx["tile"]
+    n0 = (n_out - 1) // tile * tile          # the last tile: partial and small
+    nt = n_out - n0
+    assert 0 < nt < 512
+    if name == GENERIC_DEFECTS[0]:
+        order = n0 + np.argsort(pos.phase1[n0:], kind="stable")       # the tile's outputs by phase row
+        per_wave = ((nt + 15) // 16 + 7) & ~7
+        late = []
+        for begin in range(0, nt, per_wave):
+            end = min(begin + per_wave, nt)
+            late += list(order[begin + (end - begin) // 8 * 8:end])   # the outputs of the wave's last pass, where it is partial
+        assert late and order[0] not in late
+        q = copy.copy(pos)
+        q.index, q.phase1, q.phase2, q.frac = pos.index.copy(), pos.phase1.copy(), pos.phase2.copy(), pos.frac.copy()
+        for field in (q.index, q.phase1, q.phase2, q.frac):
+            field[late] = field[order[0]]
+        return R.fir_f64(x, ch, coeffs, q), la
+    if name == GENERIC_DEFECTS[1]:
+        assert taps == 16
+        k = np.nonzero(pos.phase1 == DEFECT_ROW)[0]
+        assert k.size >= 1
+        y = la.ref.reshape(-1, ch).copy()
+        f = pos.frac[k]
+        xs = x.reshape(-1, ch).astype(np.float64)
+        for t in range(12, 16):
+            w = (np.float32(1.0) - f).astype(np.float64) * coeffs[pos.phase1[k], t] + f.astype(np.float64) * coeffs[pos.phase2[k], t]
+            y[k] -= w[:, None] * xs[pos.index[k] + t]
+        return y.reshape(-1), la
+    if name == GENERIC_DEFECTS[2]:
+        q = copy.copy(pos)
+        q.index = pos.index.copy()
+        q.index[n0:] += 1
+        return R.fir_f64(x, ch, coeffs, q), la
+    assert name == GENERIC_DEFECTS[3] and ch == 1
+    widest = max(s[0] for s in case.streams)
+    xs = x.astype(np.float64)
+    w0 = pos.index[np.arange(n_out) // tile * tile]                   # the window start of every output's tile
+    idx = np.minimum(w0[:, None] + widest * (pos.index[:, None] - w0[:, None] + np.arange(taps)[None, :]), xs.size - 1)
+    c64 = coeffs.astype(np.float64)
+    s1, s2 = np.sum(c64[pos.phase1] * xs[idx], axis=1), np.sum(c64[pos.phase2] * xs[idx], axis=1)
+    f = pos.frac
+    return s1 * (np.float32(1.0) - f).astype(np.float64) + s2 * f.astype(np.float64), la
+
+
+def test_a_clean_f32_result_passes_the_generic_gate():
+    """The f64 sums of the smallest tiled case's first launch rounded to f32 pass at the family's margins."""
+    g, case, stream, launch = generic_defect_case(GENERIC_DEFECTS[0])
+    la = g.case_data(case)[stream]["launches"][launch]
+    m_rms, m_max = R.MARGINS["fir_generic"]
+    r_rms, r_max = R.budget(la.ref.astype(np.float32), la.ref, la.yard)
+    print(f"fir_generic {case.name}: the f64 sums as f32 x{r_rms:.3f} rms, x{r_max:.3f} max")
+    assert r_rms <= min(1.0, m_rms) and r_max <= min(1.0, m_max), (r_rms, r_max)
+    assert R.budget(la.yard, la.ref, la.yard) == (1.0, 1.0)
+
+
+@pytest.mark.parametrize("name", GENERIC_DEFECTS)
+def test_a_tiled_kernel_defect_fails_the_generic_gate(name):
+    """Each defect applied to the f64 evaluation of one launch -- the first, tiled, launch of the smallest case it can occur in -- and
+    the result rounded to f32: a kernel whose ONLY fault is the defect, gated as tests/test_fir_generic_builds_gpu.py gates a launch.
+    The tile is the fixture's; the partial pass, the late window and nothing else are in the launch's last tile, which has fewer
+    than 512 outputs.  Every defect fails both bounds of "fir_generic" and both caps.
+    Measured (values changed; RMS against the scalar oracle; then RMS and max against f64 in multiples of the oracle's distance):
+      1 ch 48000 -> 44101 Hz, 128 taps, 8201 values, last tile of 9 outputs
+        partial pass on the first output's meta      1    1.13e-2     x1.2e5    x1.3e6
+        window staged one frame late                 9    1.95e-2     x2.1e5    x1.2e6
+      2 ch 44100 -> 48001 Hz, 16 taps, 16404 values, phase row 5
+        last float4 chunk dropped                   18    1.76e-4     x5.3e3    x3.0e4
+      {2, 1, 3}-channel batch, the one-channel stream, 8202 values
+        indexed with three channels               8202    8.02e-1     x8.5e6    x4.2e6"""
+    g, case, stream, launch = generic_defect_case(name)
+    y, la = generic_defect(g, case, stream, launch, name)
+    y = y.astype(np.float32)
+    changed = int(np.count_nonzero(y != la.ref.astype(np.float32)))
+    old_rms, old_max = R.errors(y, la.yard)
+    r_rms, r_max = R.budget(y, la.ref, la.yard)
+    print(f"fir_generic {case.name} stream {stream} ({la.ref.size} values) {name}: {changed} values changed; against the oracle {old_rms:.3e} "
+          f"(max {old_max:.3e}); against f64 x{r_rms:.3g} rms, x{r_max:.3g} max")
+    assert changed > 0
+    m_rms, m_max = R.MARGINS["fir_generic"]
+    assert r_rms > max(m_rms, R.M_RMS_CAP) and r_max > max(m_max, R.M_MAX_CAP), (r_rms, r_max, R.MARGINS["fir_generic"])
