@@ -121,6 +121,13 @@ extern "C" {
     fn rsmp_f32_to_pcm_gain_device(d_in: *const f32, n_values: usize, bits: c_int, gain: f32, dither: c_int, seed: u64, first_index: u64,
                                    d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats, stream: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_pcm_normalise_gain(stats: *const PcmStats, target_peak: f32, gain: *mut f32) -> c_int;
+    fn rsmp_fir_set_pcm_dither_shape(r: *mut rsmp_fir, shape: c_int) -> c_int;
+    fn rsmp_fir_pcm_dither_shape(r: *const rsmp_fir, shape: *mut c_int) -> c_int;
+    fn rsmp_f32_to_pcm_shaped(input: *const f32, n_values: usize, bits: c_int, gain: f32, dither: c_int, shape: c_int, channels: u32, seed: u64,
+                              first_index: u64, out_pcm: *mut std::os::raw::c_void, stats: *mut PcmStats) -> c_int;
+    fn rsmp_f32_to_pcm_shaped_device(d_in: *const f32, n_values: usize, bits: c_int, gain: f32, dither: c_int, shape: c_int, channels: u32, seed: u64,
+                                     first_index: u64, d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats,
+                                     stream: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_fir_set_pcm_stats(r: *mut rsmp_fir, enable: c_int) -> c_int;
     fn rsmp_fir_pcm_stats(r: *mut rsmp_fir, stats: *mut PcmStats) -> c_int;
     fn rsmp_fir_pcm_stats_clear(r: *mut rsmp_fir) -> c_int;
@@ -133,6 +140,8 @@ extern "C" {
                                                    stream: *mut std::os::raw::c_void) -> c_int;
     fn rsmp_fft_set_pcm_dither(r: *mut rsmp_fft, dither: c_int, seed: u64) -> c_int;
     fn rsmp_fft_pcm_dither(r: *const rsmp_fft, dither: *mut c_int, seed: *mut u64) -> c_int;
+    fn rsmp_fft_set_pcm_dither_shape(r: *mut rsmp_fft, shape: c_int) -> c_int;
+    fn rsmp_fft_pcm_dither_shape(r: *const rsmp_fft, shape: *mut c_int) -> c_int;
     fn rsmp_fft_set_pcm_gain(r: *mut rsmp_fft, gain: f32) -> c_int;
     fn rsmp_fft_pcm_gain(r: *const rsmp_fft, gain: *mut f32) -> c_int;
     fn rsmp_fft_set_pcm_stats(r: *mut rsmp_fft, enable: c_int) -> c_int;
@@ -269,6 +278,18 @@ impl ResamplerFir {
     pub fn set_pcm_gain(&mut self, gain: f32) -> Result<(), ResampleError> {
         status(unsafe { rsmp_fir_set_pcm_gain(self.handle, gain) })
     }
+    /// Shape of the TPDF dither of the PCM the fused entry writes for this stream (rsmp_fir_set_pcm_dither_shape): white (the
+    /// default) or high-pass; the bytes are `f32_to_pcm_shaped_device`'s of the f32 output.  A setting like the dither mode, read
+    /// only under `Dither::Tpdf`; one shape for all the streams of a batch.
+    pub fn set_pcm_dither_shape(&mut self, shape: DitherShape) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fir_set_pcm_dither_shape(self.handle, shape as c_int) })
+    }
+    /// The shape as `set_pcm_dither_shape` left it.
+    pub fn pcm_dither_shape(&self) -> DitherShape {
+        let mut v: c_int = 0;
+        unsafe { rsmp_fir_pcm_dither_shape(self.handle, &mut v) };
+        if v == 1 { DitherShape::Highpass } else { DitherShape::White }
+    }
     /// The gain as `set_pcm_gain` left it.
     pub fn pcm_gain(&self) -> f32 {
         let mut g = 1.0f32;
@@ -323,6 +344,12 @@ impl PcmStats {
 #[repr(C)]
 pub enum Dither { None = 0, Tpdf = 1 }
 
+/// Spectral shape of the TPDF noise (RSMP_DITHER_SHAPE_*): white, or high-pass -- the difference of consecutive values of one uniform
+/// sequence per channel: nothing at DC, twice the white level at Nyquist, the same variance.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(C)]
+pub enum DitherShape { White = 0, Highpass = 1 }
+
 /// Addition to the reference API: f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host; the library's quantiser --
 /// round half to even of x * 2^(bits-1), saturated to the code range, NaN -> 0; without dither (`f32_to_pcm_dither` adds it).
 pub fn f32_to_pcm(input: &[f32], bits: u32) -> Result<Vec<u8>, ResampleError> {
@@ -366,6 +393,26 @@ pub fn f32_to_pcm_gain(input: &[f32], bits: u32, gain: f32, dither: Dither, seed
 pub unsafe fn f32_to_pcm_gain_device(d_in: *const f32, n_values: usize, bits: u32, gain: f32, dither: Dither, seed: u64, first_index: u64,
                                      d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats) -> Result<(), ResampleError> {
     status(rsmp_f32_to_pcm_gain_device(d_in, n_values, bits as c_int, gain, dither as c_int, seed, first_index, d_pcm, d_stats, std::ptr::null_mut()))
+}
+/// `f32_to_pcm_gain` with a shape of the TPDF noise and the channel count of the interleaved buffer (rsmp_f32_to_pcm_shaped,
+/// include/resampler_amd.h): with `DitherShape::Highpass` value i takes f32(r1(i) - r1(i - channels)) * 2^-16, the index wrapping in 64
+/// bits.  What the fused PCM stores do for a handle with `set_pcm_dither_shape(shape)`.
+pub fn f32_to_pcm_shaped(input: &[f32], bits: u32, gain: f32, dither: Dither, shape: DitherShape, channels: u32, seed: u64,
+                         first_index: u64) -> Result<(Vec<u8>, PcmStats), ResampleError> {
+    let mut out = vec![0u8; input.len() * (bits as usize / 8)];
+    let mut st = PcmStats::default();
+    status(unsafe {
+        rsmp_f32_to_pcm_shaped(input.as_ptr(), input.len(), bits as c_int, gain, dither as c_int, shape as c_int, channels, seed, first_index,
+                               out.as_mut_ptr() as *mut std::os::raw::c_void, &mut st)
+    })
+    .map(|_| (out, st))
+}
+/// The same on device pointers (rsmp_f32_to_pcm_shaped_device; `d_stats` may be null), on the null stream.
+pub unsafe fn f32_to_pcm_shaped_device(d_in: *const f32, n_values: usize, bits: u32, gain: f32, dither: Dither, shape: DitherShape, channels: u32,
+                                       seed: u64, first_index: u64, d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats)
+                                       -> Result<(), ResampleError> {
+    status(rsmp_f32_to_pcm_shaped_device(d_in, n_values, bits as c_int, gain, dither as c_int, shape as c_int, channels, seed, first_index, d_pcm,
+                                         d_stats, std::ptr::null_mut()))
 }
 /// The gain that brings a first pass's peak to `target_peak` in a second pass (rsmp_pcm_normalise_gain): target_peak / stats.peak.
 pub fn normalise_gain(stats: &PcmStats, target_peak: f32) -> Result<f32, ResampleError> {
@@ -455,6 +502,18 @@ impl ResamplerFft {
     /// 2^-32 <= |gain| <= 2^32, negative for a polarity flip -- anything else is an error and changes nothing.
     pub fn set_pcm_gain(&mut self, gain: f32) -> Result<(), ResampleError> {
         status(unsafe { rsmp_fft_set_pcm_gain(self.handle, gain) })
+    }
+    /// Shape of the TPDF dither of the PCM the fused entry writes for this stream (rsmp_fft_set_pcm_dither_shape): white (the
+    /// default) or high-pass; the bytes are `f32_to_pcm_shaped_device`'s of the f32 output.  A setting like the dither mode, read
+    /// only under `Dither::Tpdf`; one shape for all the streams of a batch.
+    pub fn set_pcm_dither_shape(&mut self, shape: DitherShape) -> Result<(), ResampleError> {
+        status(unsafe { rsmp_fft_set_pcm_dither_shape(self.handle, shape as c_int) })
+    }
+    /// The shape as `set_pcm_dither_shape` left it.
+    pub fn pcm_dither_shape(&self) -> DitherShape {
+        let mut v: c_int = 0;
+        unsafe { rsmp_fft_pcm_dither_shape(self.handle, &mut v) };
+        if v == 1 { DitherShape::Highpass } else { DitherShape::White }
     }
     /// The gain as `set_pcm_gain` left it.
     pub fn pcm_gain(&self) -> f32 {

@@ -91,6 +91,10 @@ enum { RSMP_FIR_KERNEL_AUTO = 0, RSMP_FIR_KERNEL_GENERIC = 1, RSMP_FIR_KERNEL_PE
 /* Dither of PCM output (no counterpart in the reference, which writes f32): none, or triangular noise of +-1 LSB added before
  * rounding -- the rule is stated at rsmp_f32_to_pcm_dither. */
 enum { RSMP_DITHER_NONE = 0, RSMP_DITHER_TPDF = 1 };
+/* Spectral shape of the TPDF noise (read only with RSMP_DITHER_TPDF): white -- the noise rsmp_f32_to_pcm_dither states --, or
+ * high-pass: the difference of two consecutive values of ONE uniform sequence per channel, zero at DC and doubled at Nyquist --
+ * the rule is stated at rsmp_f32_to_pcm_shaped.  No error feedback anywhere: the noise stays a function of the seed and the index. */
+enum { RSMP_DITHER_SHAPE_WHITE = 0, RSMP_DITHER_SHAPE_HIGHPASS = 1 };
 
 const char* rsmp_last_error(void);          /* thread-local message of the last failing call */
 int rsmp_device_count(void);                /* number of HIP devices, 0 when there is none   */
@@ -242,6 +246,17 @@ int rsmp_fir_batch_resample_bulk_pcm_out_device(rsmp_fir* const* rs, size_t n, c
  * changed --; the seeds are per stream.  rsmp_fir_pcm_dither reads the setting back (either pointer may be NULL). */
 int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed);
 int rsmp_fir_pcm_dither(const rsmp_fir* r, int* dither, uint64_t* seed);
+/* Shape of that dither: RSMP_DITHER_SHAPE_WHITE (the default: the bytes of a handle that never set it) or
+ * RSMP_DITHER_SHAPE_HIGHPASS; anything else, or a null handle, is RSMP_ERR_INVALID_ARGUMENT and the setting stays.  A setting like
+ * the dither mode: it survives rsmp_fir_reset and rsmp_fir_seek, and only a PCM-output launch whose dither mode is RSMP_DITHER_TPDF
+ * reads it -- with RSMP_DITHER_NONE it has no effect.  The bytes, and with statistics on the totals, are exactly
+ * rsmp_f32_to_pcm_shaped_device's (below) of the f32 entry's output with the handle's gain, dither, shape and seed, the stream's
+ * `channels` and first_index = abs_out * channels: the first frame after a reset draws its earlier value from the wrapped index
+ * 2^64 - channels + c, and a chunk the repair pass rewrites gets the noise it had.  One shape for all the streams of a batch, as the
+ * dither mode and out_bits -- a mix is RSMP_ERR_INVALID_ARGUMENT before any launch: nothing written, no state changed, nothing
+ * counted --; seeds and gains stay per stream.  rsmp_fir_pcm_dither_shape reads the setting back (null: RSMP_ERR_INVALID_ARGUMENT). */
+int rsmp_fir_set_pcm_dither_shape(rsmp_fir* r, int shape);
+int rsmp_fir_pcm_dither_shape(const rsmp_fir* r, int* shape);
 /* Output gain of the PCM that entry writes for this handle, folded into the factor its stores multiply by anyway -- the rule is
  * rsmp_f32_to_pcm_gain's (below), and the bytes are exactly rsmp_f32_to_pcm_gain_device's of the f32 entry's output with the
  * handle's gain, dither, seed and first_index = abs_out * channels.  A setting, not state: the default is 1 (the bytes of a handle
@@ -475,8 +490,8 @@ int rsmp_pcm_to_stereo_f32_device(const void* d_pcm, int bits, int channels, siz
 /* The way back, f32 -> little-endian integer PCM of `bits` (16, packed 24, 32), n_values * bits / 8 bytes:
  *   q = saturate(round_half_to_even(x * 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1),  NaN -> 0.
  * The product is exact (a power of two); +inf and everything above the range give the top code, -inf and everything below the
- * bottom one, -0.0 and denormals 0; +1.0 saturates to the top code.  No dither here (rsmp_f32_to_pcm_dither below), no noise
- * shaping.  Decoding with
+ * bottom one, -0.0 and denormals 0; +1.0 saturates to the top code.  No dither here (rsmp_f32_to_pcm_dither below; its high-pass
+ * form: rsmp_f32_to_pcm_shaped), no error-feedback noise shaping.  Decoding with
  * rsmp_pcm_to_stereo_f32_device and quantising again at the same width is the identity on every 16-bit and 24-bit code.  At 32
  * bits it is NOT: the reference decodes 32-bit files with the divisor -2^31 (resample/src/main.rs:131), the scale here is
  * +2^31 -- an f32 value means what it says --, so that round trip gives saturate(-f32(s)): polarity inverted, the bottom code
@@ -494,7 +509,8 @@ int rsmp_f32_to_pcm_device(const float* d_in, size_t n_values, int bits, void* d
  *   z = (z ^ z >> 27) * 0x94D049BB133111EB;          w = z ^ z >> 31;
  *   h = low 32 bits of w for even i, high 32 bits for odd i;  r1 = h & 0xFFFF, r2 = h >> 16;  d = f32(r1 - r2) * 2^-16
  * -- the difference of two uniform 16-bit numbers: triangular on (-1, 1) LSB, variance 1/6, the usual TPDF dither; the error
- * of the result has mean zero and a variance that does not depend on the signal.  One mix serves two consecutive values, one
+ * of the result has mean zero and a variance that does not depend on the signal.  This noise is spectrally white; its high-pass
+ * form, with the same density and variance, is RSMP_DITHER_SHAPE_HIGHPASS (rsmp_f32_to_pcm_shaped).  One mix serves two consecutive values, one
  * two-channel frame.  Converting a buffer in pieces, each with first_index advanced by the values before it, gives the bytes of
  * one call.  Unknown modes are RSMP_ERR_INVALID_ARGUMENT.  Host / device versions, pointers and alignment as above. */
 int rsmp_f32_to_pcm_dither(const float* in, size_t n_values, int bits, int dither, uint64_t seed, uint64_t first_index,
@@ -542,6 +558,27 @@ int rsmp_f32_to_pcm_gain(const float* in, size_t n_values, int bits, float gain,
                          void* out_pcm, rsmp_pcm_stats* stats);
 int rsmp_f32_to_pcm_gain_device(const float* d_in, size_t n_values, int bits, float gain, int dither, uint64_t seed,
                                 uint64_t first_index, void* d_pcm, rsmp_pcm_stats* d_stats, void* stream);
+/* rsmp_f32_to_pcm_gain with a shape of the TPDF noise (RSMP_DITHER_SHAPE_*) and the channel count of the interleaved buffer:
+ * what the fused PCM stores do under rsmp_fir_set_pcm_dither_shape / rsmp_fft_set_pcm_dither_shape.  With h(seed, i) the 32 bits
+ * rsmp_f32_to_pcm_dither gives value i, r1(i) = h & 0xFFFF and r2(i) = h >> 16:
+ *   RSMP_DITHER_SHAPE_WHITE     d = f32(r1(i) - r2(i)) * 2^-16             -- unchanged: bytes and statistics are
+ *                                                                             rsmp_f32_to_pcm_gain's for every input;
+ *   RSMP_DITHER_SHAPE_HIGHPASS  d = f32(r1(i) - r1(i - channels)) * 2^-16  -- i - channels wraps in 64 bits: value i < channels
+ *                                                                             draws from index 2^64 - channels + i.
+ * Value j of the call has index i = first_index + j and belongs to channel i % channels; only the lag depends on `channels`
+ * (>= 1).  The high-pass noise is u[n] - u[n-1] of one uniform sequence per channel: the same triangular density on (-1, 1) LSB
+ * and the same variance 1/6 as white, the error's first two moments independent of the signal, consecutive values of a channel
+ * correlated by -1/2 and no others, so that the noise power follows 1 - cos(w) times the white level: nothing at DC, twice the
+ * white level at Nyquist, 0.0064 of it in the lowest sixteenth of the band.  No error feedback: the noise has no state, and
+ * converting a buffer in pieces, each with first_index advanced by the values before it, gives the bytes of one call -- pieces may
+ * end inside a frame.  Everything around d -- k, the one rounding of x * k, the one f32 addition, rounding, saturation, NaN, the
+ * statistics -- is rsmp_f32_to_pcm_gain's; with RSMP_DITHER_NONE the shape has no effect (it must still be a known one).
+ * Pointers, alignment, NULL stats / out_pcm and the merged device statistics as rsmp_f32_to_pcm_gain[_device].  Unknown bits,
+ * dither or shape, channels == 0, a gain outside the range: RSMP_ERR_INVALID_ARGUMENT, nothing written. */
+int rsmp_f32_to_pcm_shaped(const float* in, size_t n_values, int bits, float gain, int dither, int shape, uint32_t channels,
+                           uint64_t seed, uint64_t first_index, void* out_pcm, rsmp_pcm_stats* stats);
+int rsmp_f32_to_pcm_shaped_device(const float* d_in, size_t n_values, int bits, float gain, int dither, int shape, uint32_t channels,
+                                  uint64_t seed, uint64_t first_index, void* d_pcm, rsmp_pcm_stats* d_stats, void* stream);
 /* The gain that brings a first pass's peak to target_peak in a second pass: *gain = f32(target_peak / stats->peak).
  * RSMP_ERR_INVALID_ARGUMENT, *gain untouched, when the peak is 0 or not finite, when the result is no accepted gain, or for a null
  * pointer.  The second pass's peak is target_peak to within two f32 roundings (the quotient and the product). */
@@ -618,6 +655,12 @@ int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, size_t n, c
  * pointer may be NULL). */
 int rsmp_fft_set_pcm_dither(rsmp_fft* r, int dither, uint64_t seed);
 int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* seed);
+/* Shape of that dither: rsmp_fir_set_pcm_dither_shape's twin, the rule rsmp_f32_to_pcm_shaped's with channels = 2 and
+ * first_index = abs_out * 2.  Default RSMP_DITHER_SHAPE_WHITE; read only by a PCM-output launch whose dither mode is
+ * RSMP_DITHER_TPDF; one shape for all the streams of a batch (a mix: RSMP_ERR_INVALID_ARGUMENT before any launch); an unknown shape
+ * or a null handle is RSMP_ERR_INVALID_ARGUMENT and the setting stays. */
+int rsmp_fft_set_pcm_dither_shape(rsmp_fft* r, int shape);
+int rsmp_fft_pcm_dither_shape(const rsmp_fft* r, int* shape);
 /* Output gain of the PCM that entry writes for this handle: rsmp_fir_set_pcm_gain's twin, the rule rsmp_f32_to_pcm_gain's.  The
  * bytes are exactly rsmp_f32_to_pcm_gain_device's of the f32 entry's output with the handle's gain, dither, seed and
  * first_index = abs_out * 2; with statistics on, the totals describe the gained values.  A setting with default 1, per stream

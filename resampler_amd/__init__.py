@@ -89,6 +89,13 @@ class Dither(enum.IntEnum):
     TPDF = 1
 
 
+class DitherShape(enum.IntEnum):
+    """Spectral shape of the TPDF noise (RSMP_DITHER_SHAPE_*): white, or high-pass -- the difference of consecutive values of one
+    uniform sequence per channel, nothing at DC and twice the white level at Nyquist (rsmp_f32_to_pcm_shaped)."""
+    WHITE = 0
+    HIGHPASS = 1
+
+
 class PcmStats(C.Structure):
     """What a PCM writer did to the values it was given (rsmp_pcm_stats, 32 bytes): how many it quantised, how many of them lay
     outside the code range and were saturated, how many were NaN (stored as 0, not clipped), and the largest |x| of the others
@@ -146,6 +153,8 @@ _SIGNATURES = [
     ("rsmp_fir_set_profiling", C.c_int, [C.c_void_p, C.c_int]),
     ("rsmp_fir_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("rsmp_fir_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("rsmp_fir_set_pcm_dither_shape", C.c_int, [C.c_void_p, C.c_int]),
+    ("rsmp_fir_pcm_dither_shape", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rsmp_fir_set_pcm_gain", C.c_int, [C.c_void_p, C.c_float]),
     ("rsmp_fir_pcm_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rsmp_fir_set_pcm_stats", C.c_int, [C.c_void_p, C.c_int]),
@@ -223,6 +232,10 @@ _SIGNATURES = [
     ("rsmp_f32_to_pcm_stats_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rsmp_f32_to_pcm_gain", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(PcmStats)]),
     ("rsmp_f32_to_pcm_gain_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rsmp_f32_to_pcm_shaped", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                                         C.POINTER(PcmStats)]),
+    ("rsmp_f32_to_pcm_shaped_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     ("rsmp_pcm_normalise_gain", C.c_int, [C.POINTER(PcmStats), C.c_float, C.POINTER(C.c_float)]),
     ("rsmp_device_stream_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rsmp_fft_new", C.c_void_p, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
@@ -252,6 +265,8 @@ _SIGNATURES = [
      [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, _szp, C.c_void_p]),
     ("rsmp_fft_set_pcm_dither", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("rsmp_fft_pcm_dither", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("rsmp_fft_set_pcm_dither_shape", C.c_int, [C.c_void_p, C.c_int]),
+    ("rsmp_fft_pcm_dither_shape", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rsmp_fft_set_pcm_gain", C.c_int, [C.c_void_p, C.c_float]),
     ("rsmp_fft_pcm_gain", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rsmp_fft_set_pcm_stats", C.c_int, [C.c_void_p, C.c_int]),
@@ -445,6 +460,18 @@ class ResamplerFir:
         d, sd = C.c_int(), C.c_uint64()
         _check(lib().rsmp_fir_pcm_dither(self._h, C.byref(d), C.byref(sd)))
         return d.value, sd.value
+
+    def set_pcm_dither_shape(self, shape: int) -> None:
+        """Shape of that dither (rsmp_fir_set_pcm_dither_shape): DitherShape.WHITE (the default) or DitherShape.HIGHPASS.  A setting
+        like the mode, read only by a PCM-output launch under Dither.TPDF; one shape for all the streams of a batch.
+        f32_to_pcm_device(..., dither, seed, first_index, gain, shape=shape, channels=channels) of the f32 output gives the same bytes."""
+        _check(lib().rsmp_fir_set_pcm_dither_shape(self._h, int(shape)))
+
+    def pcm_dither_shape(self) -> int:
+        """The shape as set_pcm_dither_shape left it."""
+        v = C.c_int()
+        _check(lib().rsmp_fir_pcm_dither_shape(self._h, C.byref(v)))
+        return v.value
 
     def set_pcm_gain(self, gain: float) -> None:
         """Output gain of the PCM that FirBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fir_set_pcm_gain), folded
@@ -914,6 +941,18 @@ class ResamplerFft:
         _check(lib().rsmp_fft_pcm_dither(self._h, C.byref(d), C.byref(s)))
         return d.value, s.value
 
+    def set_pcm_dither_shape(self, shape: int) -> None:
+        """Shape of that dither (rsmp_fft_set_pcm_dither_shape): DitherShape.WHITE (the default) or DitherShape.HIGHPASS.  A setting
+        like the mode, read only by a PCM-output launch under Dither.TPDF; one shape for all the streams of a batch.
+        f32_to_pcm_device(..., dither, seed, first_index, gain, shape=shape, channels=channels) of the f32 output gives the same bytes."""
+        _check(lib().rsmp_fft_set_pcm_dither_shape(self._h, int(shape)))
+
+    def pcm_dither_shape(self) -> int:
+        """The shape as set_pcm_dither_shape left it."""
+        v = C.c_int()
+        _check(lib().rsmp_fft_pcm_dither_shape(self._h, C.byref(v)))
+        return v.value
+
     def set_pcm_gain(self, gain: float) -> None:
         """Output gain of the PCM that FftBatch.resample_bulk_pcm_out_device writes for this stream (rsmp_fft_set_pcm_gain):
         ResamplerFir.set_pcm_gain's twin -- a setting, default 1, per stream, read by the PCM-output entry alone."""
@@ -1035,15 +1074,19 @@ def pcm_to_stereo_f32_device(d_pcm, bits: int, channels: int, d_out, stream: Opt
                                                C.c_void_p(d_out.data_ptr()), C.c_void_p(stream or 0)))
 
 
-def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, gain: float = 1.0) -> bytes:
+def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, gain: float = 1.0, shape: int = 0, channels: int = 1) -> bytes:
     """f32 -> little-endian PCM of `bits` (16 / packed 24 / 32) on the host, no device needed (rsmp_f32_to_pcm[_dither]): the
     library's quantiser -- round half to even of x * 2^(bits-1), saturated, NaN -> 0.  dither = Dither.TPDF: value j takes, before
     the rounding, the triangular noise of (seed, first_index + j) -- the rule is stated at rsmp_f32_to_pcm_dither.  gain other than
     1: the quantiser under an output gain (rsmp_f32_to_pcm_gain: x * (gain * 2^(bits-1)) in one rounding), what the fused PCM stores
-    do for a handle with set_pcm_gain(gain)."""
+    do for a handle with set_pcm_gain(gain).  shape other than DitherShape.WHITE, or channels other than 1: rsmp_f32_to_pcm_shaped --
+    with DitherShape.HIGHPASS value j takes the noise of its index against the value `channels` indices earlier."""
     a = _np_f32(x).reshape(-1)
     out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8)
-    if gain != 1.0:
+    if shape != 0 or channels != 1:
+        _check(lib().rsmp_f32_to_pcm_shaped(C.c_void_p(a.ctypes.data), a.size, bits, float(gain), int(dither), int(shape), int(channels), int(seed) & _U64,
+                                            int(first_index) & _U64, C.c_void_p(out.ctypes.data), None))
+    elif gain != 1.0:
         _check(lib().rsmp_f32_to_pcm_gain(C.c_void_p(a.ctypes.data), a.size, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
                                           C.c_void_p(out.ctypes.data), None))
     elif dither == 0:
@@ -1055,13 +1098,16 @@ def f32_to_pcm(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 
 
 
 def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None, dither: int = 0, seed: int = 0, first_index: int = 0,
-                      gain: float = 1.0) -> None:
+                      gain: float = 1.0, shape: int = 0, channels: int = 1) -> None:
     """The same on HBM-resident torch tensors (rsmp_f32_to_pcm[_dither]_device): d_in = float32, d_pcm = uint8 with room for
     d_in.numel() * bits / 8 bytes, 4-byte aligned; exactly those bytes are written.  gain other than 1: rsmp_f32_to_pcm_gain_device."""
     n = d_in.numel()
     if bits in (16, 24, 32):
         assert d_pcm.numel() >= n * (bits // 8)
-    if gain != 1.0:
+    if shape != 0 or channels != 1:   # (rsmp_f32_to_pcm_shaped_device)
+        _check(lib().rsmp_f32_to_pcm_shaped_device(C.c_void_p(_dev_ptr(d_in)), n, bits, float(gain), int(dither), int(shape), int(channels), int(seed) & _U64,
+                                                   int(first_index) & _U64, C.c_void_p(d_pcm.data_ptr()), None, C.c_void_p(stream or 0)))
+    elif gain != 1.0:
         _check(lib().rsmp_f32_to_pcm_gain_device(C.c_void_p(_dev_ptr(d_in)), n, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
                                                  C.c_void_p(d_pcm.data_ptr()), None, C.c_void_p(stream or 0)))
     elif dither == 0:
@@ -1071,13 +1117,18 @@ def f32_to_pcm_device(d_in, bits: int, d_pcm, stream: Optional[int] = None, dith
                                                    C.c_void_p(d_pcm.data_ptr()), C.c_void_p(stream or 0)))
 
 
-def f32_to_pcm_stats(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, want_pcm: bool = True, gain: float = 1.0):
+def f32_to_pcm_stats(x, bits: int, dither: int = 0, seed: int = 0, first_index: int = 0, want_pcm: bool = True, gain: float = 1.0,
+                     shape: int = 0, channels: int = 1):
     """f32_to_pcm that also says what it did (rsmp_f32_to_pcm_stats, host, no device needed: the definition of the statistics):
     returns (bytes, PcmStats) -- the bytes are f32_to_pcm's with the same arguments; (None, PcmStats) with want_pcm = False
     (out_pcm = NULL: measure only).  gain other than 1: rsmp_f32_to_pcm_gain, whose statistics describe the gained values."""
     a = _np_f32(x).reshape(-1)
     out = np.empty(a.size * (bits // 8) if bits in (16, 24, 32) else 0, np.uint8) if want_pcm else None
     st = PcmStats()
+    if shape != 0 or channels != 1:   # (rsmp_f32_to_pcm_shaped)
+        _check(lib().rsmp_f32_to_pcm_shaped(C.c_void_p(a.ctypes.data), a.size, bits, float(gain), int(dither), int(shape), int(channels), int(seed) & _U64,
+                                            int(first_index) & _U64, C.c_void_p(out.ctypes.data) if want_pcm else None, C.byref(st)))
+        return (out.tobytes() if want_pcm else None), st
     if gain != 1.0:
         _check(lib().rsmp_f32_to_pcm_gain(C.c_void_p(a.ctypes.data), a.size, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
                                           C.c_void_p(out.ctypes.data) if want_pcm else None, C.byref(st)))
@@ -1088,7 +1139,7 @@ def f32_to_pcm_stats(x, bits: int, dither: int = 0, seed: int = 0, first_index: 
 
 
 def f32_to_pcm_stats_device(d_in, bits: int, d_pcm, d_stats, stream: Optional[int] = None, dither: int = 0, seed: int = 0,
-                            first_index: int = 0, gain: float = 1.0) -> None:
+                            first_index: int = 0, gain: float = 1.0, shape: int = 0, channels: int = 1) -> None:
     """The same on HBM-resident torch tensors (rsmp_f32_to_pcm_stats_device): d_pcm as f32_to_pcm_device's, or None to measure only;
     d_stats = a tensor of 32 bytes, 8-byte aligned, that the caller zeroed -- the call's statistics are MERGED into it, so a buffer
     converted in pieces accumulates one result (PcmStats.from_tensor reads it).  gain other than 1: rsmp_f32_to_pcm_gain_device."""
@@ -1096,6 +1147,11 @@ def f32_to_pcm_stats_device(d_in, bits: int, d_pcm, d_stats, stream: Optional[in
     if d_pcm is not None and bits in (16, 24, 32):
         assert d_pcm.numel() >= n * (bits // 8)
     assert d_stats.numel() * d_stats.element_size() >= C.sizeof(PcmStats)
+    if shape != 0 or channels != 1:   # (rsmp_f32_to_pcm_shaped_device)
+        _check(lib().rsmp_f32_to_pcm_shaped_device(C.c_void_p(_dev_ptr(d_in)), n, bits, float(gain), int(dither), int(shape), int(channels), int(seed) & _U64,
+                                                   int(first_index) & _U64, C.c_void_p(d_pcm.data_ptr()) if d_pcm is not None else None,
+                                                   C.c_void_p(d_stats.data_ptr()), C.c_void_p(stream or 0)))
+        return
     if gain != 1.0:
         _check(lib().rsmp_f32_to_pcm_gain_device(C.c_void_p(_dev_ptr(d_in)), n, bits, float(gain), int(dither), int(seed) & _U64, int(first_index) & _U64,
                                                  C.c_void_p(d_pcm.data_ptr()) if d_pcm is not None else None, C.c_void_p(d_stats.data_ptr()),

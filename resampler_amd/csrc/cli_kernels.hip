@@ -411,14 +411,16 @@ extern "C" int rsmp_f32_to_pcm_stats_device(const float* d_in, size_t n_values, 
 namespace {
 
 // f32_to_pcm_stats_kernel's lanes, loads and stores; `out` and `stats` may each be null.
-template <int BITS, bool TPDF>
+// HP: the high-pass form of the TPDF noise (fir_pcm_dither_shaped: value i with the value `channels` indices before it) -- builds of
+// their own beside the white ones, which stay what they were.
+template <int BITS, bool TPDF, bool HP = false>
 __global__ __launch_bounds__(kThreads) void f32_to_pcm_gain_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, uint64_t n, float k, uint64_t seed,
-                                                                   uint64_t first, rsmp_pcm_stats* __restrict__ stats) {
+                                                                   uint64_t first, rsmp_pcm_stats* __restrict__ stats, uint32_t channels = 0) {
     typedef float v4f_in __attribute__((ext_vector_type(4)));
     const uint64_t n4 = n / 4, stride = static_cast<uint64_t>(gridDim.x) * kThreads;
     rsmp::FirPcmStat mine{0, 0, 0, 0};
     auto code = [&](float x, uint64_t i) {
-        const float d = TPDF ? rsmp::fir_pcm_dither(seed, first + i) : 0.0f;
+        const float d = !TPDF ? 0.0f : HP ? rsmp::fir_pcm_dither_shaped(seed, first + i, RSMP_DITHER_SHAPE_HIGHPASS, channels) : rsmp::fir_pcm_dither(seed, first + i);
         return static_cast<uint32_t>(rsmp::fir_pcm_quantise_gain_stat(x, k, BITS, d, mine));
     };
     for (uint64_t i = blockIdx.x * static_cast<uint64_t>(kThreads) + threadIdx.x; i <= n4; i += stride) {
@@ -513,7 +515,7 @@ extern "C" int rsmp_f32_to_pcm_gain_device(const float* d_in, size_t n_values, i
     uint8_t* o = static_cast<uint8_t*>(d_pcm);
     const uint64_t n = n_values;
     const float k = rsmp::fir_pcm_gain_scale(gain, static_cast<uint32_t>(bits));
-#define RSMP_GAIN_LAUNCH(BITS, TPDF) hipLaunchKernelGGL((f32_to_pcm_gain_kernel<BITS, TPDF>), grid, dim3(kThreads), 0, s, d_in, o, n, k, seed, first_index, d_stats)
+#define RSMP_GAIN_LAUNCH(BITS, TPDF) hipLaunchKernelGGL((f32_to_pcm_gain_kernel<BITS, TPDF>), grid, dim3(kThreads), 0, s, d_in, o, n, k, seed, first_index, d_stats, 0u)
     if (dither == RSMP_DITHER_TPDF) {
         if (bits == 16) RSMP_GAIN_LAUNCH(16, true);
         else if (bits == 24) RSMP_GAIN_LAUNCH(24, true);
@@ -524,6 +526,62 @@ extern "C" int rsmp_f32_to_pcm_gain_device(const float* d_in, size_t n_values, i
         else RSMP_GAIN_LAUNCH(32, false);
     }
 #undef RSMP_GAIN_LAUNCH
+    RSMP_HIP_CHECK(hipGetLastError());
+    return RSMP_OK;
+}
+
+// The same with a shape of the TPDF noise (fir_pcm_dither_shaped): the two-pass reference of rsmp_fir_set_pcm_dither_shape /
+// rsmp_fft_set_pcm_dither_shape.  White, or no dither: rsmp_f32_to_pcm_gain itself.
+extern "C" int rsmp_f32_to_pcm_shaped(const float* in, size_t n_values, int bits, float gain, int dither, int shape, uint32_t channels, uint64_t seed,
+                                      uint64_t first_index, void* out_pcm, rsmp_pcm_stats* stats) {
+    if (!pcm_gain_args_ok(bits, gain, dither) || (shape != RSMP_DITHER_SHAPE_WHITE && shape != RSMP_DITHER_SHAPE_HIGHPASS) || channels == 0 ||
+        (n_values != 0 && (!in || (!out_pcm && !stats))))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_shaped: 16 / 24 / 32 bits, a finite gain with 2^-32 <= |gain| <= 2^32, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, RSMP_DITHER_SHAPE_WHITE / RSMP_DITHER_SHAPE_HIGHPASS, channels >= 1, non-null input, and output or statistics");
+    if (dither != RSMP_DITHER_TPDF || shape == RSMP_DITHER_SHAPE_WHITE) return rsmp_f32_to_pcm_gain(in, n_values, bits, gain, dither, seed, first_index, out_pcm, stats);
+    uint8_t* o = static_cast<uint8_t*>(out_pcm);
+    const size_t bytes = static_cast<size_t>(bits) / 8;
+    const float k = rsmp::fir_pcm_gain_scale(gain, static_cast<uint32_t>(bits));
+    rsmp::FirPcmStat acc{0, 0, 0, 0};
+    rsmp_pcm_stats t{};
+    for (size_t i = 0; i < n_values; ++i) {
+        rsmp::FirPcmStat one{0, 0, 0, acc.peak};
+        const uint32_t q = static_cast<uint32_t>(rsmp::fir_pcm_quantise_gain_stat(
+            in[i], k, static_cast<uint32_t>(bits), rsmp::fir_pcm_dither_shaped(seed, first_index + i, static_cast<uint32_t>(shape), channels), one));
+        t.values += one.values;
+        t.clipped += one.clipped;
+        t.nans += one.nans;
+        acc.peak = one.peak;
+        if (o)   // (null: measure only)
+            for (size_t b = 0; b < bytes; ++b) o[i * bytes + b] = static_cast<uint8_t>(q >> (8 * b));   // little-endian
+    }
+    if (stats) {
+        std::memcpy(&t.peak, &acc.peak, sizeof acc.peak);
+        *stats = t;
+    }
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_f32_to_pcm_shaped_device(const float* d_in, size_t n_values, int bits, float gain, int dither, int shape, uint32_t channels, uint64_t seed,
+                                             uint64_t first_index, void* d_pcm, rsmp_pcm_stats* d_stats, void* stream) {
+    if (!pcm_gain_args_ok(bits, gain, dither) || (shape != RSMP_DITHER_SHAPE_WHITE && shape != RSMP_DITHER_SHAPE_HIGHPASS) || channels == 0 ||
+        (n_values != 0 && (!d_in || (!d_pcm && !d_stats))))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_shaped_device: 16 / 24 / 32 bits, a finite gain with 2^-32 <= |gain| <= 2^32, RSMP_DITHER_NONE / RSMP_DITHER_TPDF, RSMP_DITHER_SHAPE_WHITE / RSMP_DITHER_SHAPE_HIGHPASS, channels >= 1, non-null buffers");
+    if (dither != RSMP_DITHER_TPDF || shape == RSMP_DITHER_SHAPE_WHITE)
+        return rsmp_f32_to_pcm_gain_device(d_in, n_values, bits, gain, dither, seed, first_index, d_pcm, d_stats, stream);
+    if (reinterpret_cast<uintptr_t>(d_in) % 16 != 0 || reinterpret_cast<uintptr_t>(d_pcm) % 4 != 0 || reinterpret_cast<uintptr_t>(d_stats) % 8 != 0)
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_f32_to_pcm_shaped_device: d_in 16-byte aligned, d_pcm 4-byte aligned, d_stats 8-byte aligned");
+    if (int rc = check_device()) return rc;
+    if (n_values == 0) return RSMP_OK;
+    const dim3 grid = f32_to_pcm_grid(n_values);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* o = static_cast<uint8_t*>(d_pcm);
+    const uint64_t n = n_values;
+    const float k = rsmp::fir_pcm_gain_scale(gain, static_cast<uint32_t>(bits));
+#define RSMP_SHAPED_LAUNCH(BITS) hipLaunchKernelGGL((f32_to_pcm_gain_kernel<BITS, true, true>), grid, dim3(kThreads), 0, s, d_in, o, n, k, seed, first_index, d_stats, channels)
+    if (bits == 16) RSMP_SHAPED_LAUNCH(16);
+    else if (bits == 24) RSMP_SHAPED_LAUNCH(24);
+    else RSMP_SHAPED_LAUNCH(32);
+#undef RSMP_SHAPED_LAUNCH
     RSMP_HIP_CHECK(hipGetLastError());
     return RSMP_OK;
 }

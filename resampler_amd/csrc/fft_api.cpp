@@ -163,6 +163,8 @@ struct rsmp_fft {
     uint64_t pcm_dither_seed = 0;
     // The output gain of the PCM-output entries (rsmp_fft_set_pcm_gain): a setting like the dither, per stream; the f32 entries ignore it
     float pcm_gain = 1.0f;
+    // The shape of the TPDF noise (rsmp_fft_set_pcm_dither_shape): a setting like the mode, read only by a PCM-output launch under RSMP_DITHER_TPDF
+    int pcm_dither_shape = RSMP_DITHER_SHAPE_WHITE;
     // Statistics of the PCM the pair kernel stores for this handle (rsmp_fft_set_pcm_stats): a setting like the dither.  The totals
     // are one rsmp_pcm_stats in device memory, allocated and zeroed when the setting is first turned on; the counting builds
     // (fft_pair_pcm_stats.hip) merge into it.  A clear sets pcm_stats_cleared and nothing else: the handle's next counting launch
@@ -291,7 +293,8 @@ int launch_fft_jobs(rsmp_fft* leader, const std::vector<FftJob>& jobs, hipStream
     FftPcmOutDesc* h_pcm = out_bits != 0 ? reinterpret_cast<FftPcmOutDesc*>(h + n) : nullptr;
     for (size_t i = 0; h_pcm && i < n; ++i)
         h_pcm[i] = FftPcmOutDesc{jobs[i].r->pcm_dither_seed, jobs[i].r->abs_out, static_cast<uint32_t>(jobs[i].r->pcm_dither),
-                                 rsmp::fir_pcm_gain_scale(jobs[i].r->pcm_gain, out_bits)};
+                                 rsmp::fir_pcm_gain_scale(jobs[i].r->pcm_gain, out_bits),
+                                 jobs[i].r->pcm_dither == RSMP_DITHER_TPDF ? static_cast<uint32_t>(jobs[i].r->pcm_dither_shape) : 0u, 0u};
     rsmp_pcm_stats** h_acc = stats ? reinterpret_cast<rsmp_pcm_stats**>(reinterpret_cast<char*>(h) + acc_off) : nullptr;
     for (size_t i = 0; h_acc && i < n; ++i) h_acc[i] = jobs[i].r->d_pcm_stats;
     const FftStreamDesc* d_descs = h;   // (mapped host memory: the same address on the device)
@@ -547,6 +550,8 @@ extern "C" int rsmp_fft_batch_resample_bulk_pcm_out_device(rsmp_fft* const* rs, 
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one device and one rate pair and have two channels (%s)", kWayOut);
         if (rs[i]->pcm_dither != rs[0]->pcm_dither)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one dither mode: stream %zu differs (%s)", i, kWayOut);
+        if (rs[0]->pcm_dither == RSMP_DITHER_TPDF && rs[i]->pcm_dither_shape != rs[0]->pcm_dither_shape)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one dither shape (rsmp_fft_set_pcm_dither_shape): stream %zu differs (%s)", i, kWayOut);
         if (rs[i]->pcm_stats != rs[0]->pcm_stats)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM-output batch streams must share one statistics setting (rsmp_fft_set_pcm_stats): stream %zu differs", i);
         if (!d_in[i] || !d_out_pcm[i])
@@ -585,6 +590,19 @@ extern "C" int rsmp_fft_pcm_dither(const rsmp_fft* r, int* dither, uint64_t* see
     if (!r) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_dither: null handle");
     if (dither) *dither = r->pcm_dither;
     if (seed) *seed = r->pcm_dither_seed;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fft_set_pcm_dither_shape(rsmp_fft* r, int shape) {
+    if (!r || (shape != RSMP_DITHER_SHAPE_WHITE && shape != RSMP_DITHER_SHAPE_HIGHPASS))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_set_pcm_dither_shape: null handle, or shape not RSMP_DITHER_SHAPE_WHITE / RSMP_DITHER_SHAPE_HIGHPASS");
+    r->pcm_dither_shape = shape;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fft_pcm_dither_shape(const rsmp_fft* r, int* shape) {
+    if (!r || !shape) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fft_pcm_dither_shape: null argument");
+    *shape = r->pcm_dither_shape;
     return RSMP_OK;
 }
 

@@ -50,8 +50,10 @@ struct FftPcmOutDesc {
     uint64_t abs_out;     // output frames the handle had produced before this launch
     uint32_t dither;      // RSMP_DITHER_NONE / RSMP_DITHER_TPDF: one mode for all the streams of a launch
     float pcm_k;          // the factor every store multiplies by: f32(gain) * 2^(out_bits-1), the stream's own gain (fir_pcm_gain_scale)
+    uint32_t shape;       // RSMP_DITHER_SHAPE_*: one shape for all the streams of a launch, read under RSMP_DITHER_TPDF only (fir_dither_value_hp)
+    uint32_t reserved;
 };
-static_assert(sizeof(FftPcmOutDesc) == 24, "pcm_k took the reserved word: the size stays");
+static_assert(sizeof(FftPcmOutDesc) == 32, "read by the PCM-output builds alone: the f32 kernels do not know the type");
 
 // pcm_bits != 0: every stream's `in` is PCM of that width (FftStreamDesc::in_bits); hipErrorNotSupported where no kernel
 // that reads PCM serves the plan / channel count.  Which kernel, grid, block and LDS a launch gets: fft_launch.h.

@@ -317,9 +317,17 @@ __device__ __forceinline__ void pair_pcm_store(const FftStreamDesc& d, const Fft
     const float pl = v.x * scale, pr = v.y * scale;   // p of the gain rule: one rounding each
     float sl = pl, sr = pr;
     if (po.dither == RSMP_DITHER_TPDF) {
-        const uint64_t w = fir_dither_word(po.seed, po.abs_out + frame0 + n);
-        sl += fir_dither_value(static_cast<uint32_t>(w));
-        sr += fir_dither_value(static_cast<uint32_t>(w >> 32));
+        const uint64_t g = po.abs_out + frame0 + n;   // the stream's frame: values 2 g and 2 g + 1
+        const uint64_t key = po.seed + (g + 1) * kFirDitherStep;
+        const uint64_t w = fir_dither_mix(key);   // (fir_dither_word(po.seed, g))
+        if (po.shape == RSMP_DITHER_SHAPE_HIGHPASS) {   // uniform, as the mode: the frame before's word as well (rsmp_f32_to_pcm_shaped, channels = 2)
+            const uint64_t wp = fir_dither_mix(fir_dither_prev_key(key, kFirDitherStep, g == 0));
+            sl += fir_dither_value_hp(static_cast<uint32_t>(w), static_cast<uint32_t>(wp));
+            sr += fir_dither_value_hp(static_cast<uint32_t>(w >> 32), static_cast<uint32_t>(wp >> 32));
+        } else {
+            sl += fir_dither_value(static_cast<uint32_t>(w));
+            sr += fir_dither_value(static_cast<uint32_t>(w >> 32));
+        }
     }
 #if RSMP_PAIR_PCM_OUT == 2
     const float vl = rintf(sl), vr = rintf(sr);

@@ -324,7 +324,8 @@ int pcm_call(const char* entry, rsmp_fir* const* rs, size_t n, const void* const
     if (!rs || !rs[0] || !d_in || !in_lens || !d_out || !out_caps || chunk_len == 0 || required_bits == 0)
         return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "%s: null / zero argument", entry);
     const rsmp::FirFormat f{static_cast<uint32_t>(in_bits), static_cast<uint32_t>(out_bits),   // (the handles' settings: read only where PCM is written)
-                            out_bits != 0 ? static_cast<uint32_t>(rs[0]->pcm_dither) : 0u, out_bits != 0 && rs[0]->pcm_stats};
+                            out_bits != 0 ? static_cast<uint32_t>(rs[0]->pcm_dither) : 0u, out_bits != 0 && rs[0]->pcm_stats,
+                            out_bits != 0 && rs[0]->pcm_dither == RSMP_DITHER_TPDF ? static_cast<uint32_t>(rs[0]->pcm_dither_shape) : 0u};
     std::vector<const float*> in(n);
     std::vector<float*> out(n);
     for (size_t i = 0; i < n; ++i) {
@@ -334,6 +335,8 @@ int pcm_call(const char* entry, rsmp_fir* const* rs, size_t n, const void* const
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "%s", rsmp::format_fault_text(fault));
         if (out_bits != 0 && static_cast<uint32_t>(rs[i]->pcm_dither) != f.dither)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: one dither mode for all the streams of a batch (rsmp_fir_set_pcm_dither; the seeds may differ)");
+        if (out_bits != 0 && f.dither == RSMP_DITHER_TPDF && static_cast<uint32_t>(rs[i]->pcm_dither_shape) != f.dither_shape)
+            return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: one dither shape for all the streams of a batch (rsmp_fir_set_pcm_dither_shape; the seeds may differ)");
         if (out_bits != 0 && rs[i]->pcm_stats != f.stats)
             return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "PCM output: statistics for all the streams of a batch or for none (rsmp_fir_set_pcm_stats)");
         if ((in_bits != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) || (out_bits != 0 && reinterpret_cast<uintptr_t>(d_out[i]) % 4 != 0))
@@ -447,6 +450,20 @@ extern "C" int rsmp_fir_set_pcm_dither(rsmp_fir* r, int dither, uint64_t seed) {
         return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_set_pcm_dither: null handle or unknown dither mode %d", dither);
     r->pcm_dither = dither;
     r->pcm_dither_seed = seed;
+    return RSMP_OK;
+}
+
+// ... and its shape: a setting like the mode, read only by a launch whose mode is TPDF.
+extern "C" int rsmp_fir_set_pcm_dither_shape(rsmp_fir* r, int shape) {
+    if (!r || (shape != RSMP_DITHER_SHAPE_WHITE && shape != RSMP_DITHER_SHAPE_HIGHPASS))
+        return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_set_pcm_dither_shape: null handle or unknown dither shape %d", shape);
+    r->pcm_dither_shape = shape;
+    return RSMP_OK;
+}
+
+extern "C" int rsmp_fir_pcm_dither_shape(const rsmp_fir* r, int* shape) {
+    if (!r || !shape) return rsmp::fail(RSMP_ERR_INVALID_ARGUMENT, "rsmp_fir_pcm_dither_shape: null argument");
+    *shape = r->pcm_dither_shape;
     return RSMP_OK;
 }
 
@@ -719,7 +736,8 @@ extern "C" int rsmp_fir_batch_resample_bulk_pcm_device(rsmp_fir* const* rs, size
 // entry's output, without the f32 ever reaching HBM (f32 written, f32 read, PCM written: two passes less).
 // Handles set to RSMP_DITHER_TPDF (rsmp_fir_set_pcm_dither; all of a batch or none: the entry refuses a mix) add their noise at
 // the same sites, value (frame n of the launch, channel c) with index (abs_out + n) * channels + c -- rsmp_f32_to_pcm_dither_device's
-// bytes with the handle's seed and first_index = abs_out * channels.
+// bytes with the handle's seed and first_index = abs_out * channels.  With rsmp_fir_set_pcm_dither_shape(RSMP_DITHER_SHAPE_HIGHPASS) -- one
+// shape for a batch under TPDF -- the noise is the high-pass form: rsmp_f32_to_pcm_shaped_device's bytes with the stream's channels.
 // Handles set to count (rsmp_fir_set_pcm_stats; all of a batch or none) take the kernels' counting builds: the same bytes, and
 // rsmp_f32_to_pcm_stats's statistics of them in the handles' totals.
 // Which streams and launches: format_stream_fault and format_group_fault (fir_geometry.cpp).  Even counts of 4 .. 16 channels are written by the

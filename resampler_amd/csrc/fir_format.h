@@ -13,12 +13,19 @@ namespace rsmp {
 // How a build stores its sums (the kernels' template argument OUT): f32, PCM, PCM with TPDF dither -- and PCM that is counted as
 // it is stored (rsmp_fir_set_pcm_stats): builds of their own, with the dither a uniform branch on FirStreamDesc::dither.
 enum FirOut : int { kFirOutF32 = 0, kFirOutPcm = 1, kFirOutPcmTpdf = 2, kFirOutPcmStats = 3 };
+// The split kernel alone: its dithered builds' twins for RSMP_DITHER_SHAPE_HIGHPASS (a second mix per frame; as a run-time branch of
+// the white builds it cost those 0.005 ms of a 0.35 ms launch at 16 bits: profiles/pcm_dither_shape.txt).  Not an out_mode(): the
+// generic kernels and the repair pass read the shape from the descriptor, and so do the counting builds.
+constexpr int kFirOutPcmTpdfHp = 4;
 
 struct FirFormat {
     uint32_t in_bits = 0;    // 0: interleaved f32; 16 / 24 / 32: a WAV file's PCM, read in place (FirStreamDesc::in_bits)
     uint32_t out_bits = 0;   // 0: interleaved f32; 16 / 24 / 32: PCM, quantised where it is stored (FirStreamDesc::out_bits)
     uint32_t dither = 0;     // RSMP_DITHER_*, read only with out_bits != 0 (FirStreamDesc::dither)
     bool stats = false;      // the PCM output is counted (rsmp_fir_set_pcm_stats), only with out_bits != 0
+    uint32_t dither_shape = 0;   // RSMP_DITHER_SHAPE_*, read only with out_bits != 0 and dither == RSMP_DITHER_TPDF (FirStreamDesc::dither_shape):
+                                 // a run-time value of the generic kernels, the repair pass and every counting build; of the split
+                                 // kernel's dithered builds it selects the high-pass twins (SplitBuild::hp)
     bool pcm() const { return in_bits != 0 || out_bits != 0; }
     // Counted wins over dithered (the counting builds serve both dither modes); neither exists without PCM output.
     RSMP_HD constexpr FirOut out_mode() const {

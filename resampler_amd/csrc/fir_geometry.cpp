@@ -296,7 +296,8 @@ void periodic_fill_wrap_bits(const std::vector<uint32_t>& wraps, uint64_t abs_ou
 // PCM output (FirStreamDesc::out_bits): the same three windows, from f32 or PCM input, as builds of their own that read the
 // width from the descriptor -- and, from f32 input, the channel-pair builds of those windows (an even count of 4 .. 16 channels);
 // kNotSupported for any other geometry (the caller converts with rsmp_f32_to_pcm_device afterwards).
-// dither != 0 (FirStreamDesc::dither): their twins that add TPDF dither.  stats: their twins that count what they store, with or
+// dither != 0 (FirStreamDesc::dither): their twins that add TPDF dither -- white, or with format.dither_shape ==
+// RSMP_DITHER_SHAPE_HIGHPASS the high-pass twins of those (SplitBuild::hp).  stats: their twins that count what they store, with or
 // without dither (one build for both: a uniform branch).
 SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, const FirFormat& format) {
     const uint32_t pcm_bits = format.in_bits, out_bits = format.out_bits;
@@ -326,7 +327,8 @@ SplitChoice split_build_for(const PeriodicGeometry& geo, bool diag, const FirFor
             (out_bits != 0 && !width_ok(out_bits)))
             return {b, BuildError::kNotSupported};
         const FirOut mode = format.out_mode();
-        b = SplitBuild{nk, 2, false, pairs_out ? 1 : 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, mode == kFirOutPcmTpdf, mode == kFirOutPcmStats};
+        b = SplitBuild{nk, 2, false, pairs_out ? 1 : 0, two_rounds ? 2 : 1, static_cast<int>(pcm_bits), out_bits != 0, mode == kFirOutPcmTpdf, mode == kFirOutPcmStats,
+                       mode == kFirOutPcmTpdf && format.dither_shape == RSMP_DITHER_SHAPE_HIGHPASS};
     }
     return {b, BuildError::kNone};
 }

@@ -64,6 +64,7 @@ struct rsmp_fir {
     // A setting, not state: reset and seek leave it alone; the noise counter is the mirror's abs_out.
     int pcm_dither = RSMP_DITHER_NONE;
     uint64_t pcm_dither_seed = 0;
+    int pcm_dither_shape = RSMP_DITHER_SHAPE_WHITE;   // (rsmp_fir_set_pcm_dither_shape; read only under RSMP_DITHER_TPDF)
     // ... and the stream's output gain (rsmp_fir_set_pcm_gain): only the PCM-output entry reads it
     float pcm_gain = 1.0f;
     // ... and its statistics (rsmp_fir_set_pcm_stats): the setting -- reset and seek leave it -- and the handle's totals, one

@@ -42,6 +42,9 @@ struct FirStreamDesc {
     uint32_t taps;
     // periodic kernel: in_hz/out_hz = num/den reduced, absolute counters at launch start
     uint32_t num, den;
+    // PCM output with TPDF dither only: RSMP_DITHER_SHAPE_*, one shape for all the streams of a launch (fir_pcm_dither_shaped below).
+    // It sits in what was padding in front of abs_out: no other field moves.  No f32 build and no undithered build reads it.
+    uint32_t dither_shape;
     uint64_t abs_out;              // output frames produced since reset, before this launch
     uint64_t abs_consumed;         // input frames retired since reset, before this launch
     uint64_t wrap_k0;              // wrap_bits bit K <-> absolute output (wrap_k0 + K) * den
@@ -63,6 +66,7 @@ struct FirStreamDesc {
     float pcm_k;
     uint64_t dither_seed;
 };
+static_assert(offsetof(FirStreamDesc, dither_shape) == 140 && offsetof(FirStreamDesc, abs_out) == 144, "dither_shape fills the padding in front of abs_out");
 static_assert(offsetof(FirStreamDesc, pcm_k) == 188 && offsetof(FirStreamDesc, dither_seed) == 192 && sizeof(FirStreamDesc) == 200,
               "pcm_k fills the hole in front of dither_seed: the descriptor keeps its size and every other field its place");
 
@@ -118,6 +122,31 @@ __host__ __device__ __forceinline__ float fir_dither_value(uint32_t h) {   // h:
 __host__ __device__ __forceinline__ float fir_pcm_dither(uint64_t seed, uint64_t i) {
     const uint64_t w = fir_dither_word(seed, i >> 1);
     return fir_dither_value(static_cast<uint32_t>((i & 1) ? w >> 32 : w));
+}
+// High-pass TPDF dither (RSMP_DITHER_SHAPE_HIGHPASS; rsmp_f32_to_pcm_shaped): THE definition, every site calls fir_dither_value_hp.
+// With h(seed, i) the 32 bits above (fir_dither_half) and r1 = h & 0xFFFF, value i of a stream of `channels` channels takes
+//   d = f32(r1(i) - r1(i - channels)) * 2^-16,        i - channels wrapping in 64 bits,
+// u[n] - u[n-1] of one uniform sequence per channel: the white form's density and variance, consecutive values of a channel
+// correlated by -1/2, the power 1 - cos(w) times the white level.  Still a function of (seed, index): no state, no error feedback.
+// The earlier value's word is an earlier counter's mix -- for a two-channel frame or a channel pair the word `pairs` counters
+// back, key - pairs * kFirDitherStep -- EXCEPT in the stream's first frame: index 2^64 - channels + c has the counter
+// 2^63 - channels / 2 + ..., not -channels / 2 + ... (i >> 1 drops the bit the subtraction borrowed), so that frame's earlier key is
+// the stepped-back key with bit 63 flipped (2^63 * kFirDitherStep = 2^63 mod 2^64: the step is odd).  fir_dither_prev_key does that.
+__host__ __device__ __forceinline__ uint32_t fir_dither_half(uint64_t seed, uint64_t i) {   // h(seed, i)
+    const uint64_t w = fir_dither_word(seed, i >> 1);
+    return static_cast<uint32_t>((i & 1) ? w >> 32 : w);
+}
+__host__ __device__ __forceinline__ float fir_dither_value_hp(uint32_t h, uint32_t h_prev) {   // h, h_prev: the 32 bits of values i and i - channels
+    return static_cast<float>(static_cast<int32_t>(h & 0xFFFFu) - static_cast<int32_t>(h_prev & 0xFFFFu)) * (1.0f / 65536.0f);
+}
+// (key: the mix counter of a frame's even-indexed pair of values, seed + (pair + 1) * kFirDitherStep; back: pairs a frame * kFirDitherStep;
+// first: the frame is the stream's frame 0)
+__host__ __device__ __forceinline__ uint64_t fir_dither_prev_key(uint64_t key, uint64_t back, bool first) {
+    return (key - back) ^ (first ? 0x8000000000000000ull : 0ull);
+}
+__host__ __device__ __forceinline__ float fir_pcm_dither_shaped(uint64_t seed, uint64_t i, uint32_t shape, uint32_t channels) {
+    const uint32_t h = fir_dither_half(seed, i);
+    return shape == RSMP_DITHER_SHAPE_HIGHPASS ? fir_dither_value_hp(h, fir_dither_half(seed, i - channels)) : fir_dither_value(h);
 }
 // The quantiser with the noise `d` of the value's index added: THE definition of dithered output, every site calls it.
 __host__ __device__ __forceinline__ int32_t fir_pcm_quantise_dither(float x, uint32_t bits, float d) {
@@ -247,7 +276,7 @@ __device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i
 __device__ __forceinline__ void fir_pcm_store(void* out, uint32_t bits, size_t i, float y, float k) { fir_pcm_store_code(out, bits, i, fir_pcm_quantise_gain(y, k, bits)); }
 // A counting build's store of value `i` (as fir_out_store below): the bytes of the plain / dithered builds, and `s` says what was done.
 __device__ __forceinline__ void fir_out_store_stat(const FirStreamDesc& d, size_t i, float y, FirPcmStat& s) {
-    const float noise = d.dither == RSMP_DITHER_TPDF ? fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i) : 0.0f;
+    const float noise = d.dither == RSMP_DITHER_TPDF ? fir_pcm_dither_shaped(d.dither_seed, d.abs_out * d.channels + i, d.dither_shape, d.channels) : 0.0f;
     fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_gain_stat(y, d.pcm_k, d.out_bits, noise, s));
 }
 // Value `i` of a stream's output in this launch.  OUT: the PCM-output builds of the generic kernels and of the repair pass (out_bits
@@ -255,7 +284,7 @@ __device__ __forceinline__ void fir_out_store_stat(const FirStreamDesc& d, size_
 template <int OUT>
 __device__ __forceinline__ void fir_out_store(const FirStreamDesc& d, size_t i, float y) {
     if constexpr (OUT == kFirOutPcmTpdf)
-        fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_gain(y, d.pcm_k, d.out_bits, fir_pcm_dither(d.dither_seed, d.abs_out * d.channels + i)));
+        fir_pcm_store_code(d.out, d.out_bits, i, fir_pcm_quantise_gain(y, d.pcm_k, d.out_bits, fir_pcm_dither_shaped(d.dither_seed, d.abs_out * d.channels + i, d.dither_shape, d.channels)));
     else if constexpr (OUT == kFirOutPcm) fir_pcm_store(d.out, d.out_bits, i, y, d.pcm_k);
     else d.out[i] = y;
 }

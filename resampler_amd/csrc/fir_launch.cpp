@@ -256,6 +256,7 @@ int fill_descriptors(Launch& L) {
         ds.in_bits = L.format.in_bits;
         ds.out_bits = L.format.out_bits;
         ds.dither = L.format.dither;
+        ds.dither_shape = L.format.out_bits != 0 && L.format.dither == RSMP_DITHER_TPDF ? L.format.dither_shape : 0;
         ds.dither_seed = L.format.out_bits != 0 ? r->pcm_dither_seed : 0;
         // (written for every PCM-output launch, whatever was cached: the descriptors are this launch's own, and publish() compares the image)
         ds.pcm_k = L.format.out_bits != 0 ? fir_pcm_gain_scale(r->pcm_gain, L.format.out_bits) : 0.0f;

@@ -82,10 +82,11 @@ struct SplitBuild {
     int bits;         // PCM input of that width (0: f32)
     bool pcm_out;     // PCM output (its width is the descriptor's, read at run time)
     bool dither;      // ... with TPDF dither (the seeds are the descriptors')
-    bool stats;       // ... counted as it is stored (SplitArgs::stat); these builds read the dither mode from the descriptor (dither = false)
+    bool stats;       // ... counted as it is stored (SplitArgs::stat); these builds read the dither mode and shape from the descriptor (dither = false)
+    bool hp = false;  // with dither: the twin that makes high-pass noise (RSMP_DITHER_SHAPE_HIGHPASS)
     bool operator==(const SplitBuild& o) const {
         return nk == o.nk && planes == o.planes && diag == o.diag && wide == o.wide && rounds == o.rounds && bits == o.bits &&
-               pcm_out == o.pcm_out && dither == o.dither && stats == o.stats;
+               pcm_out == o.pcm_out && dither == o.dither && stats == o.stats && hp == o.hp;
     }
 };
 enum class BuildError { kNone, kInvalid, kNotSupported };   // the launchers' hipErrorInvalidValue / hipErrorNotSupported

@@ -483,9 +483,10 @@ __device__ __forceinline__ uint32_t consumer_index(uint32_t w) { return w < 6 ? 
 // OUT: the streams' `out` is PCM (FirStreamDesc::out_bits: 16 / 24 / 32, one width per launch, read from the descriptor by
 // these builds alone): the consumers quantise their sums where they store them (fir_pcm_quantise_gain, by the stream's own
 // factor FirStreamDesc::pcm_k = gain * 2^(out_bits-1): a pending store carries its stream's) -- OUT is a FirOut; the
-// kFirOutPcmTpdf builds add TPDF dither there (the stream's seed from the descriptor, one 64-bit mix per frame).
+// kFirOutPcmTpdf builds add TPDF dither there (the stream's seed from the descriptor, one 64-bit mix per frame); the kFirOutPcmTpdfHp
+// builds add its high-pass form (RSMP_DITHER_SHAPE_HIGHPASS: a second mix per frame, the frame before's word -- fir_dither_value_hp).
 // The kFirOutPcmStats builds also count every value they store into its chunk's entry of g.stat (fir_pcm_stat), where the wave
-// decides what it stores -- a deferred store is counted once, there --; they serve both dither modes (a wave-uniform branch).
+// decides what it stores -- a deferred store is counted once, there --; they serve both dither modes and both shapes (wave-uniform branches).
 template <int NK, int PLANES, bool DIAG, int WIDE, int ROUNDS = 1, int BITS = 0, int OUT = kFirOutF32>   // WIDE: 0 two channels, 1 channel pairs, 2 one channel, 3 pairs + a last channel alone; BITS: the input's PCM width (0: f32)
 __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__ descs, const SplitArgs& g,
                                                const uint32_t wg, const uint32_t n_wgs) {   // workgroup `wg` of the `n_wgs` that share g's items
@@ -1357,8 +1358,18 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     struct NoKey {
         __device__ NoKey operator+(uint64_t) const { return NoKey{}; }
     };
-    constexpr bool kKeyed = OUT == kFirOutPcmTpdf || OUT == kFirOutPcmStats;
-    typedef typename std::conditional<kKeyed, uint64_t, NoKey>::type dkey_t;
+    // (first: the frame is the stream's frame 0, whose high-pass noise draws its earlier word from behind the 64-bit wrap of the value
+    // index -- fir_dither_prev_key; the frames behind a key's own are never frame 0)
+    struct FrameKey {
+        uint64_t k;
+        bool first;
+        __device__ FrameKey operator+(uint64_t s) const { return FrameKey{k + s, first && s == 0}; }
+    };
+    constexpr bool kKeyed = OUT == kFirOutPcmTpdf || OUT == kFirOutPcmTpdfHp || OUT == kFirOutPcmStats;
+    // the builds that can make high-pass noise: the dithered builds' high-pass twins, and the counting builds by the descriptor; the
+    // white dithered builds keep the bare counter as their key (and the code they had)
+    constexpr bool kShaped = OUT == kFirOutPcmTpdfHp || OUT == kFirOutPcmStats;
+    typedef typename std::conditional<kShaped, FrameKey, typename std::conditional<kKeyed, uint64_t, NoKey>::type>::type dkey_t;
     dkey_t pend_k{};
     // PCM output: a stream's store factor (FirStreamDesc::pcm_k = gain * 2^(out_bits-1); the streams of a launch may differ in gain,
     // so a pending store carries its own); nothing in the f32 builds, as the key above.  Fetched through the scalar cache when
@@ -1397,6 +1408,15 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
         typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
         dith = __builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[0].dither)) == RSMP_DITHER_TPDF;
     }
+    // the builds that can make high-pass noise: how far back in mix counters the same pair of the frame before lies -- one step for
+    // a two-channel frame, g.pairs steps for a channel pair --, and for the counting builds the launch's shape (wave-uniform, as the mode)
+    bool hp = OUT == kFirOutPcmTpdfHp;
+    uint64_t key_back = 0;
+    if constexpr (kShaped) key_back = WIDE ? static_cast<uint64_t>(g.pairs) * kFirDitherStep : kFirDitherStep;
+    if constexpr (OUT == kFirOutPcmStats) {
+        typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;
+        hp = __builtin_amdgcn_readfirstlane(*(const_u32_ptr)(&descs[0].dither_shape)) == RSMP_DITHER_SHAPE_HIGHPASS;
+    }
     typedef uint8_t __attribute__((address_space(1)))* g_u8_ptr;
     typedef uint16_t __attribute__((address_space(1)))* g_u16_ptr;
     typedef uint32_t __attribute__((address_space(1)))* g_u32_ptr;
@@ -1407,9 +1427,30 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
     // the key + kFirDitherStep each.  The key carries the stream's seed and counter: a pending store needs nothing else of `d`.
     auto dither_key = [&](const StreamCtx& d, int32_t n) -> dkey_t {
         if constexpr (!kKeyed) return NoKey{};
-        // channel pairs: values (abs_out + n) * channels + 2 pair and + 1 -- an even index, word (abs_out + n) * pairs + pair
-        else if constexpr (WIDE) return d.dither_seed + ((d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n))) * g.pairs + key_pair + 1u) * kFirDitherStep;
-        else return d.dither_seed + (d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n)) + 1u) * kFirDitherStep;
+        else {
+            const uint64_t f = d.abs_out + static_cast<uint64_t>(static_cast<int64_t>(n));   // the stream's frame
+            uint64_t k;
+            // channel pairs: values (abs_out + n) * channels + 2 pair and + 1 -- an even index, word (abs_out + n) * pairs + pair
+            if constexpr (WIDE) k = d.dither_seed + (f * g.pairs + key_pair + 1u) * kFirDitherStep;
+            else k = d.dither_seed + (f + 1u) * kFirDitherStep;
+            if constexpr (kShaped) return FrameKey{k, f == 0};
+            else return k;
+        }
+    };
+    // a frame's two noise values by the launch's shape (fir_kernels.h: fir_dither_value, fir_dither_value_hp); the high-pass form
+    // mixes the earlier frame's word as well (a wave-uniform branch)
+    auto frame_noise = [&](const dkey_t& k, float& d0, float& d1) {
+        if constexpr (kShaped) {
+            const uint64_t w = fir_dither_mix(k.k);
+            if (OUT == kFirOutPcmTpdfHp || hp) {
+                const uint64_t wp = fir_dither_mix(fir_dither_prev_key(k.k, key_back, k.first));
+                d0 = fir_dither_value_hp(static_cast<uint32_t>(w), static_cast<uint32_t>(wp));
+                d1 = fir_dither_value_hp(static_cast<uint32_t>(w >> 32), static_cast<uint32_t>(wp >> 32));
+            } else {
+                d0 = fir_dither_value(static_cast<uint32_t>(w));
+                d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
+            }
+        }
     };
     // a frame's two dithered codes (the undithered builds quantise below, in the statements they always had: their code is unchanged)
     auto dither_frame = [&](float y0, float y1, dkey_t k, pks_t ks, uint32_t& q0, uint32_t& q1) {
@@ -1417,13 +1458,14 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
             const uint64_t w = fir_dither_mix(k);
             q0 = static_cast<uint32_t>(fir_pcm_quantise_gain(y0, ks, out_bits, fir_dither_value(static_cast<uint32_t>(w))));
             q1 = static_cast<uint32_t>(fir_pcm_quantise_gain(y1, ks, out_bits, fir_dither_value(static_cast<uint32_t>(w >> 32))));
+        } else if constexpr (OUT == kFirOutPcmTpdfHp) {
+            float d0, d1;
+            frame_noise(k, d0, d1);
+            q0 = static_cast<uint32_t>(fir_pcm_quantise_gain(y0, ks, out_bits, d0));
+            q1 = static_cast<uint32_t>(fir_pcm_quantise_gain(y1, ks, out_bits, d1));
         } else if constexpr (OUT == kFirOutPcmStats) {
             float d0 = 0.0f, d1 = 0.0f;   // (no dither: x * k + 0 rounds to the undithered form's code)
-            if (dith) {
-                const uint64_t w = fir_dither_mix(k);
-                d0 = fir_dither_value(static_cast<uint32_t>(w));
-                d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
-            }
+            if (dith) frame_noise(k, d0, d1);
             q0 = static_cast<uint32_t>(fir_pcm_quantise_gain(y0, ks, out_bits, d0));
             q1 = static_cast<uint32_t>(fir_pcm_quantise_gain(y1, ks, out_bits, d1));
         }
@@ -1444,11 +1486,7 @@ __device__ __forceinline__ void fir_split_body(const FirStreamDesc* __restrict__
                 fr[r] = FirPcmStat{0, 0, 0, 0};
                 if (full || (j0 + r < g.b && n >= 0 && n < n_limit)) {
                     float d0 = 0.0f, d1 = 0.0f;
-                    if (dith) {
-                        const uint64_t w = fir_dither_mix(dither_key(d, n));
-                        d0 = fir_dither_value(static_cast<uint32_t>(w));
-                        d1 = fir_dither_value(static_cast<uint32_t>(w >> 32));
-                    }
+                    if (dith) frame_noise(dither_key(d, n), d0, d1);
                     (void)fir_pcm_quantise_gain_stat(y[2 * r], ks, out_bits, d0, fr[r]);
                     (void)fir_pcm_quantise_gain_stat(y[2 * r + 1], ks, out_bits, d1, fr[r]);
                     c_last = n >> kNfChunkShift;
@@ -1796,6 +1834,11 @@ template <int NK, int ROUNDS, int BITS>
 __global__ __launch_bounds__(1024) void fir_split_pcm_tpdf_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
     fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcmTpdf>(descs, g, blockIdx.x, gridDim.x);
 }
+// ... and with high-pass TPDF dither (FirStreamDesc::dither_shape): builds of their own again, so that the white ones stay as they were
+template <int NK, int ROUNDS, int BITS>
+__global__ __launch_bounds__(1024) void fir_split_pcm_tpdf_hp_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
+    fir_split_body<NK, 2, false, 0, ROUNDS, BITS, kFirOutPcmTpdfHp>(descs, g, blockIdx.x, gridDim.x);
+}
 // ... and counted as it is stored (SplitArgs::stat), with or without dither
 template <int NK, int ROUNDS, int BITS>
 __global__ __launch_bounds__(1024) void fir_split_pcm_stats_kernel(const FirStreamDesc* __restrict__ descs, const SplitArgs g) {
@@ -1902,11 +1945,13 @@ const void* split_kernel_for(const SplitBuild& build) {
 #define RSMP_SPLIT_OUT1(NK, R, B)                                                                                        \
     {SplitBuild{NK, 2, false, 0, R, B, true, false, false}, reinterpret_cast<const void*>(fir_split_pcm_out_kernel<NK, R, B>)},  \
     {SplitBuild{NK, 2, false, 0, R, B, true, true, false}, reinterpret_cast<const void*>(fir_split_pcm_tpdf_kernel<NK, R, B>)},  \
+    {SplitBuild{NK, 2, false, 0, R, B, true, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_tpdf_hp_kernel<NK, R, B>)},  \
     {SplitBuild{NK, 2, false, 0, R, B, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_stats_kernel<NK, R, B>)}
 #define RSMP_SPLIT_OUT(B) RSMP_SPLIT_OUT1(5, 1, B), RSMP_SPLIT_OUT1(5, 2, B), RSMP_SPLIT_OUT1(6, 2, B)
 #define RSMP_SPLIT_OUT_WIDE(NK, R)                                                                                                          \
     {SplitBuild{NK, 2, false, 1, R, 0, true, false, false}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcm>)},      \
     {SplitBuild{NK, 2, false, 1, R, 0, true, true, false}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcmTpdf>)},   \
+    {SplitBuild{NK, 2, false, 1, R, 0, true, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcmTpdfHp>)},   \
     {SplitBuild{NK, 2, false, 1, R, 0, true, false, true}, reinterpret_cast<const void*>(fir_split_pcm_wide_kernel<NK, R, kFirOutPcmStats>)}
 #define RSMP_SPLIT_1TO5(P, D, W) RSMP_SPLIT(1, P, D, W, 1, 0), RSMP_SPLIT(2, P, D, W, 1, 0), RSMP_SPLIT(3, P, D, W, 1, 0), RSMP_SPLIT(4, P, D, W, 1, 0), RSMP_SPLIT(5, P, D, W, 1, 0)
 #define RSMP_SPLIT_PCM(B) RSMP_SPLIT(5, 2, false, 0, 1, B), RSMP_SPLIT(5, 2, false, 0, 2, B), RSMP_SPLIT(6, 2, false, 0, 2, B)

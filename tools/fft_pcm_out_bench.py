@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--gain", type=float, default=1.0)
+    ap.add_argument("--shape", choices=("white", "highpass"), default="white",
+                    help="the handles' dither shape (ResamplerFft.set_pcm_dither_shape) and the tpdf two_pass rows'; white leaves the setting alone")
     ap.add_argument("--stats", action="store_true", help="add the rows of the store's statistics: setting off / on, two-pass counted, parent")
     ap.add_argument("--parent-lib", default=None, help="--stats: a libresampler_amd.so of the parent commit, for the `parent` rows")
     a = ap.parse_args()
@@ -59,9 +61,12 @@ def main():
     hs = [ra.ResamplerFft.new(2, ra.SampleRate.Hz44100, ra.SampleRate.Hz48000) for _ in range(S)]
     n_in, n_out = hs[0].chunk_size_input(), hs[0].chunk_size_output()
     gain_kw = {"gain": a.gain} if a.gain != 1.0 else {}
+    shape_kw = {"shape": int(ra.DitherShape.HIGHPASS), "channels": 2} if a.shape == "highpass" else {}
     for h in hs:
         if gain_kw:
             h.set_pcm_gain(a.gain)
+        if shape_kw:
+            h.set_pcm_dither_shape(ra.DitherShape.HIGHPASS)
     base = torch.from_numpy(synth.sweep(blocks * n_in // 2, 2, 44100.0)).to(dev)
     gains = torch.linspace(0.5, 1.0, S, device=dev)
     d_f32 = [(base * gains[i]).contiguous() for i in range(S)]
@@ -99,7 +104,7 @@ def main():
                         ra.f32_to_pcm_device(out_all, bits, pcm_all, stream, **gain_kw)
                     else:   # (first_index 0: the noise of a fresh stream; which index it starts at costs nothing)
                         for i in range(S):
-                            ra.f32_to_pcm_device(d_out[i], bits, d_pcm_out[i], stream, dither=dither, seed=a.seed + i, first_index=0, **gain_kw)
+                            ra.f32_to_pcm_device(d_out[i], bits, d_pcm_out[i], stream, dither=dither, seed=a.seed + i, first_index=0, **gain_kw, **shape_kw)
 
                 def fused(in_bits=in_bits, bits=bits, dither=dither, d_pcm_out=d_pcm_out):
                     if hs[0].pcm_dither()[0] != int(dither):
@@ -138,6 +143,8 @@ def main():
     result = {"streams": S, "blocks": blocks, "reps": a.reps, "burst": a.burst, "rounds": a.rounds, "lib": os.path.basename(ra.LIB_PATH), "rows": {}}
     if gain_kw:
         result.update(gain=a.gain)
+    if shape_kw:
+        result.update(shape=a.shape)
     for k in rows:
         v = np.asarray(all_t[k])
         result["rows"][k] = {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(v.min()), 4), "max_ms": round(float(v.max()), 4),

@@ -29,6 +29,9 @@ process; the rows are then over all their repetitions and carry every round's me
 route's own spread from round to round stands beside the gain.
 --gain G (default 1: the setting is left alone, so that a library from before it can be measured): every handle's output gain
 (ResamplerFir.set_pcm_gain); the conversion passes of the two-pass rows take the same gain.
+--shape highpass (default white: the setting is left alone, so that a library from before it can be measured): with --dither tpdf,
+every handle's dither shape (ResamplerFir.set_pcm_dither_shape); the conversion passes of the two-pass rows take the same shape and
+the streams' channel count.
 --convert: instead of the table, the stand-alone conversion alone -- rsmp_f32_to_pcm_device without and with dither over
 --convert-values values, and rsmp_device_stream_copy moving the same number of bytes (the conversion reads 4 and writes bits / 8
 bytes a value, the copy reads and writes 4 bytes a float) -- each bracketed by events, median of --reps bursts, with GB/s.
@@ -104,6 +107,7 @@ def main():
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--gain", type=float, default=1.0)
+    ap.add_argument("--shape", choices=("white", "highpass"), default="white")
     ap.add_argument("--convert", action="store_true")
     ap.add_argument("--convert-values", type=int, default=1 << 27)
     a = ap.parse_args()
@@ -123,6 +127,8 @@ def main():
         h.set_pcm_dither(dither, a.seed + i)
         if a.gain != 1.0:
             h.set_pcm_gain(a.gain)
+        if a.shape == "highpass":
+            h.set_pcm_dither_shape(ra.DitherShape.HIGHPASS)
     batch = ra.FirBatch(hs)
     batch.device_planner = False   # (the fused entry is planned on the host: the same planner for every row of the table)
     base = torch.from_numpy(synth.sweep(N, C, 44100.0)).to(dev)
@@ -163,6 +169,9 @@ def main():
     gain_kw = {"gain": a.gain} if a.gain != 1.0 else {}
     if gain_kw:
         result.update(gain=a.gain)
+    if a.shape == "highpass":   # (the converter's keywords travel with the gain's)
+        gain_kw.update(shape=int(ra.DitherShape.HIGHPASS), channels=C)
+        result.update(shape=a.shape)
     if C != 2 or a.rounds != 1:
         result.update(channels=C, rounds=a.rounds)
     produced = [0]
