@@ -128,6 +128,15 @@ extern "C" {
     fn rsmp_f32_to_pcm_shaped_device(d_in: *const f32, n_values: usize, bits: c_int, gain: f32, dither: c_int, shape: c_int, channels: u32, seed: u64,
                                      first_index: u64, d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats,
                                      stream: *mut std::os::raw::c_void) -> c_int;
+    // addition: the converters over many streams in one launch (rsmp_pcm_batch_*), and the decoder's definition on the host
+    fn rsmp_pcm_batch_new(max_streams: usize, device: c_int) -> *mut rsmp_pcm_batch;
+    fn rsmp_pcm_batch_free(b: *mut rsmp_pcm_batch);
+    fn rsmp_pcm_batch_f32_to_pcm_device(b: *mut rsmp_pcm_batch, items: *const PcmBatchItem, n: usize, bits: c_int, dither: c_int, shape: c_int,
+                                        stream: *mut c_void) -> c_int;
+    fn rsmp_pcm_batch_pcm_to_f32_device(b: *mut rsmp_pcm_batch, items: *const PcmBatchItem, n: usize, bits: c_int, stream: *mut c_void) -> c_int;
+    fn rsmp_pcm_batch_tile_values() -> usize;
+    fn rsmp_pcm_batch_last_grid(b: *const rsmp_pcm_batch, workgroups: *mut u32, tiles: *mut u64) -> c_int;
+    fn rsmp_pcm_to_f32(pcm: *const c_void, n_samples: usize, bits: c_int, out: *mut f32) -> c_int;
     fn rsmp_fir_set_pcm_stats(r: *mut rsmp_fir, enable: c_int) -> c_int;
     fn rsmp_fir_pcm_stats(r: *mut rsmp_fir, stats: *mut PcmStats) -> c_int;
     fn rsmp_fir_pcm_stats_clear(r: *mut rsmp_fir) -> c_int;
@@ -435,6 +444,62 @@ pub fn f32_to_pcm_stats(input: &[f32], bits: u32, dither: Dither, seed: u64, fir
 pub unsafe fn f32_to_pcm_stats_device(d_in: *const f32, n_values: usize, bits: u32, dither: Dither, seed: u64, first_index: u64,
                                       d_pcm: *mut std::os::raw::c_void, d_stats: *mut PcmStats) -> Result<(), ResampleError> {
     status(rsmp_f32_to_pcm_stats_device(d_in, n_values, bits as c_int, dither as c_int, seed, first_index, d_pcm, d_stats, std::ptr::null_mut()))
+}
+
+/// One stream of a batched conversion (rsmp_pcm_batch_item, 64 bytes): device pointers, the length in values, and -- for f32 -> PCM --
+/// the stream's seed, first index, statistics block (or null), gain and channel count.  `reserved` is 0.
+#[derive(Clone, Copy, Debug)]
+#[repr(C)]
+pub struct PcmBatchItem {
+    pub src: *const c_void,
+    pub dst: *mut c_void,
+    pub n_values: u64,
+    pub seed: u64,
+    pub first_index: u64,
+    pub stats: *mut PcmStats,
+    pub gain: f32,
+    pub channels: u32,
+    pub reserved: u64,
+}
+const _: () = assert!(core::mem::size_of::<PcmBatchItem>() == 64);
+
+#[repr(C)]
+pub struct rsmp_pcm_batch { _private: [u8; 0] }
+
+/// Batched PCM converters (rsmp_pcm_batch_*, include/resampler_amd.h): many device buffers in one launch.  Per stream the bytes and
+/// statistics are `f32_to_pcm_shaped`'s, the decoded values `pcm_to_f32`'s.  Calls are asynchronous on the null stream.
+pub struct PcmBatch { handle: *mut rsmp_pcm_batch }
+
+impl PcmBatch {
+    pub fn new(max_streams: usize, device: i32) -> Option<PcmBatch> {
+        let handle = unsafe { rsmp_pcm_batch_new(max_streams, device as c_int) };
+        if handle.is_null() { None } else { Some(PcmBatch { handle }) }
+    }
+    /// Values of one tile (a multiple of 4; a tile never holds values of two streams).
+    pub fn tile_values() -> usize { unsafe { rsmp_pcm_batch_tile_values() } }
+    pub unsafe fn f32_to_pcm_device(&mut self, items: &[PcmBatchItem], bits: u32, dither: Dither, shape: DitherShape) -> Result<(), ResampleError> {
+        status(rsmp_pcm_batch_f32_to_pcm_device(self.handle, items.as_ptr(), items.len(), bits as c_int, dither as c_int, shape as c_int, std::ptr::null_mut()))
+    }
+    pub unsafe fn pcm_to_f32_device(&mut self, items: &[PcmBatchItem], bits: u32) -> Result<(), ResampleError> {
+        status(rsmp_pcm_batch_pcm_to_f32_device(self.handle, items.as_ptr(), items.len(), bits as c_int, std::ptr::null_mut()))
+    }
+    /// (workgroups, tiles) of the last accepted call.
+    pub fn last_grid(&self) -> (u32, u64) {
+        let (mut wg, mut tiles) = (0u32, 0u64);
+        unsafe { rsmp_pcm_batch_last_grid(self.handle, &mut wg, &mut tiles) };
+        (wg, tiles)
+    }
+}
+
+impl Drop for PcmBatch {
+    fn drop(&mut self) { unsafe { rsmp_pcm_batch_free(self.handle) } }
+}
+
+/// Little-endian PCM of `bits` (16 / packed 24 / 32) -> f32 on the host (rsmp_pcm_to_f32: the decoder's definition).
+pub fn pcm_to_f32(pcm: &[u8], bits: u32) -> Result<Vec<f32>, ResampleError> {
+    let n = if bits == 16 || bits == 24 || bits == 32 { pcm.len() / (bits as usize / 8) } else { 0 };
+    let mut out = vec![0.0f32; n];
+    status(unsafe { rsmp_pcm_to_f32(pcm.as_ptr() as *const c_void, n, bits as c_int, out.as_mut_ptr()) }).map(|_| out)
 }
 
 /// impl fmt::Debug for ResamplerFir (src/resampler_fir.rs:203-211): channels, taps, phases, `..`

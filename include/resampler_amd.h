@@ -583,6 +583,56 @@ int rsmp_f32_to_pcm_shaped_device(const float* d_in, size_t n_values, int bits, 
  * RSMP_ERR_INVALID_ARGUMENT, *gain untouched, when the peak is 0 or not finite, when the result is no accepted gain, or for a null
  * pointer.  The second pass's peak is target_peak to within two f32 roundings (the quotient and the product). */
 int rsmp_pcm_normalise_gain(const rsmp_pcm_stats* stats, float target_peak, float* gain);
+/* Batched converters: the two directions above over MANY buffers in ONE launch, each buffer -- a "stream" -- with its own length,
+ * seed, first index, gain, channel count and statistics block.  What every PCM entry that refuses a launch points to (take f32 and
+ * convert) then costs one launch per batch, not one per stream: FIR streams of 1, 3 or 5 channels, ResamplerFft launches the pair
+ * kernel does not serve, every lock-step step or run, PCM input of any channel count.
+ * One stream of a batched conversion; 64 bytes; host memory, copied by the call. */
+typedef struct rsmp_pcm_batch_item {
+    const void*     src;          /* device. to PCM: f32, 16-byte aligned.  to f32: PCM, 4-byte aligned */
+    void*           dst;          /* device. to PCM: 4-byte aligned; may be NULL where stats != NULL (measure only).  to f32: 16-byte aligned */
+    uint64_t        n_values;     /* frames * channels; 0: the stream is skipped, src / dst may be NULL */
+    uint64_t        seed;         /* TPDF */
+    uint64_t        first_index;  /* index of the stream's value 0 (wraps in 64 bits) */
+    rsmp_pcm_stats* stats;        /* device, 8-byte aligned, or NULL; the call's statistics are MERGED into it */
+    float           gain;         /* rsmp_f32_to_pcm_gain's rule and range; 1 = none */
+    uint32_t        channels;     /* >= 1; only the high-pass lag reads it */
+    uint64_t        reserved;     /* 0 */
+} rsmp_pcm_batch_item;
+/* The handle owns the descriptor tables of its calls -- a small ring of pinned host tables and their device twins, each of
+ * max_streams entries (1 .. 2^24), ordered by events -- and knows its device's size.  NULL + rsmp_last_error() on failure.  Not
+ * thread-safe.  rsmp_pcm_batch_free waits for the handle's launches that still read a table, and takes NULL. */
+typedef struct rsmp_pcm_batch rsmp_pcm_batch;
+rsmp_pcm_batch* rsmp_pcm_batch_new(size_t max_streams, int device);
+void rsmp_pcm_batch_free(rsmp_pcm_batch* b);
+/* f32 -> PCM.  For every stream the bytes are exactly those of rsmp_f32_to_pcm_shaped over the stream's n_values values with its
+ * gain, seed, first_index and channels and the call's bits, dither and shape; exactly n_values * bits / 8 bytes are written per
+ * stream and none outside.  Where stats != NULL, that function's statistics of the stream are MERGED into *stats by the rule of
+ * rsmp_f32_to_pcm_stats_device (zeroed by the caller; two items may name one block); dst may then be NULL: measure only.
+ * Streams without a block are not counted at all, and a batch without any runs kernels that cannot count.
+ * Asynchronous on `stream`; `items` may be changed or freed when the call returns; calls on one handle may follow each other on
+ * the same or on different streams without a host wait (the host waits only when more calls than the ring has tables -- four --
+ * are in flight).  Buffers of one call must not overlap.
+ * RSMP_ERR_INVALID_ARGUMENT, decided before anything is enqueued and with nothing written: a null handle; null items with n > 0;
+ * n > max_streams; unknown bits, dither or shape; a gain outside the accepted range; channels == 0; reserved != 0; a misaligned
+ * pointer, src == NULL, or dst == NULL without stats, where n_values > 0; a batch of more than 2^32 - 1 tiles
+ * (rsmp_pcm_batch_tile_values).  n == 0, or every stream empty: RSMP_OK without a launch. */
+int rsmp_pcm_batch_f32_to_pcm_device(rsmp_pcm_batch* b, const rsmp_pcm_batch_item* items, size_t n, int bits, int dither, int shape,
+                                     void* stream);
+/* PCM -> f32.  Reads src, dst and n_values (and reserved, which must be 0); stats must be NULL.  Sample j of a stream becomes
+ * s / 2^(bits-1), with the reference's divisor -2^31 at 32 bits (resample/src/main.rs:131) -- the value the fused PCM-input loads
+ * give, bit-equal to rsmp_pcm_to_stereo_f32_device for two channels and to rsmp_pcm_to_f32.  It decodes samples, whatever the
+ * channel count: no mono duplication.  Ordering and refusals as above. */
+int rsmp_pcm_batch_pcm_to_f32_device(rsmp_pcm_batch* b, const rsmp_pcm_batch_item* items, size_t n, int bits, void* stream);
+/* Diagnostics: the values of one tile of the batched converters (a multiple of 4; a tile never holds values of two streams), and
+ * the grid of the handle's last accepted call: its workgroups and the tiles they shared (0, 0 where nothing was launched).  A
+ * counting launch issues at most 4 x (workgroups + stream changes seen by workgroups) atomics.  Either pointer may be NULL. */
+size_t rsmp_pcm_batch_tile_values(void);
+int rsmp_pcm_batch_last_grid(const rsmp_pcm_batch* b, uint32_t* workgroups, uint64_t* tiles);
+/* The decoder's definition: host memory, needs no device.  n_samples little-endian samples of `bits` (16, packed 24, 32) ->
+ * out[j] = f32(s) / 2^(bits-1), the divisor -2^31 at 32 bits.  Unknown bits or a null buffer with n_samples > 0:
+ * RSMP_ERR_INVALID_ARGUMENT. */
+int rsmp_pcm_to_f32(const void* pcm, size_t n_samples, int bits, float* out);
 /* Measurement aid (no counterpart in the reference): a plain streaming copy of n_values floats, 16 bytes per lane --
  * the rate a kernel that reads as much as it writes can reach on this GPU; bench.py reports it next to every
  * roofline fraction.  16-byte aligned device pointers, n_values a multiple of 4, asynchronous on `stream`. */

@@ -120,6 +120,19 @@ class PcmStats(C.Structure):
         return "PcmStats(values=%d, clipped=%d, nans=%d, peak=%r)" % self.as_tuple()
 
 
+class PcmBatchItem(C.Structure):
+    """One stream of a batched conversion (rsmp_pcm_batch_item, 64 bytes): device pointers as integers, the stream's length in
+    values, and -- for f32 -> PCM -- its seed, first index, statistics block (or None), gain and channel count."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n_values", C.c_uint64), ("seed", C.c_uint64), ("first_index", C.c_uint64),
+                ("stats", C.c_void_p), ("gain", C.c_float), ("channels", C.c_uint32), ("reserved", C.c_uint64)]
+
+    def __init__(self, src=None, dst=None, n_values=0, seed=0, first_index=0, stats=None, gain=1.0, channels=1, reserved=0):
+        super().__init__(src or None, dst or None, int(n_values), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index) & 0xFFFFFFFFFFFFFFFF,
+                         stats or None, float(gain), int(channels), int(reserved))
+
+
+assert C.sizeof(PcmBatchItem) == 64, C.sizeof(PcmBatchItem)
+
 RSMP_OK = 0
 _U64 = 0xFFFFFFFFFFFFFFFF
 _f32p = C.POINTER(C.c_float)
@@ -237,6 +250,13 @@ _SIGNATURES = [
     ("rsmp_f32_to_pcm_shaped_device", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
     ("rsmp_pcm_normalise_gain", C.c_int, [C.POINTER(PcmStats), C.c_float, C.POINTER(C.c_float)]),
+    ("rsmp_pcm_batch_new", C.c_void_p, [C.c_size_t, C.c_int]),
+    ("rsmp_pcm_batch_free", None, [C.c_void_p]),
+    ("rsmp_pcm_batch_f32_to_pcm_device", C.c_int, [C.c_void_p, C.POINTER(PcmBatchItem), C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("rsmp_pcm_batch_pcm_to_f32_device", C.c_int, [C.c_void_p, C.POINTER(PcmBatchItem), C.c_size_t, C.c_int, C.c_void_p]),
+    ("rsmp_pcm_batch_tile_values", C.c_size_t, []),
+    ("rsmp_pcm_batch_last_grid", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("rsmp_pcm_to_f32", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     ("rsmp_device_stream_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rsmp_fft_new", C.c_void_p, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     ("rsmp_fft_free", None, [C.c_void_p]),
@@ -1160,6 +1180,68 @@ def f32_to_pcm_stats_device(d_in, bits: int, d_pcm, d_stats, stream: Optional[in
     _check(lib().rsmp_f32_to_pcm_stats_device(C.c_void_p(_dev_ptr(d_in)), n, bits, int(dither), int(seed) & _U64, int(first_index) & _U64,
                                               C.c_void_p(d_pcm.data_ptr()) if d_pcm is not None else None, C.c_void_p(d_stats.data_ptr()),
                                               C.c_void_p(stream or 0)))
+
+
+def pcm_to_f32(pcm, bits: int) -> np.ndarray:
+    """Little-endian PCM bytes of `bits` (16 / packed 24 / 32) -> f32 on the host, no device needed (rsmp_pcm_to_f32: the decoder's
+    definition): s / 2^(bits-1), with the reference's divisor -2^31 at 32 bits.  Any channel count: it decodes samples."""
+    raw = np.frombuffer(bytes(pcm), np.uint8) if not isinstance(pcm, np.ndarray) else np.ascontiguousarray(pcm).view(np.uint8).reshape(-1)
+    n = raw.size // (bits // 8) if bits in (16, 24, 32) else 0
+    out = np.empty(n, np.float32)
+    _check(lib().rsmp_pcm_to_f32(C.c_void_p(raw.ctypes.data) if raw.size else None, n, bits, C.c_void_p(out.ctypes.data) if n else None))
+    return out
+
+
+def pcm_batch_tile_values() -> int:
+    """Values of one tile of the batched converters (rsmp_pcm_batch_tile_values)."""
+    return int(lib().rsmp_pcm_batch_tile_values())
+
+
+class PcmBatch:
+    """Batched PCM converters (rsmp_pcm_batch_*): f32 -> PCM and PCM -> f32 over many device buffers in one launch, each stream a
+    PcmBatchItem with its own length, seed, first index, gain, channel count and statistics block.  The bytes and statistics are
+    f32_to_pcm_stats's per stream (rsmp_f32_to_pcm_shaped), the decoded values pcm_to_f32's.  Not thread-safe."""
+
+    def __init__(self, max_streams: int, device: int = 0):
+        self._h = lib().rsmp_pcm_batch_new(int(max_streams), int(device))
+        if not self._h:
+            raise ResampleError(4, last_error())
+        self.max_streams = int(max_streams)
+
+    @staticmethod
+    def _array(items):
+        if isinstance(items, C.Array):
+            return items, len(items)
+        items = list(items)
+        return (PcmBatchItem * max(1, len(items)))(*items), len(items)
+
+    def f32_to_pcm_device(self, items, bits: int, dither: int = 0, shape: int = 0, stream: Optional[int] = None) -> None:
+        """items: PcmBatchItems (a sequence or a ctypes array) -- src f32, dst PCM bytes (or None with stats: measure only), stats a
+        zeroed 32-byte block the statistics are merged into, or None.  Asynchronous on `stream`; items may be reused on return."""
+        arr, n = self._array(items)
+        _check(lib().rsmp_pcm_batch_f32_to_pcm_device(self._h, arr, n, int(bits), int(dither), int(shape), C.c_void_p(stream or 0)))
+
+    def pcm_to_f32_device(self, items, bits: int, stream: Optional[int] = None) -> None:
+        """items: src PCM bytes, dst f32, n_values samples; nothing else is read (stats must be None)."""
+        arr, n = self._array(items)
+        _check(lib().rsmp_pcm_batch_pcm_to_f32_device(self._h, arr, n, int(bits), C.c_void_p(stream or 0)))
+
+    def last_grid(self) -> Tuple[int, int]:
+        """(workgroups, tiles) of the last accepted call; (0, 0) where it launched nothing."""
+        wg, tiles = C.c_uint32(), C.c_uint64()
+        _check(lib().rsmp_pcm_batch_last_grid(self._h, C.byref(wg), C.byref(tiles)))
+        return int(wg.value), int(tiles.value)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().rsmp_pcm_batch_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def normalise_gain(stats: "PcmStats", target_peak: float) -> float:
