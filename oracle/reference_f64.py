@@ -214,7 +214,7 @@ M_RMS_CAP = 3.0
 M_MAX_CAP = 4.0
 # (M_RMS, M_MAX) per kernel family: 1.25 x the worst ratio over the family's cases in tests/test_accuracy_f64_gpu.py
 # ("fft_pair_io": tests/test_fft_pair_builds_gpu.py, "fft_wave_builds": tests/test_fft_wave_builds_gpu.py, "fft_workgroup":
-# tests/test_fft_workgroup_builds_gpu.py, "lockstep_step_*": tests/test_fir_lockstep_paths_gpu.py, "fir_generic": tests/test_fir_generic_builds_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
+# tests/test_fft_workgroup_builds_gpu.py, "lockstep_step_*": tests/test_fir_lockstep_paths_gpu.py, "fir_generic": tests/test_fir_generic_builds_gpu.py, "fir_split_builds": tests/test_fir_split_builds_gpu.py) on an MI355X, rounded up to one decimal -- profiles/accuracy_f64.txt (tools/accuracy_f64.py) has every case's ratios.
 MARGINS = {
     "fir_bulk": (1.5, 1.6),    # worst x1.191 / x1.256: the f32 periodic kernels (pre-mixed rows); the split kernel x0.78 / x0.92
     "lockstep": (1.0, 1.1),    # worst x0.784 / x0.867
@@ -244,6 +244,13 @@ MARGINS = {
     # rows lie at x0.82-0.89 RMS, the 128-tap rows at x0.43-0.53: four lanes of a group carry four taps each at 16 taps, so the
     # eight-partial-sum form gains less over the scalar sum ("2ch-44100-48001-Sample8-Auto" under fir_bulk: x0.84)
     "fir_generic": (1.2, 1.0),
+    # tests/test_fir_split_builds_gpu.py: every f32 build of the split kernel in steady state -- workgroups of about twenty items, ring
+    # slots reused, scales predicted, streams at levels from 2^-12 to 300 -- and the shared launches, every noise stream of every
+    # launch gated on its own (975 rows, as few as 960 values): worst x1.348 (2 channels 44.1 -> 48 kHz, 16 taps, the stream at level 300 of
+    # a shared batch) / x1.518 (48 -> 44.1 kHz, 32 taps, the same stream's second launch).  The 16 rows above x1.25 RMS are all the level-300
+    # stream at 16 taps: 300 x noise has 24-bit mantissas, of which two fp16 planes keep 22 -- worth x0.70 of the yardstick at 16 taps on
+    # its own (x0.30 at 128) --, while the level-1 noise of every other row lies on a 2^-23 grid that the planes hold exactly
+    "fir_split_builds": (1.7, 1.9),
 }
 # The (family, block) builds of fft_kernels.hip whose every case in profiles/accuracy_f64.txt (the rows of "fft_workgroup", their last
 # column) was bit-equal to the scalar spec, OracleFft(1, .., simd=False) per channel: tests/test_fft_workgroup_builds_gpu.py asserts

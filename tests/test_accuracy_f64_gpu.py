@@ -61,7 +61,7 @@ def gate(family, label, y, ref, yard):
 
 def test_margins_respect_their_conditions():
     assert set(R.MARGINS) == {"fir_bulk", "lockstep", "fft", "fft_pair_io", "fft_wave_builds", "fft_workgroup", "lockstep_step_split",
-                              "lockstep_step_f32", "lockstep_step_ref", "fir_generic"}   # (every family in use is held under the caps)
+                              "lockstep_step_f32", "lockstep_step_ref", "fir_generic", "fir_split_builds"}   # (every family in use is held under the caps)
     for family, (m_rms, m_max) in R.MARGINS.items():
         assert 0.0 < m_rms <= R.M_RMS_CAP and 0.0 < m_max <= R.M_MAX_CAP, family
 

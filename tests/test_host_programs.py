@@ -666,3 +666,98 @@ def test_fir_generic_builds_fixture_names_every_build(tmp_path):
         assert [fx[g.TILED[i].name, k, "switched"]["reason"] for k in range(3)] == ["switched_off"] * 3
     assert [g.TILED_BUILDS[i][:2] for i in g.SWITCHED] == [(2, 1), (0, 1)] and g.TILED[g.SWITCHED[1]].streams[0][0] == 3
     assert build(fx[g.RUNS.name, 0, None]) == (2, 1, 4096) and g.RUNS.chunk == 8
+
+
+# ---- the builds of the split FIR kernel that tests/test_fir_split_builds_gpu.py runs in steady state ----------------------------------
+def test_fir_split_builds_fixture_names_every_build(tmp_path, geometry_dump):
+    """tests/host/fir_split_builds_dump.cpp (plain C++, g++ with ASan + UBSan, linked with fir_geometry.cpp and fir_split_deal.cpp): its
+    sweep of fir_geometry_dump.cpp's rates, tap counts and channel counts, and what periodic_geometry, split_build_for, periodic_blocks
+    and split_deal answer to every launch of tests/test_fir_split_builds_gpu.py, with the item order and the workgroups' item ranges
+    for 256 compute units -- byte for byte tests/golden/fir_split_builds.json, which so cannot go stale.  From the fixture, the GPU
+    module's own lists and the kernel file:
+      - the sweep's (NK, WIDE, ROUNDS, groups, images) are the 46 that the rows of fir_geometry_dump.cpp's default mode reach, and
+        every one has a case at the rate pair with the smallest b; 6, 8 and 16 channels run once more at the one-round NK 5 build;
+      - every f32, non-diagnostic, two-plane build of split_kernel_for's list (fir_split.hip) has a case: 24 builds;
+      - NK 4 is reached by one row for each of WIDE 0, 2 and 3 and by five for WIDE 1;
+      - the geometry, build, item count, item order, ranges and marked items the module derives on its own are the recorded ones, the
+        recorded chunk lengths are the ones its search finds, and where den is no power of two the five noise streams have at least 8
+        class-0 outputs on row 1023 and 8 on another row;
+      - every case meets the coverage conditions (i) .. (v) and places A, Q, C, F, L and the ragged fillers as its docstring says;
+      - the shared batches are one multi-build launch of two jobs, one all-kernel launch of three bodies with a two-group job, and
+        three single-job launches of the multi builds NK 1, 2, 3; every job, sized against the recorded deal, meets the conditions."""
+    import re
+    import test_fir_split_builds_gpu as s   # (its lists of cases: nothing of them needs a GPU)
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/host/fir_split_builds_dump.cpp"
+    exe = str(tmp_path / "fir_split_builds_dump")
+    subprocess.run([gxx] + SANITIZE + [os.path.join(ROOT, "tests", "host", "fir_split_builds_dump.cpp"), os.path.join(CSRC, "fir_geometry.cpp"),
+                                       os.path.join(CSRC, "fir_split_deal.cpp"), "-o", exe], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RSMP_")}
+    run = subprocess.run([exe, str(s.FIXTURE_CUS)], input=s.requests(), env=env, capture_output=True, text=True, timeout=300)
+    _clean(run)
+    with open(os.path.join(ROOT, "tests", "golden", "fir_split_builds.json")) as fh:
+        text = fh.read()
+    assert run.stdout == text, "tests/golden/fir_split_builds.json is not what tests/host/fir_split_builds_dump.cpp prints"
+    doc = json.loads(text)
+    assert doc["cus"] == s.FIXTURE_CUS == 256
+
+    # ---- the sweep against fir_geometry_dump.cpp's rows of the default mode
+    walk = subprocess.run([geometry_dump], env=_setting_env("default"), capture_output=True, text=True, timeout=300)
+    _clean(walk)
+    reached = set()
+    for row in walk.stdout.splitlines():
+        head, geo, build = row.split(" | ")
+        g = geo.split()
+        if head.split()[2] != "0" or g[0] != "1" or g[14] != "3":
+            continue
+        nk, planes, diag, wide, rounds, bits = (int(v) for v in build.split()[0][len("split:"):].split(","))
+        assert (planes, diag, bits) == (2, 0, 0)
+        reached.add((nk, wide, rounds, int(g[16]), int(g[13])))
+    swept = [s.fields(row.split(" | ")[0]) for row in doc["sweep"]]
+    assert {(c["nk"], c["wide"], c["rounds"], c["groups"], c["images"]) for c in swept} == reached and len(swept) == len(reached) == 46
+    assert {c["groups"] for c in swept} == {1, 2} and {c["images"] for c in swept} == {2, 3, 4}
+    combos = [(c.nk, c.wide, c.rounds, c.groups, c.images) for c in s.CASES]
+    assert set(combos[:46]) == reached and len(s.CASES) == 49
+    assert [(c.nk, c.wide, c.rounds, c.groups, c.ch) for c in s.CASES[46:]] == [(5, 1, 1, 1, ch) for ch in (6, 8, 16)]
+    assert all(c.ch == {0: 2, 1: 4, 2: 1, 3: 3}[c.wide] for c in s.CASES[:46])
+    for c, row in zip(s.CASES, doc["sweep"]):   # (the smallest b of its combination: the sweep says which row that is)
+        at = s.fields(row.split(" | ")[2])
+        assert (c.taps, c.ch, c.in_hz, c.out_hz, c.a, c.b) == (at["taps"], at["ch"], at["in"], at["out"], at["a"], at["b"])
+
+    # ---- every build of the kernel's list
+    with open(os.path.join(CSRC, "fir_split.hip")) as fh:
+        hip = fh.read()
+    table = hip[hip.index("table[] = {", hip.index("const void* split_kernel_for(")):]
+    table = table[:table.index("};")]
+    listed = set()
+    for planes, diag, wide in re.findall(r"RSMP_SPLIT_1TO5\((\d), (false|true), (\d)\)", table):
+        listed |= {(nk, int(planes), diag, int(wide), 1, 0) for nk in range(1, 6)}
+    for nk, planes, diag, wide, rounds, bits in re.findall(r"RSMP_SPLIT\((\d), (\d), (false|true), (\d), (\d), (\d+)\)", table):
+        listed.add((int(nk), int(planes), diag, int(wide), int(rounds), int(bits)))
+    plain = {(b[0], b[3], b[4]) for b in listed if b[1] == 2 and b[2] == "false" and b[5] == 0}
+    assert len(plain) == 24 and plain == {(c.nk, c.wide, c.rounds) for c in s.CASES}
+    assert plain == {(nk, w, 1) for nk in range(1, 6) for w in range(4)} | {(nk, w, 2) for nk in (5, 6) for w in (0, 1)}
+    nk4 = [row.split(" | ")[0] for row in doc["nk4"]]
+    assert sorted(nk4) == ["wide=0"] + ["wide=1"] * 5 + ["wide=2", "wide=3"]
+
+    # ---- the cases: the record is what the module derives, and the conditions hold
+    for case in s.CASES:
+        chunks = s.chunks_of(case)
+        assert chunks == s.search_chunks(case) and chunks[0] != chunks[1] and set(chunks) <= set(s.CHUNKS), case.name
+        s.check_against_fixture(case)
+        runs, held = s.coverage(s.layout(case, s.FIXTURE_CUS), chunks)
+        assert min(runs["A"], runs["Q"]) >= case.images + 2 and held["C"] == 2 and held["A"] == 1
+        data_values = sum(case.ch * n for n in s.outputs_of(case, s.lengths_of(case, chunks)["full"], chunks)) * len(s.ROLES)
+        assert data_values <= 1250000, (case.name, data_values)   # (about a million gated values at the most: 16 channels, and 4 channels at b = 320)
+    assert sum(1 for c in s.CASES if c.den & (c.den - 1)) >= 20
+
+    # ---- the shared batches
+    seen = []
+    for sc, want in zip(s.SHARED, s.SHARED_LAUNCHES):
+        cases, lays, reported = s.shared_layouts(sc, s.FIXTURE_CUS)
+        assert s.launch_groups(cases) == want and all(c.ch == 2 and c.wide == 0 for c in cases)
+        for launch in reported:
+            assert sum(w for _, w in launch) <= s.FIXTURE_CUS and all(0 < w <= items for items, w in launch)
+        seen.append([(c.nk, c.rounds, c.groups) for c in cases])
+    assert seen[0] == [(5, 1, 1), (5, 1, 1)] and seen[1] == [(5, 1, 1), (6, 2, 1), (5, 1, 2)] and seen[2] == [(1, 1, 1), (3, 1, 1), (2, 1, 1)]
+    assert all((nk, r) in s.ALL_KERNEL_BUILDS for nk, r, _ in seen[1])

@@ -654,3 +654,138 @@ def test_a_tiled_kernel_defect_fails_the_generic_gate(name):
     assert changed > 0
     m_rms, m_max = R.MARGINS["fir_generic"]
     assert r_rms > max(m_rms, R.M_RMS_CAP) and r_max > max(m_max, R.M_MAX_CAP), (r_rms, r_max, R.MARGINS["fir_generic"])
+
+
+# ---- the split kernel in steady state (tests/test_fir_split_builds_gpu.py) can fail its gate ------------------------------------------
+SPLIT_DEFECTS = ["an item of Q cut into fp16 planes at the scale of the item before it, A's last block",
+                 "the class-0 outputs of an item on the ordinary row where the replay says row 1023",
+                 "the class-0 outputs of an item on row 1023 where the replay says the ordinary row",
+                 "a tile of the second tile group evaluated with the first group's coefficients",
+                 "the last 32-tap step of the window dropped for one tile"]
+
+
+def two_fp16_planes(x, peak):
+    """s x = h1 + h2 + r: a power of two s that puts `peak` into [2^14, 2^15), both planes fp16 by round to nearest (DESIGN.md
+    section 4.1); returns (h1 + h2) / s as f32."""
+    s = np.float32(2.0 ** (14 - int(np.floor(np.log2(peak)))))
+    xs = (x * s).astype(np.float32)
+    h1 = xs.astype(np.float16).astype(np.float32)
+    h2 = (xs - h1).astype(np.float16).astype(np.float32)
+    return ((h1.astype(np.float64) + h2.astype(np.float64)) / float(s)).astype(np.float32)
+
+
+def split_defect_case(s, name):
+    """(case, role): the smallest case of the defect's kind -- the fewest values in a noise stream's first launch."""
+    def size(c):
+        return c.ch * s.outputs_of(c, s.lengths_of(c, s.chunks_of(c))["full"], s.chunks_of(c))[0]
+
+    def both_rows(c):
+        if c.den & (c.den - 1) == 0:
+            return False
+        rows = s.case_data(c)["F"]["launches"][0].pos.phase1[::c.den]
+        return bool((rows == 1023).any() and (rows[16 * c.b // c.den:] != 1023).any())   # (an ordinary one behind the first item)
+
+    if "class-0" in name:
+        cases = [c for c in sorted(s.CASES, key=size) if c.den & (c.den - 1)]
+        return next(c for c in cases if both_rows(c)), "F"
+    # (the second group against the first: a period of the phase pattern that 160 classes are no multiple of)
+    cases = [c for c in s.CASES if c.groups == 2 and 160 % c.den] if "tile group" in name else s.CASES
+    return min(cases, key=size), ("Q" if name == SPLIT_DEFECTS[0] else "F")
+
+
+def split_defect(s, case, role, name):
+    """The f64 evaluation of the first launch of one noise stream with one defect in ONE item (16 periods of the stream)."""
+    d = s.case_data(case)[role]
+    la, x = d["launches"][0], d["x"]
+    ch, lat, in_hz, out_hz = s.spec_of(case)
+    coeffs = R.fir_table(in_hz, out_hz, case.taps, 90)
+    pos, n_out, b = la.pos, len(la.pos), case.b
+    item = 16 * b                                   # outputs of an item
+    assert n_out > 3 * item
+    if name == SPLIT_DEFECTS[0]:
+        frames = slice(0, 16 * case.a + case.taps)  # (the first item of Q: the one whose slot A's last block left)
+        xq = x.reshape(-1, ch).copy()
+        same = xq.copy()
+        same[frames] = two_fp16_planes(xq[frames], 1.0)
+        assert np.array_equal(same, xq), "a scale 2^12 above Q's own already costs a sample of Q something"
+        xq[frames] = two_fp16_planes(xq[frames], s.LOUD_END)
+        return R.fir_f64(xq.reshape(-1), ch, coeffs, pos), la
+    q = copy.copy(pos)
+    q.index, q.phase1, q.phase2, q.frac = pos.index.copy(), pos.phase1.copy(), pos.phase2.copy(), pos.frac.copy()
+    if "class-0" in name:
+        want = 1023 if name == SPLIT_DEFECTS[1] else 0
+        class0 = np.arange(0, n_out, case.den)
+        hit = class0[(pos.phase1[class0] == 1023) == (want == 1023)]
+        hit = hit[hit >= item] if (hit >= item).any() else hit   # (not the first item where another has one: output 0 has no frame before it)
+        first = hit[0] // item * item
+        k = class0[(class0 >= first) & (class0 < first + item)]
+        k = k[(pos.phase1[k] == 1023) == (want == 1023)]
+        assert k.size >= 1
+        if want == 1023:    # row 1023 of the frame before -> the ordinary row: row 0 at the integer position
+            q.index[k], q.phase1[k], q.phase2[k], q.frac[k] = pos.index[k] + 1, 0, 1, 0.0
+        else:               # ... and the reverse
+            q.index[k], q.phase1[k], q.phase2[k], q.frac[k] = pos.index[k] - 1, 1023, 1023, 0.0
+        assert int(q.index.min()) >= 0
+        return R.fir_f64(x, ch, coeffs, q), la
+    n = np.arange(item, 2 * item)                   # the second item
+    if name == SPLIT_DEFECTS[3]:
+        k = n[(n % b >= 160) & (n % b < 176)]       # tile 10, the first of the second group, with the coefficients of tile 0
+        assert case.groups == 2 and k.size == 16 * 16
+        q.phase1[k], q.phase2[k], q.frac[k] = pos.phase1[k - 160], pos.phase2[k - 160], pos.frac[k - 160]
+        return R.fir_f64(x, ch, coeffs, q), la
+    assert name == SPLIT_DEFECTS[4]
+    k = n[n % b < 16]                               # tile 0
+    shift = (k % b) * case.a // b                   # the class's window starts this many frames behind the tile's
+    y = la.ref.reshape(-1, ch).copy()
+    xs = x.reshape(-1, ch).astype(np.float64)
+    f = pos.frac[k]
+    dropped = 0
+    for t in range(case.taps):
+        late = shift + t >= 32 * (case.nk - 1)
+        w = (np.float32(1.0) - f).astype(np.float64) * coeffs[pos.phase1[k], t] + f.astype(np.float64) * coeffs[pos.phase2[k], t]
+        y[k[late]] -= w[late, None] * xs[pos.index[k[late]] + t]
+        dropped += int(late.sum())
+    assert dropped > 0
+    return y.reshape(-1), la
+
+
+def test_a_clean_f32_result_passes_the_split_builds_gate():
+    """The f64 sums of the smallest case's streams rounded to f32 pass at the family's margins, part by part."""
+    import test_fir_split_builds_gpu as s
+    case, _ = split_defect_case(s, SPLIT_DEFECTS[4])
+    m_rms, m_max = R.MARGINS["fir_split_builds"]
+    data = s.case_data(case)
+    for role in s.ROLES:
+        for k, la in enumerate(data[role]["launches"]):
+            for suffix, mask, _ in s.gated_parts(case, role, k, data):
+                ref, yard = (la.ref, la.yard) if mask is None else (la.ref[mask], la.yard[mask])
+                r_rms, r_max = R.budget(ref.astype(np.float32), ref, yard)
+                assert r_rms <= min(1.0, m_rms) and r_max <= min(1.0, m_max), (role, k, suffix, r_rms, r_max)
+
+
+@pytest.mark.parametrize("name", SPLIT_DEFECTS)
+def test_a_split_kernel_defect_fails_the_split_builds_gate(name):
+    """Each defect applied to ONE item -- 16 periods of one stream, what one ring slot holds -- of the f64 evaluation of the first launch
+    of a noise stream of the smallest case it can occur in, the result rounded to f32: a kernel whose ONLY fault is the defect, gated as
+    tests/test_fir_split_builds_gpu.py gates the stream.  Every defect fails "fir_split_builds" at its margins and at the caps.
+    The first one is why A's last block is 2^20 above Q: at the scale of a stream 2^12 above Q's level -- A's level 1 -- the two
+    planes still hold every bit of Q's samples (asserted: nothing changes), so a scale borrowed from such an item would not show.
+    Measured (values changed; RMS and max against f64 in multiples of the scalar spec's distance):
+      1 ch 176400 -> 48000 Hz, 64 taps (NK 4), 6383 values
+        an item of Q at the scale of A's last block         641    x4.84     x7.74
+        the last 32-tap step dropped for tile 0 (F)         112    x2.8e4    x1.2e5
+      1 ch 48000 -> 176400 Hz, 16 taps, 23 465 values (F)
+        class-0 outputs: row 1023 -> the ordinary row         2    x227      x3.0e3
+        class-0 outputs: the ordinary row -> row 1023        16    x472      x3.4e3
+      1 ch 22050 -> 48000 Hz, 128 taps, two tile groups, 40 684 values (F)
+        tile 10 with tile 0's coefficients                  256    x3.6e5    x1.4e6"""
+    import test_fir_split_builds_gpu as s
+    case, role = split_defect_case(s, name)
+    y, la = split_defect(s, case, role, name)
+    y = y.astype(np.float32)
+    changed = int(np.count_nonzero(y != la.ref.astype(np.float32)))
+    r_rms, r_max = R.budget(y, la.ref, la.yard)
+    print(f"fir_split_builds {case.name} {role} ({la.ref.size} values) {name}: {changed} values changed; against f64 x{r_rms:.3g} rms, x{r_max:.3g} max")
+    assert 0 < changed <= case.ch * 16 * case.b + case.ch * case.taps * case.b // case.a + case.ch
+    m_rms, m_max = R.MARGINS["fir_split_builds"]
+    assert r_rms > max(m_rms, R.M_RMS_CAP) and r_max > max(m_max, R.M_MAX_CAP), (r_rms, r_max, R.MARGINS["fir_split_builds"])

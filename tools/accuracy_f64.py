@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Distances of the FIR and FFT kernels from the f64 reference (oracle/reference_f64.py), in multiples of the scalar
 spec's own distance: runs every case of tests/test_accuracy_f64_gpu.py, of tests/test_fft_pair_builds_gpu.py, of
-tests/test_fft_wave_builds_gpu.py, of tests/test_fft_workgroup_builds_gpu.py, of tests/test_fir_lockstep_paths_gpu.py and of tests/test_fir_generic_builds_gpu.py without asserting
+tests/test_fft_wave_builds_gpu.py, of tests/test_fft_workgroup_builds_gpu.py, of tests/test_fir_lockstep_paths_gpu.py, of tests/test_fir_generic_builds_gpu.py and of tests/test_fir_split_builds_gpu.py without asserting
 its ratios and writes the table the margins in oracle/reference_f64.py (MARGINS) are set from.  The rows of "fft_workgroup" say in one more column whether the case was
 bit-equal to the scalar oracle, and the last lines which (family, block) builds were in every case that ran them: FFT_WORKGROUP_BIT_EQUAL,
 and how far the tiled FIR kernel's results lie from the latency kernel's on the same input ("fir_generic", RSMP_FIR_GENERIC_BULK=0).
@@ -22,6 +22,7 @@ import test_fft_wave_builds_gpu as tw  # noqa: E402
 import test_fft_workgroup_builds_gpu as tg  # noqa: E402
 import test_fir_lockstep_paths_gpu as tl  # noqa: E402
 import test_fir_generic_builds_gpu as tn  # noqa: E402
+import test_fir_split_builds_gpu as ts  # noqa: E402
 from oracle import reference_f64 as R  # noqa: E402
 
 
@@ -44,9 +45,11 @@ def main() -> int:
     tl.measure_all()
     tn.ENFORCE = False
     tn.measure_all()
+    ts.ENFORCE = False
+    ts.measure_all()
     lines = ["# tools/accuracy_f64.py: every case of tests/test_accuracy_f64_gpu.py, tests/test_fft_pair_builds_gpu.py,",
-             "# tests/test_fft_wave_builds_gpu.py, tests/test_fft_workgroup_builds_gpu.py, tests/test_fir_lockstep_paths_gpu.py and",
-             "# tests/test_fir_generic_builds_gpu.py on one MI355X.",
+             "# tests/test_fft_wave_builds_gpu.py, tests/test_fft_workgroup_builds_gpu.py, tests/test_fir_lockstep_paths_gpu.py,",
+             "# tests/test_fir_generic_builds_gpu.py and tests/test_fir_split_builds_gpu.py on one MI355X.",
              "# ratio = error against the f64 reference / the scalar spec's error against it, over the same outputs;",
              "# 'spec' = the scalar spec's own RMS / max error (absolute).  Margin = 1.25 x the family's worst ratio, rounded up",
              "# to one decimal, capped at %.1f (RMS) / %.1f (max)." % (R.M_RMS_CAP, R.M_MAX_CAP),
@@ -56,7 +59,7 @@ def main() -> int:
     worst = {}
     assert [e[0] for e in tg.EQUAL] == [rec[1] for rec in tg.OBSERVED]
     equal_of = {label: eq for label, _, eq in tg.EQUAL}
-    for family, label, r_rms, r_max, s_rms, s_max, n in t.OBSERVED + tp.OBSERVED + tw.OBSERVED + tg.OBSERVED + tl.OBSERVED + tn.OBSERVED:
+    for family, label, r_rms, r_max, s_rms, s_max, n in t.OBSERVED + tp.OBSERVED + tw.OBSERVED + tg.OBSERVED + tl.OBSERVED + tn.OBSERVED + ts.OBSERVED:
         lines.append(f"{family:10s} {r_rms:9.3f}  {r_max:9.3f}  {s_rms:9.2e}  {s_max:9.2e}  {n:8d}  {label}")
         if family == tg.FAMILY:
             lines[-1] += "  bit-equal=" + ("yes" if equal_of[label] else "no")
